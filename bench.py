@@ -7,14 +7,22 @@ reference-order assembly of the rows with r2 > 0.05 and, for N>1, their RCCL
 gather to rank 0.  Inputs (site codes + weights) are resident in HBM before
 the timed region.  Total work is fixed as N grows (strong scaling).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c4|c2|c5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c4|c2|c5] [--full] [--dump-outputs DIR]
     torchrun --nproc-per-node N bench.py --gpus N ...      (one process per GPU)
+
+A plain run sets up, settles the clock, warms up, times the K steps and prints
+the result line (value, ms_per_step, dtype, config).  --full adds everything
+else, after the timed region: the device pre-pass check, per-launch HIP-event
+times and the roofline, the same steps without the screen, the CPU baseline
+and the rows checked against the oracle.  --dump-outputs DIR writes the rows
+of the last timed step (what a caller of the step receives) as DIR/<name>.npy,
+in arrays of one fixed length (dump_outputs).
 
 With --gpus N > 1 and no WORLD_SIZE in the environment, bench.py starts its
 own N ranks (one process per GPU, RANK/LOCAL_RANK/WORLD_SIZE set) before
 anything touches torch or the GPU, and relays rank 0's line; under torchrun
 WORLD_SIZE must equal --gpus.  Rank 0 prints ONE JSON line.  The CPU baseline
-(rank 0 at N=1, after the timed region; null at N>1) is the C restatement of the
+(--full; rank 0, after the timed region) is the C restatement of the
 lib.rs simd path (oracle/wld_oracle.c, "port"), threaded like rayon over
 256x256 chunks, timed on a bounded sample of the same workload.
 """
@@ -195,6 +203,37 @@ def planted_ld(L, N, seed=0x91A7, n_tiles=400, max_per_tile=3):
             buf[b] = col
             planted.append((a, b, p))
     return buf, planted
+
+
+DUMP_ROWS = 1 << 20  # row slots of a dump: 36 bytes each, 38 MB in all
+ROW_FIELDS = ("site_a", "site_b", "d", "d_prime", "r2")
+
+
+def dump_outputs(path, cols, seed=0xD0E5):
+    """--dump-outputs: the rows a caller of the timed step received from its
+    last step, in arrays of one fixed length (DUMP_ROWS slots, whatever the
+    step's row count, so that two builds' dumps compare slot for slot; a step
+    that returns no row, as the headline workload's does, gives all-empty
+    slots): DIR/<field>.npy per column in reference order (site indices as
+    float64, exact; d, d_prime, r2 as the float32 they are), row_index.npy
+    (each slot's position in the step's row list, -1 for an empty slot, whose
+    columns hold 0) and n_rows.npy (the step's row count).  More rows than
+    slots: a seeded sample of them, in order."""
+    os.makedirs(path, exist_ok=True)
+    n = len(cols["r2"])
+    if n > DUMP_ROWS:
+        idx = np.sort(np.random.Generator(np.random.PCG64(seed)).choice(n, size=DUMP_ROWS, replace=False))
+    else:
+        idx = np.arange(n)
+    pos = np.full(DUMP_ROWS, -1.0, dtype=np.float64)
+    pos[:len(idx)] = idx
+    np.save(os.path.join(path, "row_index.npy"), pos)
+    for f in ROW_FIELDS:
+        a = np.asarray(cols[f])
+        out = np.zeros(DUMP_ROWS, dtype=np.float64 if a.dtype.kind in "ui" else np.float32)
+        out[:len(idx)] = a[idx]
+        np.save(os.path.join(path, f + ".npy"), out)
+    np.save(os.path.join(path, "n_rows.npy"), np.array([n], dtype=np.float64))
 
 
 def pairs_in_rows(L, rb, re_):
@@ -401,7 +440,13 @@ def main():
                     help="untimed back-to-back steps before the warmup while the GPU clock settles (seconds)")
     ap.add_argument("--config", default="c4", choices=sorted(CONFIGS))
     ap.add_argument("--kernel", default="auto", choices=["auto", "valu", "mfma"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, everything beyond the headline figure: the device pre-pass "
+                         "check, per-launch HIP-event times and the roofline, the steps without the screen, the "
+                         "CPU baseline and the rows checked against the oracle")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the rows of the last timed step (rank 0's gathered rows at N>1) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--unweighted", action="store_true", help="unit weights (main.rs:150-153 --unweighted)")
     ap.add_argument("--wide-weights", action="store_true",
@@ -513,14 +558,16 @@ def main():
     kernel = {"auto": W.KERNEL_AUTO, "valu": W.KERNEL_VALU, "mfma": W.KERNEL_MFMA}[args.kernel]
     # the same pre-pass on the device from the resident raw
     # buffer (filter + Henikoff + encode), checked bit for bit against the host's
-    pre = W.Context(dev_index, kernel)
+    # (--full: a check and a phase figure, not part of the timed path)
     dev_ms = []
-    for _ in range(3):
-        assert pre.load_filtered_device(d_buf.data_ptr(), L, N, unweighted=args.unweighted) == L
-        dev_ms.append(pre.stats()["load_ms"])
-    if not args.wide_weights:
-        assert np.array_equal(pre.weights().view(np.uint32), weights.view(np.uint32))
-    pre.close()
+    if args.full:
+        pre = W.Context(dev_index, kernel)
+        for _ in range(3):
+            assert pre.load_filtered_device(d_buf.data_ptr(), L, N, unweighted=args.unweighted) == L
+            dev_ms.append(pre.stats()["load_ms"])
+        if not args.wide_weights:
+            assert np.array_equal(pre.weights().view(np.uint32), weights.view(np.uint32))
+        pre.close()
     created = []  # every context of the run, closed explicitly at the end (newest first)
 
     def new_ctx():
@@ -612,11 +659,13 @@ def main():
     def nrows(res):
         return int(res[1].shape[1]) if res is not None and res[1] is not None else 0
 
+    last = {}  # N>1 step path: the last completed step's result (--dump-outputs)
+
     def step():
         if not dist_on:
             return ctx.run_chunks(thr, cb, ce)
-        _, rows = shard_step(thr, cb, ce)
-        return int(rows.shape[1]) if rows is not None else 0
+        last["res"] = shard_step(thr, cb, ce)
+        return nrows(last["res"])
 
     # steps stay in flight after a step with rows too: its gather is queued
     # behind its scan on the device (C2 0.157 -> 0.135 ms/step, LD blocks
@@ -643,6 +692,8 @@ def main():
                 pend.append(c)
             while pend:
                 r = pend.popleft().run_wait()
+            if k:
+                last["ctx"] = ctxs1[(k - 1) % len(ctxs1)]
             return r
         if pipe is None:
             r = 0
@@ -651,7 +702,8 @@ def main():
             return r
         for _ in range(k):
             pipe.submit(thr, cb, ce)
-        return nrows(pipe.drain())
+        last["res"] = pipe.drain()
+        return nrows(last["res"])
 
     # Clock settle (untimed, before the warmup): back-to-back steps for about
     # settle_s seconds.  The pair kernel's time falls over the first ~30
@@ -696,10 +748,24 @@ def main():
     if dist_on:
         dist.barrier()
     elapsed = time.perf_counter() - t0
-    # per-launch HIP-event times of the same steps, sampled after the timed
-    # region so that reading them adds nothing to it
-    kms, oms, sms, cand, cblk, cpairs = [], [], [], [], [], []
-    for _ in range(min(args.steps, 20)):
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed its caller, before any later step
+        # reuses the context's row buffers
+        if dist_on:
+            dump_outputs(args.dump_outputs, wdist.unpack_rows(last["res"][1]))
+        else:
+            g = last.get("ctx", ctx).rows()
+            dump_outputs(args.dump_outputs, {f: getattr(g, f) for f in ROW_FIELDS})
+    # the last timed step's own record on ctx (the contexts run the same pass
+    # on the same inputs): which kernels ran and how many candidates they left
+    st = ctx.stats()
+    cand, cblk, cpairs = [st["candidate_tiles"]], [st["candidate_blocks"]], [st["candidate_pairs"]]
+    # --full: per-launch HIP-event times of the same steps, sampled after the
+    # timed region so that reading them adds nothing to it
+    kms, oms, sms = [], [], []
+    if args.full:
+        cand, cblk, cpairs = [], [], []
+    for _ in range(min(args.steps, 20) if args.full else 0):
         tg = time.perf_counter()
         step()
         st = ctx.stats()
@@ -718,7 +784,9 @@ def main():
     # the same steps without the screen (every tile, every plane; same rows),
     # reported alongside: a few sequential runs after the timed region
     unscreened_ms = None
-    if dist_on:  # every rank runs the same steps (their collectives pair up), whatever its own policy chose
+    if not args.full:
+        screened_any = False
+    elif dist_on:  # every rank runs the same steps (their collectives pair up), whatever its own policy chose
         t = torch.tensor([int(screened)], dtype=torch.int64, device=cdev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         screened_any = bool(t.item())
@@ -736,10 +804,12 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=cdev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    kernel_ms = screen_ms = None  # (--full)
+    if dist_on and args.full:
         km = torch.tensor([float(np.mean(kms)), float(np.mean(sms))], dtype=torch.float64, device=cdev)
         dist.all_reduce(km, op=dist.ReduceOp.MAX)
         kernel_ms, screen_ms = float(km[0].item()), float(km[1].item())
-    else:
+    elif args.full:
         kernel_ms, screen_ms = float(np.mean(kms)), float(np.mean(sms))
     st = ctx.stats()
     kern_name = "mfma" if st["kernel"] == W.KERNEL_MFMA else "valu"
@@ -794,106 +864,108 @@ def main():
         total_pairs = shard_pairs  # one rank's shard of a K-way split, timed alone
         desc += " (rehearsal: rank 0's shard of %d)" % args.rehearse_shard
     value = total_pairs * args.steps / elapsed
-    # Roofline of the dominant kernel: ALGORITHMIC work per
-    # launch, SURVEY 8(d)'s 4 masked multiply-adds per (pair, sequence) =
-    # 8 N ops per pair, over the launch's HIP-event time.  Screened runs: the
-    # dominant kernel is the one-plane screen, which evaluates every pair of
-    # the shard (its bound, from one digit plane of every sequence); the
-    # candidate launch recomputes the few tiles it cannot reject.
-    alg_ops = shard_pairs * 8.0 * N
-    # the f32 kernel ran every tile: the f32 fallback, or the reference order
-    # without a screen in front (thresholds <= 0, --no-screen)
-    f32_path = kern_name == "valu" or (args.ref_sums and not screened)
-    if not f32_path:
-        # the dominant kernel's peak: dense i8 MFMA, or dense fp6 MFMA for the
-        # fp6 screen (no sparsity in either)
-        peak, unit = (FP6_MFMA_PEAK_TFLOPS if fp6 else I8_MFMA_PEAK_TOPS), "TFLOP/s"
-        dom_ms = screen_ms if screened else kernel_ms
-        achieved = alg_ops / (dom_ms * 1e-3) / 1e12
-        if fp6:
-            # tile pairs (two tiles sharing one A image per workgroup) from
-            # WLD_OPT_FP6_PAIRS_MIN_TILES tiles (default 0) while the pair
-            # list's 15-bit tile index holds the sites
-            pairs_min = ctx.get_option("fp6_pairs_min_tiles")
-            kname = ("pair_fp6_screen2w_kernel<tile pairs, 32x64 per wave, fp6 x fp4 16x16x128>"
-                     if (L + 63) // 64 <= 0x7FFF and n_tiles >= pairs_min
-                     else "pair_fp6_screen_kernel<fp6 x fp4 16x16x128>")
-        elif screen_kind == 4:
-            kname = "pair_mfma_kernel<candidate pairs, %d planes>" % min(planes, 2)
-        elif screened and screen_kind == 1 and ctx.get_option("i8_pairs") and NP <= 16384 and \
-                bool(np.all(weights >= 0)) and (L + 63) // 64 <= 0x7FFF:
-            # the i8 one-plane screen on the tile-pair list (WLD_OPT_I8_PAIRS)
-            kname = "pair_i8_screen2w_kernel<tile pairs, 32x64 per wave, i8 16x16x64, pre-multiplied operands>"
-        elif screened:
-            kname = "pair_mfma_kernel<screen,%d plane%s>" % ((2, "s") if screen_kind == 3 else (1, ""))
+    roof = hbm_alg = None
+    if args.full:
+        # Roofline of the dominant kernel: ALGORITHMIC work per
+        # launch, SURVEY 8(d)'s 4 masked multiply-adds per (pair, sequence) =
+        # 8 N ops per pair, over the launch's HIP-event time.  Screened runs: the
+        # dominant kernel is the one-plane screen, which evaluates every pair of
+        # the shard (its bound, from one digit plane of every sequence); the
+        # candidate launch recomputes the few tiles it cannot reject.
+        alg_ops = shard_pairs * 8.0 * N
+        # the f32 kernel ran every tile: the f32 fallback, or the reference order
+        # without a screen in front (thresholds <= 0, --no-screen)
+        f32_path = kern_name == "valu" or (args.ref_sums and not screened)
+        if not f32_path:
+            # the dominant kernel's peak: dense i8 MFMA, or dense fp6 MFMA for the
+            # fp6 screen (no sparsity in either)
+            peak, unit = (FP6_MFMA_PEAK_TFLOPS if fp6 else I8_MFMA_PEAK_TOPS), "TFLOP/s"
+            dom_ms = screen_ms if screened else kernel_ms
+            achieved = alg_ops / (dom_ms * 1e-3) / 1e12
+            if fp6:
+                # tile pairs (two tiles sharing one A image per workgroup) from
+                # WLD_OPT_FP6_PAIRS_MIN_TILES tiles (default 0) while the pair
+                # list's 15-bit tile index holds the sites
+                pairs_min = ctx.get_option("fp6_pairs_min_tiles")
+                kname = ("pair_fp6_screen2w_kernel<tile pairs, 32x64 per wave, fp6 x fp4 16x16x128>"
+                         if (L + 63) // 64 <= 0x7FFF and n_tiles >= pairs_min
+                         else "pair_fp6_screen_kernel<fp6 x fp4 16x16x128>")
+            elif screen_kind == 4:
+                kname = "pair_mfma_kernel<candidate pairs, %d planes>" % min(planes, 2)
+            elif screened and screen_kind == 1 and ctx.get_option("i8_pairs") and NP <= 16384 and \
+                    bool(np.all(weights >= 0)) and (L + 63) // 64 <= 0x7FFF:
+                # the i8 one-plane screen on the tile-pair list (WLD_OPT_I8_PAIRS)
+                kname = "pair_i8_screen2w_kernel<tile pairs, 32x64 per wave, i8 16x16x64, pre-multiplied operands>"
+            elif screened:
+                kname = "pair_mfma_kernel<screen,%d plane%s>" % ((2, "s") if screen_kind == 3 else (1, ""))
+            else:
+                kname = "pair_mfma_kernel<%d planes>" % planes
+            roof = {"bound": "mfma", "achieved": achieved, "peak": peak, "unit": unit, "frac": achieved / peak,
+                    "work": "algorithmic: 8*N ops per site pair (4 masked weighted sums)",
+                    "kernel": kname, "kernel_ms": dom_ms}
+            # what the matrix cores executed: P digit planes x 8 N per pair (one
+            # or two i8 planes when screened)
+            ex_planes = (2 if screen_kind == 3 else 1) if screened and screen_kind != 4 else \
+                min(planes, 2) if screen_kind == 4 else planes
+            roof["executed_frac"] = shard_pairs * 8.0 * ex_planes * N / (dom_ms * 1e-3) / 1e12 / peak
+            roof["executed_work"] = ("fp6 weights x fp4 codes, 8*N ops per pair" if fp6 else
+                                     "%d i8 digit plane(s) x 8*N ops per pair" % ex_planes)
+            # against the i8 peak as well (the integer kernels' roofline)
+            roof["frac_of_i8_peak"] = achieved / I8_MFMA_PEAK_TOPS
         else:
-            kname = "pair_mfma_kernel<%d planes>" % planes
-        roof = {"bound": "mfma", "achieved": achieved, "peak": peak, "unit": unit, "frac": achieved / peak,
-                "work": "algorithmic: 8*N ops per site pair (4 masked weighted sums)",
-                "kernel": kname, "kernel_ms": dom_ms}
-        # what the matrix cores executed: P digit planes x 8 N per pair (one
-        # or two i8 planes when screened)
-        ex_planes = (2 if screen_kind == 3 else 1) if screened and screen_kind != 4 else \
-            min(planes, 2) if screen_kind == 4 else planes
-        roof["executed_frac"] = shard_pairs * 8.0 * ex_planes * N / (dom_ms * 1e-3) / 1e12 / peak
-        roof["executed_work"] = ("fp6 weights x fp4 codes, 8*N ops per pair" if fp6 else
-                                 "%d i8 digit plane(s) x 8*N ops per pair" % ex_planes)
-        # against the i8 peak as well (the integer kernels' roofline)
-        roof["frac_of_i8_peak"] = achieved / I8_MFMA_PEAK_TOPS
-    else:
-        achieved = alg_ops / (kernel_ms * 1e-3) / 1e12
-        # finite weights: f32-input MFMA (v_mfma_f32_16x16x4_f32), whose peak is the
-        # f32 vector peak (MI355X_MICROARCH.md, Matrix cores: F32 row)
-        roof = {"bound": "mfma", "achieved": achieved, "peak": F32_VALU_PEAK_TFLOPS, "unit": "TFLOP/s",
-                "frac": achieved / F32_VALU_PEAK_TFLOPS, "path": "f32 MFMA 16x16x4",
-                "work": "algorithmic: 8*N f32 flops per site pair",
-                # (lib.rs's order on up to 4 x 768 tiles: 16-row items, one
-                # sub-block per wave, capi.hip / pair_valu.hip ref_item_kernel)
-                "kernel": ("ref_item_kernel<lib.rs order, 16-row items>" if args.ref_sums and n_tiles <= 4 * 768
-                           else "pair_valu_kernel<%s>" % ("lib.rs order" if args.ref_sums else "two-level sums")),
-                "kernel_ms": kernel_ms}
-    roof["pair_phase_ms"] = kernel_ms
-    roof["pair_phase_frac"] = alg_ops / (kernel_ms * 1e-3) / 1e12 / roof["peak"]
-    if screened:
-        n_cand = float(np.mean(cand))
-        cand_ms = kernel_ms - screen_ms
-        # the candidate launch: every plane of its tiles (or, --ref-sums, the
-        # f32 reference-order kernel), algorithmic work 8N per pair of its
-        # tiles (4096 pairs each, diagonal tiles counted whole)
-        cand_peak = F32_VALU_PEAK_TFLOPS if args.ref_sums else I8_MFMA_PEAK_TOPS
-        cand_ops = n_cand * 4096 * 8.0 * N
-        if screen_kind == 4:  # the per-pair kernel's algorithmic work: 8N per candidate pair
-            cand_ops = float(np.mean(cpairs)) * 8.0 * N
-        roof["screen"] = {"kind": "fp6 x fp4" if fp6 else {3: "i8 two-plane", 4: "candidate pairs (i8 pass on the top two digit planes, rigorous bound)"}.get(screen_kind, "i8"),
-                          "tiles": n_tiles,
-                          "candidate_tiles": n_cand, "candidate_fraction": n_cand / max(n_tiles, 1),
-                          "screen_ms": screen_ms, "candidate_launch_ms": cand_ms,
-                          "candidate_kernel": ("ref_rows_kernel<lib.rs order, one pair per thread>" if screen_kind == 4
-                                               else "ref_item_kernel<lib.rs order, f32 MFMA, 16-row items>" if args.ref_sums else
-                                               "pair_mfma_kernel<prefilter, %d planes>" % planes),
-                          "candidate_pairs": float(np.mean(cpairs)) if screen_kind == 4 else None,
-                          "candidate_frac": (cand_ops / (cand_ms * 1e-3) / 1e12 / cand_peak) if cand_ms > 0.02 else None,
-                          "candidate_peak": cand_peak,
-                          # --ref-sums computes only the candidate tiles' 16x16
-                          # sub-blocks holding a pair the screen could not reject
-                          "candidate_blocks": float(np.mean(cblk)),
-                          "candidate_computed_frac": ((float(np.mean(cblk)) * 256 * 8.0 * N) / (cand_ms * 1e-3) / 1e12
-                                                      / cand_peak) if cand_ms > 0.02 and args.ref_sums else None,
-                          "unscreened_pair_kernel_ms": unscreened_ms,
-                          "unscreened_frac": alg_ops / (unscreened_ms * 1e-3) / 1e12 / roof["peak"]}
-    # PMC traffic (profiles/traffic.json) was measured on the default C4 line's
-    # dominant kernel (the one-plane i8 screen); other lines report null
-    # (keyed by the data set too: the same kernel moves different bytes on linkage blocks)
-    tr = load_traffic(args.config + ("-unweighted" if args.unweighted else "") +
-                      ("-ldblocks" if args.data == "ldblocks" else ""),
-                      "fp6" if fp6 else "i8pairs" if roof.get("kernel", "").startswith("pair_i8_screen2w") else kern_name)
-    same_kernel = (screen_kind == 1 and args.thr is None and not args.wide_weights
-                   and not (args.rehearse_dist and args.rehearse_shard > 1))
-    # ... and only for the kernel those counters were collected on
-    if tr and tr.get("kernel") and tr["kernel"].split("<")[0] != roof.get("kernel", "").split("<")[0]:
-        tr = None
-    roof["traffic"] = tr.get("hbm_bytes_per_launch") if tr and same_kernel else None
-    hbm_alg = shard_pairs * 2.0 * N / (kernel_ms * 1e-3) / 1e9  # 2N bytes per pair
+            achieved = alg_ops / (kernel_ms * 1e-3) / 1e12
+            # finite weights: f32-input MFMA (v_mfma_f32_16x16x4_f32), whose peak is the
+            # f32 vector peak (F32_VALU_PEAK_TFLOPS above)
+            roof = {"bound": "mfma", "achieved": achieved, "peak": F32_VALU_PEAK_TFLOPS, "unit": "TFLOP/s",
+                    "frac": achieved / F32_VALU_PEAK_TFLOPS, "path": "f32 MFMA 16x16x4",
+                    "work": "algorithmic: 8*N f32 flops per site pair",
+                    # (lib.rs's order on up to 4 x 768 tiles: 16-row items, one
+                    # sub-block per wave, capi.hip / pair_valu.hip ref_item_kernel)
+                    "kernel": ("ref_item_kernel<lib.rs order, 16-row items>" if args.ref_sums and n_tiles <= 4 * 768
+                               else "pair_valu_kernel<%s>" % ("lib.rs order" if args.ref_sums else "two-level sums")),
+                    "kernel_ms": kernel_ms}
+        roof["pair_phase_ms"] = kernel_ms
+        roof["pair_phase_frac"] = alg_ops / (kernel_ms * 1e-3) / 1e12 / roof["peak"]
+        if screened:
+            n_cand = float(np.mean(cand))
+            cand_ms = kernel_ms - screen_ms
+            # the candidate launch: every plane of its tiles (or, --ref-sums, the
+            # f32 reference-order kernel), algorithmic work 8N per pair of its
+            # tiles (4096 pairs each, diagonal tiles counted whole)
+            cand_peak = F32_VALU_PEAK_TFLOPS if args.ref_sums else I8_MFMA_PEAK_TOPS
+            cand_ops = n_cand * 4096 * 8.0 * N
+            if screen_kind == 4:  # the per-pair kernel's algorithmic work: 8N per candidate pair
+                cand_ops = float(np.mean(cpairs)) * 8.0 * N
+            roof["screen"] = {"kind": "fp6 x fp4" if fp6 else {3: "i8 two-plane", 4: "candidate pairs (i8 pass on the top two digit planes, rigorous bound)"}.get(screen_kind, "i8"),
+                              "tiles": n_tiles,
+                              "candidate_tiles": n_cand, "candidate_fraction": n_cand / max(n_tiles, 1),
+                              "screen_ms": screen_ms, "candidate_launch_ms": cand_ms,
+                              "candidate_kernel": ("ref_rows_kernel<lib.rs order, one pair per thread>" if screen_kind == 4
+                                                   else "ref_item_kernel<lib.rs order, f32 MFMA, 16-row items>" if args.ref_sums else
+                                                   "pair_mfma_kernel<prefilter, %d planes>" % planes),
+                              "candidate_pairs": float(np.mean(cpairs)) if screen_kind == 4 else None,
+                              "candidate_frac": (cand_ops / (cand_ms * 1e-3) / 1e12 / cand_peak) if cand_ms > 0.02 else None,
+                              "candidate_peak": cand_peak,
+                              # --ref-sums computes only the candidate tiles' 16x16
+                              # sub-blocks holding a pair the screen could not reject
+                              "candidate_blocks": float(np.mean(cblk)),
+                              "candidate_computed_frac": ((float(np.mean(cblk)) * 256 * 8.0 * N) / (cand_ms * 1e-3) / 1e12
+                                                          / cand_peak) if cand_ms > 0.02 and args.ref_sums else None,
+                              "unscreened_pair_kernel_ms": unscreened_ms,
+                              "unscreened_frac": alg_ops / (unscreened_ms * 1e-3) / 1e12 / roof["peak"]}
+        # PMC traffic (profiles/traffic.json) was measured on the default C4 line's
+        # dominant kernel (the one-plane i8 screen); other lines report null
+        # (keyed by the data set too: the same kernel moves different bytes on linkage blocks)
+        tr = load_traffic(args.config + ("-unweighted" if args.unweighted else "") +
+                          ("-ldblocks" if args.data == "ldblocks" else ""),
+                          "fp6" if fp6 else "i8pairs" if roof.get("kernel", "").startswith("pair_i8_screen2w") else kern_name)
+        same_kernel = (screen_kind == 1 and args.thr is None and not args.wide_weights
+                       and not (args.rehearse_dist and args.rehearse_shard > 1))
+        # ... and only for the kernel those counters were collected on
+        if tr and tr.get("kernel") and tr["kernel"].split("<")[0] != roof.get("kernel", "").split("<")[0]:
+            tr = None
+        roof["traffic"] = tr.get("hbm_bytes_per_launch") if tr and same_kernel else None
+        hbm_alg = shard_pairs * 2.0 * N / (kernel_ms * 1e-3) / 1e9  # 2N bytes per pair
     # the arithmetic the timed steps executed
     fixed = "%d-bit fixed-point weights" % (31 if planes == 4 else 23)
     if kern_name == "mfma" and screen_kind == 4:
@@ -959,6 +1031,8 @@ def main():
                            (" (auto: the faster of two interleaved trials of each order)"
                             if serialize_trials else ""))
                         if (pipe is not None or ctxs1 is not None) else ""))},
+        "full": args.full,
+        # (--full; null on a plain run, like the other figures measured after the timed steps)
         "roofline": roof,
         # N=1 "auto": ms/step of each trial of the two step orders (the timed steps ran the faster)
         "pipe_order_trials_ms": serialize_trials,
@@ -966,14 +1040,19 @@ def main():
         # re-read both site columns from HBM) — not a roofline: the kernel
         # stages columns through LDS/L2 and reads each far fewer times
         "north_star_hbm_model": {"model_bytes_per_pair": 2 * N, "model_GBps": hbm_alg,
-                                 "hbm_peak_GBps": HBM_PEAK_GBPS, "model_over_peak": hbm_alg / HBM_PEAK_GBPS},
-        "order_ms": float(np.mean(oms)),
+                                 "hbm_peak_GBps": HBM_PEAK_GBPS,
+                                 "model_over_peak": hbm_alg / HBM_PEAK_GBPS} if args.full else None,
+        "order_ms": float(np.mean(oms)) if args.full else None,
         # SURVEY 8(d) timing window: phases outside `value`'s step are reported, not timed in it
         "phases_ms": {"host_prepass_filter_henikoff": prepass_ms,
-                      "device_prepass_filter_henikoff_encode": float(min(dev_ms)), "h2d_inputs": h2d_ms,
-                      "device_encode_prep": load_ms, "pair_phase": kernel_ms, "order_assembly": float(np.mean(oms)),
-                      "step_minus_kernel_rank0": float(np.median(gms))},
+                      "device_prepass_filter_henikoff_encode": float(min(dev_ms)) if args.full else None,
+                      "h2d_inputs": h2d_ms, "device_encode_prep": load_ms, "pair_phase": kernel_ms,
+                      "order_assembly": float(np.mean(oms)) if args.full else None,
+                      "step_minus_kernel_rank0": float(np.median(gms)) if args.full else None},
+        "cpu_baseline": None,
     }
+    if args.dump_outputs:
+        out["outputs_dumped"] = {"rows": rows, "slots": DUMP_ROWS, "fields": list(ROW_FIELDS)}
     if checked:
         # every checked step's rows (gathered to rank 0 at N>1) against the
         # oracle over the same chunk range: the same rows in the same order,
@@ -998,9 +1077,7 @@ def main():
         out["steps_check"] = {"steps": len(checked), "equal_to_oracle": equal, "rows_per_step": len(ref["site_a"]),
                               "compare": "bitwise" if args.ref_sums else "within 1e-5"}
         assert equal == len(checked) == args.check_steps, out["steps_check"]
-    if args.no_cpu_baseline:
-        out["cpu_baseline"] = None
-    else:
+    if args.full and not args.no_cpu_baseline:
         # rank 0 (at N>1 after the other ranks have left: no rank polls beside
         # it), a bounded sample at N>1 so that a scaling run stays short
         oref, ochunks, out["cpu_baseline"] = cpu_baseline(buf, weights, thr, args.cpu_seconds if world == 1 else

@@ -1,6 +1,7 @@
-"""bench.py's contract: the synthetic inputs (CPU) and the one JSON line a
-short default run prints (GPU, run as a child process exactly as the driver
-runs it)."""
+"""bench.py's contract: the synthetic inputs (CPU), the one JSON line a short
+run prints (GPU, run as a child process exactly as the driver runs it: plain,
+and with --full for the roofline, the CPU baseline and the oracle checks) and
+the rows --dump-outputs writes."""
 import json
 import os
 import subprocess
@@ -52,10 +53,10 @@ REQUIRED = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step
 
 @pytest.mark.gpu
 def test_bench_json_line():
-    """A short default-config run: one JSON line with the driver's keys, the
-    roofline object, rows equal to the oracle's (bench asserts it)."""
+    """A short default-config run with --full: one JSON line with the driver's
+    keys, the roofline object, rows equal to the oracle's (bench asserts it)."""
     env = dict(os.environ)
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "5", "--warmup", "2", "--cpu-seconds", "2"],
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "5", "--warmup", "2", "--cpu-seconds", "2"],
                        cwd=REPO, env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -77,6 +78,84 @@ def test_bench_json_line():
     assert set(tr) == {"pair", "0"} and all(len(v) == 2 and min(v) > 0 for v in tr.values())
     chosen = "screens may overlap" if sum(tr["0"]) < sum(tr["pair"]) else "pair kernels queued back to back"
     assert chosen in out["config"]["parallelism"], out["config"]["parallelism"]
+
+
+@pytest.mark.gpu
+def test_plain_run_line_and_dumped_rows(tmp_path):
+    """A plain run (no --full) times its steps and prints the headline keys
+    with nothing measured beside them (no roofline, CPU baseline or oracle
+    check), and --dump-outputs writes the last timed step's rows: BASELINE
+    config 2 at threshold 0 (every pair a row; 6 steps, so the last one ran on
+    the pipelined loop's second context; more rows than the dump has slots, so
+    a seeded sample of them), each dumped row equal to the oracle's row at its
+    position bit for bit, in reference order, as float64 indices and float32
+    values."""
+    import weightedld_amd as W
+    import _oracle as O
+
+    dump = tmp_path / "out"
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--config", "c2", "--steps", "6", "--warmup", "2",
+                        "--dump-outputs", str(dump)], cwd=REPO, env=dict(os.environ), capture_output=True, text=True,
+                       timeout=120)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-3000:]
+    out = json.loads(lines[0])
+    assert REQUIRED <= set(out), sorted(REQUIRED - set(out))
+    assert out["metric"] == bench.METRIC and out["unit"] == "site-pairs/s" and out["higher_is_better"] is True
+    assert out["steps"] == 6 and out["warmup"] == 2 and out["ms_per_step"] > 0 and out["dtype"]
+    assert abs(out["value"] * out["ms_per_step"] / 1e3 / (2000 * 1999 // 2) - 1) < 0.01
+    assert out["full"] is False and out["roofline"] is None and out["cpu_baseline"] is None
+    assert "rows_check" not in out and out["phases_ms"]["pair_phase"] is None
+    buf = bench.synth(2000, 500)
+    ref = O.all_pairs(buf, W.henikoff_weights(W.SiteSet.from_buffer(buf)), 0.0)
+    names = bench.ROW_FIELDS + ("row_index", "n_rows")
+    assert sorted(p.name for p in dump.iterdir()) == sorted(f + ".npy" for f in names)
+    got = {f: np.load(dump / (f + ".npy")) for f in names}
+    n = int(got["n_rows"][0])
+    assert n == len(ref["r2"]) == out["config"]["rows_passing"] > bench.DUMP_ROWS
+    # more rows than slots: every slot holds a row, at ascending positions
+    idx = got["row_index"].astype(np.int64)
+    assert idx.shape == (bench.DUMP_ROWS,) and idx[0] >= 0 and idx[-1] < n and np.all(np.diff(idx) > 0)
+    for f in ("site_a", "site_b"):
+        assert got[f].dtype == np.float64 and np.array_equal(got[f], ref[f][idx].astype(np.float64)), f
+    for f in ("d", "d_prime", "r2"):
+        assert got[f].dtype == np.float32 and np.array_equal(got[f].view(np.uint32), ref[f][idx].view(np.uint32)), f
+
+
+def _rows(n, seed=3):
+    rng = np.random.default_rng(seed)
+    return {"site_a": rng.integers(0, 9, n).astype(np.uint32), "site_b": np.arange(n, dtype=np.uint32),
+            "d": rng.random(n, dtype=np.float32) - 0.5, "d_prime": rng.random(n, dtype=np.float32),
+            "r2": rng.random(n, dtype=np.float32)}
+
+
+@pytest.mark.parametrize("n", [0, 1, 999, 1000, 1001, 5000])
+def test_dump_outputs_fixed_length(tmp_path, monkeypatch, n):
+    """Every dumped array has DUMP_ROWS slots whatever the step's row count
+    (none, fewer, exactly as many, more): the rows in order, or a seeded sample
+    of them in order when there are more, the same from run to run; row_index
+    holds each slot's position in the row list, -1 and zero columns in the
+    slots past the rows; all float32 / float64 and within 64 MB at the real
+    slot count."""
+    assert bench.DUMP_ROWS * 36 + 8 <= 64_000_000
+    monkeypatch.setattr(bench, "DUMP_ROWS", 1000)
+    cols = _rows(n)
+    bench.dump_outputs(str(tmp_path / "a"), cols)
+    bench.dump_outputs(str(tmp_path / "b"), cols)
+    got = {}
+    for f in bench.ROW_FIELDS + ("row_index", "n_rows"):
+        got[f], b = np.load(tmp_path / "a" / (f + ".npy")), np.load(tmp_path / "b" / (f + ".npy"))
+        assert got[f].dtype == (np.float32 if f in ("d", "d_prime", "r2") else np.float64)
+        assert got[f].shape == ((1,) if f == "n_rows" else (1000,)) and np.array_equal(got[f], b)
+    assert got["n_rows"][0] == n
+    k = min(n, 1000)
+    idx = got["row_index"].astype(np.int64)
+    assert np.all(idx[k:] == -1) and np.all(np.diff(idx[:k]) > 0) and (k == 0 or (idx[0] >= 0 and idx[k - 1] < n))
+    if n <= 1000:
+        assert np.array_equal(idx[:k], np.arange(n))
+    for f in bench.ROW_FIELDS:
+        assert np.array_equal(got[f][:k], cols[f][idx[:k]].astype(got[f].dtype)) and not got[f][k:].any()
 
 
 def test_launcher_starts_n_ranks_before_the_gpu():
@@ -111,7 +190,7 @@ def test_launcher_two_ranks_rows_equal_oracle_every_step():
     equal the oracle's bit for bit, in reference order; the line says n_gpus 2
     and leaves the CPU baseline (an N=1 figure) null."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--collectives", "gloo", "--config", "c2",
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--gpus", "2", "--collectives", "gloo", "--config", "c2",
                         "--steps", "5", "--warmup", "2", "--settle-s", "0", "--check-steps", "4",
                         "--cpu-seconds", "2", "--counts", "collective"], cwd=REPO, env=env, capture_output=True,
                        text=True, timeout=300)
@@ -143,7 +222,7 @@ def test_launcher_eight_ranks_rows_equal_oracle_every_step():
     n_gpus 8.  The row counts go through host shared memory (--counts auto on
     one host; the two-rank test above keeps the collective count exchange)."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "8", "--collectives", "gloo", "--config", "c2",
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--gpus", "8", "--collectives", "gloo", "--config", "c2",
                         "--steps", "3", "--warmup", "1", "--settle-s", "0", "--check-steps", "2",
                         "--cpu-seconds", "1"], cwd=REPO, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """One line per bench JSON log: ms/step, value, pair phase, screen, candidate launch.
-    python tools/bench_summary.py gpurun_out/r03h/*.log"""
+The logs are those of `bench.py --full` runs (the roofline object is read).
+    python tools/bench_summary.py LOG..."""
 import json
 import sys
 
