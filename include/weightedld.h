@@ -263,6 +263,46 @@ int wld_set_kernel(wld_ctx *ctx, int kernel);
 int wld_set_option(wld_ctx *ctx, int option, int64_t value);
 int wld_get_option(wld_ctx *ctx, int option, int64_t *value);
 
+/* The window: which pairs a run computes at all (PLINK's --ld-window /
+ * --ld-window-kb, VCFtools' --ld-window / --ld-window-bp; not in the
+ * reference).  With pos[i] = site_map[i] of the loaded (filtered) set, or i
+ * without a map, a pair a < b of loaded indices is in the window iff
+ *   (max_distance == 0 || pos[b] - pos[a] <= max_distance) and
+ *   (max_sites == 0 || b - a <= max_sites);
+ * 0 means no limit, (0, 0) (the default) no window.  max_distance is in
+ * parent coordinates (VCF POS, alignment columns), max_sites counts loaded
+ * sites.  The rows of a windowed run are exactly the rows of the same run
+ * without a window whose pair is in the window: same order, parent indices
+ * and bits, on every kernel path; tiles without an in-window pair are not
+ * computed.  Per context (a device group forwards it to every member), it
+ * persists across loads until changed, and is obeyed by wld_run,
+ * wld_run_chunks[_async], wld_run_host and wld_all_weighted_ld_pairs.
+ * wld_dense and wld_single_weighted_ld_pair IGNORE it.  Under a window
+ * wld_run_stats.pairs counts the in-window pairs of the run's chunks and
+ * .tiles the 64x64 tiles holding one; staging, the 2^32 pairs-per-run limit
+ * and wld_run_host's batches are sized by in-window pairs; progress is called
+ * once per chunk that holds an in-window pair, with in-window counts.
+ * With max_distance > 0 the loaded site_map must be non-decreasing (equal
+ * neighbours allowed: multi-allelic VCF lines share a POS): otherwise
+ * WLD_E_ARG naming the first offending index, from whichever of wld_load* and
+ * wld_set_window comes second (a refused window leaves the previous one).
+ * WLD_E_STATE while a run is in flight.  Sets of more than 2^24 chunks
+ * (about 1.48M sites) take no window. */
+int wld_set_window(wld_ctx *ctx, uint64_t max_distance, uint64_t max_sites);
+int wld_get_window(wld_ctx *ctx, uint64_t *max_distance, uint64_t *max_sites);
+/* In-window pairs of the linear chunks [begin,end) of the loaded set under
+ * the current window (= wld_pairs_in_chunks without one). */
+int wld_window_pairs_in_chunks(wld_ctx *ctx, uint32_t begin, uint32_t end, uint64_t *pairs);
+/* wld_shard_chunks for the loaded set, balanced by in-window pairs: contiguous
+ * linear ranges, shard 0 takes the LAST one; no shard exceeds total/n_shards
+ * by more than the largest single chunk's count.  wld_run_host on a device
+ * group uses it when a window is set.  (= wld_shard_chunks without one.) */
+int wld_shard_chunks_window(wld_ctx *ctx, int n_shards, int shard, uint32_t *begin, uint32_t *end);
+/* The window's per-site limits as the device computed them from the resident
+ * site_map: hi[a] = the last in-window partner of loaded site a (a itself:
+ * none), n_sites entries; for tests.  WLD_E_STATE without a window. */
+int wld_window_limits_copy(wld_ctx *ctx, uint32_t *hi);
+
 /* Rows of PairStore<LdStats> (lib.rs:523-576) as structure-of-arrays, in the
  * reference's order: 256x256 chunks in triu_index order (lib.rs:623-635:
  * chunk rows descending, columns ascending), then site_a, then site_b
@@ -295,7 +335,8 @@ int wld_all_weighted_ld_pairs(wld_ctx *ctx, const uint8_t *sites, size_t n_sites
 
 /* Drop-in for single_weighted_ld_pair (lib.rs:390-521) with the histograms of
  * a and b taken from the slices themselves (as SiteSet does).  Returns 1 and
- * fills out[3] = {d, d_prime, r2} for Some, 0 for None, <0 on error. */
+ * fills out[3] = {d, d_prime, r2} for Some, 0 for None, <0 on error.  Ignores
+ * the window (wld_set_window). */
 int wld_single_weighted_ld_pair(wld_ctx *ctx, const uint8_t *a, const uint8_t *b,
                                 const float *weights, size_t n_seqs, float out[3]);
 
@@ -415,7 +456,8 @@ int wld_rows_copy(wld_ctx *ctx, uint32_t *site_a, uint32_t *site_b, float *d, fl
  * before returning. */
 int wld_rows_copy_device(wld_ctx *ctx, void *site_a, void *site_b, void *d, void *d_prime, void *r2);
 /* Dense stats of every pair a<b of the loaded set into host n_sites*n_sites
- * row-major matrices (valid[a*L+b] = 1 for Some); for tests. */
+ * row-major matrices (valid[a*L+b] = 1 for Some); for tests.  Ignores the
+ * window (wld_set_window): every pair. */
 int wld_dense(wld_ctx *ctx, float *d, float *d_prime, float *r2, uint8_t *valid);
 
 typedef struct {

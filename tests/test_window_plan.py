@@ -1,0 +1,22 @@
+"""The windowed run's host plan (weightedld_amd/csrc/window_plan.hpp: per-site
+limits, per-chunk in-window pair counts, the windowed tile list, the shard
+partition) against a brute-force O(L^2) restatement of the window predicate
+(tests/cpp/window_plan_check.cpp, host only), plain and under
+AddressSanitizer + UndefinedBehaviorSanitizer (a stand-alone host program)."""
+import os
+import subprocess
+
+import pytest
+
+from conftest import REPO
+
+
+@pytest.mark.parametrize("san", [[], ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-g"]],
+                         ids=["plain", "asan_ubsan"])
+def test_window_plan_against_brute_force(tmp_path, san):
+    exe = str(tmp_path / "window_plan_check")
+    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", *san,
+                    "-I", os.path.join(REPO, "weightedld_amd", "csrc"),
+                    os.path.join(REPO, "tests", "cpp", "window_plan_check.cpp"), "-o", exe], check=True)
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0 and out.stdout.strip().endswith("OK"), out.stdout + out.stderr

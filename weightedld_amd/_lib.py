@@ -108,6 +108,11 @@ SIGNATURES = {
     "wld_set_kernel": (_int, [_vp, _int]),
     "wld_set_option": (_int, [_vp, _int, ctypes.c_int64]),
     "wld_get_option": (_int, [_vp, _int, ctypes.POINTER(ctypes.c_int64)]),
+    "wld_set_window": (_int, [_vp, ctypes.c_uint64, ctypes.c_uint64]),
+    "wld_get_window": (_int, [_vp, _u64p, _u64p]),
+    "wld_window_pairs_in_chunks": (_int, [_vp, ctypes.c_uint32, ctypes.c_uint32, _u64p]),
+    "wld_shard_chunks_window": (_int, [_vp, _int, _int, _u32p, _u32p]),
+    "wld_window_limits_copy": (_int, [_vp, _u32p]),
     "wld_pairs_free": (None, [ctypes.POINTER(Pairs)]),
     "wld_all_weighted_ld_pairs": (_int, [_vp, _u8p, _sz, _sz, _u64p, _f32p, ctypes.c_float, PROGRESS_FN, _vp,
                                          ctypes.POINTER(Pairs)]),

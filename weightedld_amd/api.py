@@ -280,6 +280,38 @@ class Context:
         check(lib().wld_get_option(self._h, OPTIONS[name], ctypes.byref(v)), "wld_get_option")
         return int(v.value)
 
+    def set_window(self, max_distance=None, max_sites=None):
+        """wld_set_window: later runs compute only the pairs a < b with
+        site_map[b] - site_map[a] <= max_distance (parent coordinates) and
+        b - a <= max_sites (loaded sites); None or 0: no limit.  Persists
+        across loads; dense() and single_weighted_ld_pair ignore it."""
+        check(lib().wld_set_window(self._h, int(max_distance or 0), int(max_sites or 0)), "wld_set_window")
+
+    def window(self):
+        """(max_distance, max_sites) of wld_get_window; 0 = no limit."""
+        d, k = ctypes.c_uint64(), ctypes.c_uint64()
+        check(lib().wld_get_window(self._h, ctypes.byref(d), ctypes.byref(k)), "wld_get_window")
+        return int(d.value), int(k.value)
+
+    def window_pairs_in_chunks(self, begin, end):
+        """In-window pairs of the loaded set's linear chunks [begin, end) (wld_window_pairs_in_chunks)."""
+        n = ctypes.c_uint64()
+        check(lib().wld_window_pairs_in_chunks(self._h, begin, end, ctypes.byref(n)), "wld_window_pairs_in_chunks")
+        return int(n.value)
+
+    def shard_chunks_window(self, n_shards, shard):
+        """Linear chunk range [begin, end) of `shard`, balanced by in-window pairs (wld_shard_chunks_window)."""
+        b, e = ctypes.c_uint32(), ctypes.c_uint32()
+        check(lib().wld_shard_chunks_window(self._h, n_shards, shard, ctypes.byref(b), ctypes.byref(e)),
+              "wld_shard_chunks_window")
+        return int(b.value), int(e.value)
+
+    def window_limits(self, n_sites):
+        """The device's per-site limits hi[] under the window (wld_window_limits_copy; tests)."""
+        hi = np.zeros(n_sites, dtype=np.uint32)
+        check(lib().wld_window_limits_copy(self._h, _p(hi, ctypes.c_uint32)), "wld_window_limits_copy")
+        return hi
+
     def load(self, site_major, weights, site_map=None):
         buf = np.ascontiguousarray(site_major, dtype=np.uint8)
         w = np.ascontiguousarray(weights, dtype=np.float32)
@@ -481,9 +513,20 @@ def single_weighted_ld_pair(a, a_hist, b, b_hist, weights, ctx=None):
     return LdStats(r2=float(out[2]), d=float(out[0]), d_prime=float(out[1]))
 
 
-def all_weighted_ld_pairs(site_set, weights, r2_threshold, progress_report=None, ctx=None):
-    """lib.rs:578-684 -> PairStore in reference order (parent site indices)."""
+def all_weighted_ld_pairs(site_set, weights, r2_threshold, progress_report=None, ctx=None, max_distance=None,
+                          max_sites=None):
+    """lib.rs:578-684 -> PairStore in reference order (parent site indices).
+    max_distance / max_sites (not in the reference): the window of
+    Context.set_window for this call; the context's own window is restored
+    afterwards."""
     ctx = ctx or default_context()
+    if max_distance is not None or max_sites is not None:
+        before = ctx.window()
+        ctx.set_window(max_distance, max_sites)
+        try:
+            return all_weighted_ld_pairs(site_set, weights, r2_threshold, progress_report, ctx)
+        finally:
+            ctx.set_window(*before)
     buf = site_set.buffer
     w = np.ascontiguousarray(weights, dtype=np.float32)
     if w.size != site_set.n_seqs():

@@ -23,6 +23,7 @@
 
 #include "common.hpp"
 #include "tile_order.hpp"
+#include "window_plan.hpp"
 #include "kernels.hpp"
 
 using namespace wld;
@@ -212,6 +213,21 @@ struct wld_ctx {
     size_t plog_cap = 0;
     const std::function<void(uint64_t)> *on_chunk = nullptr;  // set by run_host_range for its runs
     bool prog_pass = false;  // the pass in flight logs its chunks
+    uint32_t prog_expect = 0;  // ... this many of them (under a window: the chunks with an in-window pair)
+
+    // the window (wld_set_window; 0 = no limit; persists across loads) and its
+    // plan for the loaded set (window_prepare; window_plan.hpp)
+    uint64_t win_d = 0, win_k = 0;
+    bool has_pos = false;
+    std::vector<uint32_t> pos_host;      // the loaded site_map (has_pos), for the plan
+    std::vector<uint32_t> win_hi_host;   // hi[a], the last in-window partner of a
+    std::vector<uint64_t> win_pre;       // prefix of the in-window pairs per linear chunk
+    std::vector<uint32_t> win_live_pre;  // prefix of the chunks holding an in-window pair
+    DevBuf win_hi, win_pairs;            // hi[] ([LP], window_limits_kernel) and the per-chunk counts on the device
+    bool tiles_windowed = false;         // the tile list was cut to the window ...
+    uint64_t tiles_win_d = 0, tiles_win_k = 0;  // ... this one
+    uint32_t n_tiles_listed = 0;         // its tiles without the XCD order's padding
+    bool seg_clear = false;              // a windowed list was built: seg_cnt is zeroed before the next pass
 
     ~wld_ctx() {
         for (wld_ctx *m : members) delete m;
@@ -221,7 +237,7 @@ struct wld_ctx {
         // buffers: it completes before they are freed
         if (stream && stream != own_stream) (void)hipStreamSynchronize(stream);
         DevBuf *all[] = {&keep, &htab, &htab_kept, &site_index, &raw, &wraw, &codes, &w_pad, &wstats, &site_ok, &site_map, &planes, &frag, &rcodes, &rw, &w6, &f6a, &f6b, &i8a, &i8b, &tiles, &cand, &f6_pairs, &fp6_probe_buf,
-                         &seg_cnt, &seg_off, &chunk_total, &chunk_base, &counters, &chunk_left, &prog_n, &st_a, &st_b, &st_d,
+                         &seg_cnt, &seg_off, &chunk_total, &chunk_base, &counters, &chunk_left, &prog_n, &win_hi, &win_pairs, &st_a, &st_b, &st_d,
                          &st_dp, &st_r2, &out_a, &out_b, &out_d, &out_dp, &out_r2};
         for (DevBuf *b : all) release(*b);
         for (auto &e : ev)
@@ -381,7 +397,8 @@ int i8img_prepare(wld_ctx *c) {
     return WLD_OK;
 }
 
-int build_tiles(wld_ctx *c, uint32_t lb, uint32_t le);
+int build_tiles(wld_ctx *c, uint32_t lb, uint32_t le, bool windowed);
+int window_prepare(wld_ctx *c);
 int ensure_ref_layout(wld_ctx *c);
 uint32_t chunks_of(size_t L);
 uint32_t chunk_rows_of(size_t L);
@@ -466,16 +483,26 @@ int common_load(wld_ctx *c, const uint8_t *d_sites, const float *d_w, const uint
     HIP_TRY(hipEventRecord(c->ev[1], c->stream));
 
     c->has_map = site_map != nullptr;
+    c->has_pos = false;
+    c->pos_host.clear();
     if (site_map) {
-        std::vector<uint32_t> m(L);
+        std::vector<uint32_t> &m = c->pos_host;  // kept: a window's plan reads it
+        m.resize(L);
         for (size_t i = 0; i < L; ++i) {
             if (site_map[i] > 0xFFFFFFFFull) return fail(WLD_E_ARG, "site_map[%zu] exceeds 32 bits", i);
             m[i] = (uint32_t)site_map[i];
         }
+        c->has_pos = true;
         WLD_TRY(ensure(c->site_map, std::max<size_t>(L, 1) * sizeof(uint32_t)));
         if (L) HIP_TRY(hipMemcpyAsync(c->site_map.p, m.data(), L * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
+    // a window set before the load: its plan for this set (a site_map that
+    // descends fails a distance window here)
+    c->win_hi_host.clear();
+    c->win_pre.clear();
+    c->win_live_pre.clear();
+    if (c->win_d || c->win_k) WLD_TRY(window_prepare(c));
     c->wst = MfmaWeightStats{7, 1, {0, 0, 0}, {0, 0, 0, 0}};
     if (c->kernel == WLD_KERNEL_MFMA && mfma_weight_stats(ptr<int8_t>(c->planes), c->LP, c->NP, c->stream, &c->wst))
         return fail(WLD_E_HIP, "reading the weight-plane statistics failed");
@@ -514,10 +541,58 @@ int common_load(wld_ctx *c, const uint8_t *d_sites, const float *d_w, const uint
     {
         const uint64_t T_used = (L + kTile - 1) / kTile;
         if ((uint64_t)L * (L - 1) / 2 <= 0xFFFFFFFFull && T_used * (T_used + 1) / 2 <= (1ull << 22))
-            WLD_TRY(build_tiles(c, 0, chunks_of(L)));
+            WLD_TRY(build_tiles(c, 0, chunks_of(L), true));
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
     return WLD_OK;
+}
+
+bool window_on(const wld_ctx *c) { return c->win_d != 0 || c->win_k != 0; }
+
+// The window's plan for the loaded set (window_plan.hpp): hi[] on the host
+// (tile lists, pair counts, shards) and, by window_limits_kernel from the
+// resident site_map, on the device (the kernels' pass test), the per-chunk
+// in-window pair counts on both.  Needs L, LP and the site map of the load;
+// runs when a load meets a window or a window meets a load.
+int window_prepare(wld_ctx *c) {
+    const uint32_t L = (uint32_t)c->L;
+    const uint32_t *pos = c->has_pos ? c->pos_host.data() : nullptr;
+    if (c->win_d && pos) {
+        const uint32_t i = window_plan::first_descent(pos, L);
+        if (i < L)
+            return fail(WLD_E_ARG, "a distance window (max_distance %llu) needs a non-decreasing site_map: "
+                                   "site_map[%u] = %u < site_map[%u] = %u",
+                        (unsigned long long)c->win_d, i, pos[i], i - 1, pos[i - 1]);
+    }
+    const uint32_t m = chunks_of(L);
+    if (m > (1u << 24))
+        return fail(WLD_E_ARG, "a window's plan covers up to 2^24 chunks; %zu sites have %u", c->L, m);
+    c->win_hi_host = window_plan::limits(pos, L, c->win_d, c->win_k);
+    c->win_pre = window_plan::chunk_prefix(c->win_hi_host);
+    c->win_live_pre.assign((size_t)m + 1, 0);
+    std::vector<uint32_t> cnt(std::max<uint32_t>(m, 1), 0);
+    for (uint32_t i = 0; i < m; ++i) {
+        cnt[i] = (uint32_t)(c->win_pre[i + 1] - c->win_pre[i]);  // (<= 256 x 256)
+        c->win_live_pre[i + 1] = c->win_live_pre[i] + (cnt[i] ? 1u : 0u);
+    }
+    WLD_TRY(ensure(c->win_pairs, cnt.size() * sizeof(uint32_t)));
+    WLD_TRY(ensure(c->win_hi, c->LP * sizeof(uint32_t)));
+    HIP_TRY(hipMemcpyAsync(c->win_pairs.p, cnt.data(), cnt.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    launch_window_limits(c->has_pos ? ptr<uint32_t>(c->site_map) : nullptr, L, (uint32_t)c->LP, c->win_d, c->win_k,
+                         ptr<uint32_t>(c->win_hi), c->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->stream));  // (cnt is read by the copy)
+    c->tiles_lb = c->tiles_le = ~0u;  // the tile lists follow the window
+    return WLD_OK;
+}
+
+// pairs of the linear chunks [lb, le) that a run computes: the in-window ones
+// under a window, else every pair a < b
+uint64_t pairs_in_chunks(size_t L, uint32_t lb, uint32_t le);
+uint64_t run_pairs(const wld_ctx *c, uint32_t lb, uint32_t le) {
+    if (window_on(c) && c->win_pre.size() > le) return c->win_pre[le] - c->win_pre[lb];
+    if (c->chunk_pairs_pre.size() > le) return c->chunk_pairs_pre[le] - c->chunk_pairs_pre[lb];
+    return pairs_in_chunks(c->L, lb, le);
 }
 
 uint32_t chunk_rows_of(size_t L) { return (uint32_t)((L + kChunk - 1) / kChunk); }
@@ -575,11 +650,28 @@ void rows_to_linear(uint32_t n, uint32_t rb, uint32_t re, uint32_t &lb, uint32_t
 // xcd_order and range_tiles: tile_order.hpp
 using tile_order::xcd_order;
 
-int build_tiles(wld_ctx *c, uint32_t lb, uint32_t le) {
-    if (c->tiles_lb == lb && c->tiles_le == le && c->n_tiles) return WLD_OK;
+// windowed: the list is cut to the context's window, if it has one (every
+// run); false: every tile (wld_dense, which ignores the window).  The cached
+// list is kept only for the same range AND the same window.
+int build_tiles(wld_ctx *c, uint32_t lb, uint32_t le, bool windowed) {
+    windowed = windowed && window_on(c);
+    const uint64_t wd = windowed ? c->win_d : 0, wk = windowed ? c->win_k : 0;
+    if (c->tiles_lb == lb && c->tiles_le == le && c->n_tiles && c->tiles_windowed == windowed &&
+        c->tiles_win_d == wd && c->tiles_win_k == wk)
+        return WLD_OK;
     const uint32_t T_used = (uint32_t)((c->L + kTile - 1) / kTile);
     const uint32_t n = chunk_rows_of(c->L);
-    std::vector<uint32_t> t = tile_order::range_tiles(n, T_used, lb, le);  // (ta, tb) order
+    // (ta, tb) order; under a window only the tiles holding an in-window pair
+    std::vector<uint32_t> t = windowed ? window_plan::range_tiles(n, T_used, lb, le, c->win_hi_host)
+                                       : tile_order::range_tiles(n, T_used, lb, le);
+    c->n_tiles_listed = (uint32_t)t.size();
+    c->tiles_windowed = windowed;
+    c->tiles_win_d = wd;
+    c->tiles_win_k = wk;
+    // a tile left out of the list is never written, and the gather reads the
+    // segment counts of all four b tiles of a chunk with rows: they must read
+    // as zero, whatever an earlier run (a wider window, none) left there
+    if (windowed) c->seg_clear = true;
     const uint32_t kS = tile_order::super_block_side((uint32_t)c->NP);
     // the fp6 screen's tile pairs (ordered as the tiles below, by first tile;
     // single tiles keep their flag through the ordering)
@@ -627,6 +719,9 @@ OrderArgs order_args(wld_ctx *c) {
     o.prog_log = c->prog_pass ? c->d_plog : nullptr;
     o.L = (uint32_t)c->L;
     o.guard = reinterpret_cast<unsigned *>(c->d_hcnt + 4);
+    // (the list in use is the window's: every run; wld_dense builds the full one)
+    o.win_hi = c->tiles_windowed ? ptr<uint32_t>(c->win_hi) : nullptr;
+    o.win_pairs = c->tiles_windowed ? ptr<uint32_t>(c->win_pairs) : nullptr;
     return o;
 }
 
@@ -918,6 +1013,84 @@ int wld_set_option(wld_ctx *c, int option, int64_t value) {
             break;
         default: return fail(WLD_E_ARG, "unknown option %d", option);
     }
+    return WLD_OK;
+}
+
+int wld_set_window(wld_ctx *c, uint64_t max_distance, uint64_t max_sites) {
+    if (!c) return fail(WLD_E_ARG, "null context");
+    if (c->pend.active) return fail(WLD_E_STATE, "wld_set_window during a run");
+    for (wld_ctx *m : c->members)
+        if (m->pend.active) return fail(WLD_E_STATE, "wld_set_window during a run");
+    if (!c->members.empty()) {
+        // every member gets the window; one that refuses it (a descending
+        // site_map) leaves the group on the window it had
+        for (size_t k = 0; k < c->members.size(); ++k) {
+            const int st = wld_set_window(c->members[k], max_distance, max_sites);
+            if (st != WLD_OK) {
+                const std::string msg = wld_last_error();
+                for (size_t j = 0; j < k; ++j) (void)wld_set_window(c->members[j], c->win_d, c->win_k);
+                return fail(st, "%s", msg.c_str());
+            }
+        }
+        c->win_d = max_distance;
+        c->win_k = max_sites;
+        return WLD_OK;
+    }
+    if (c->win_d == max_distance && c->win_k == max_sites) return WLD_OK;
+    const uint64_t old_d = c->win_d, old_k = c->win_k;
+    c->win_d = max_distance;
+    c->win_k = max_sites;
+    if (c->loaded && window_on(c)) {
+        int st = set_dev(c);
+        if (st == WLD_OK) st = window_prepare(c);
+        if (st != WLD_OK) {  // (a descending site_map under max_distance: the window stays as it was)
+            c->win_d = old_d;
+            c->win_k = old_k;
+            return st;
+        }
+    }
+    c->tiles_lb = c->tiles_le = ~0u;  // the tile lists follow the window
+    // the auto screen policy learned its thresholds on another set of tiles
+    c->screen_bad_thr = c->screen2_bad_thr = c->ref_pairs_bad_thr = c->fp6_bad_thr = -1.0f;
+    c->fp6_good_thr = INFINITY;
+    return WLD_OK;
+}
+
+int wld_get_window(wld_ctx *c, uint64_t *max_distance, uint64_t *max_sites) {
+    if (!c) return fail(WLD_E_ARG, "null context");
+    if (max_distance) *max_distance = c->win_d;
+    if (max_sites) *max_sites = c->win_k;
+    return WLD_OK;
+}
+
+int wld_window_pairs_in_chunks(wld_ctx *c, uint32_t begin, uint32_t end, uint64_t *pairs) {
+    if (!c || !pairs) return fail(WLD_E_ARG, "null argument");
+    if (!c->members.empty()) c = c->members[0];
+    if (!c->loaded) return fail(WLD_E_STATE, "wld_window_pairs_in_chunks before wld_load");
+    const uint32_t m = chunks_of(c->L);
+    end = std::min(end, m);
+    *pairs = begin < end ? run_pairs(c, begin, end) : 0;
+    return WLD_OK;
+}
+
+int wld_shard_chunks_window(wld_ctx *c, int n_shards, int shard, uint32_t *begin, uint32_t *end) {
+    if (!c) return fail(WLD_E_ARG, "null context");
+    if (!c->members.empty()) c = c->members[0];
+    if (!c->loaded) return fail(WLD_E_STATE, "wld_shard_chunks_window before wld_load");
+    if (!window_on(c)) return wld_shard_chunks(c->L, n_shards, shard, begin, end);
+    if (n_shards < 1 || shard < 0 || shard >= n_shards || !begin || !end)
+        return fail(WLD_E_ARG, "bad shard %d/%d", shard, n_shards);
+    window_plan::shard_range(c->win_pre, n_shards, shard, begin, end);
+    return WLD_OK;
+}
+
+int wld_window_limits_copy(wld_ctx *c, uint32_t *hi) {
+    WLD_TRY(set_dev(c));
+    if (!c->loaded) return fail(WLD_E_STATE, "wld_window_limits_copy before wld_load");
+    if (!window_on(c)) return fail(WLD_E_STATE, "wld_window_limits_copy without a window");
+    if (!hi && c->L) return fail(WLD_E_ARG, "wld_window_limits_copy: null output");
+    if (c->L) HIP_TRY(hipMemcpyAsync(hi, c->win_hi.p, c->L * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return WLD_OK;
 }
 
@@ -1305,12 +1478,10 @@ int run_enqueue(wld_ctx *c, float thr, uint32_t lin_begin, uint32_t lin_end, uns
     c->pend.active = false;
     const bool fp6_fresh = !c->fp6_tried && c->opt_fp6 != 0;
     if (fp6_fresh) WLD_TRY(fp6_prepare(c));
-    WLD_TRY(build_tiles(c, lin_begin, lin_end));
+    WLD_TRY(build_tiles(c, lin_begin, lin_end, true));
     c->fp6_sampled = false;
     WLD_TRY(fp6_sample(c, thr, fp6_fresh));
-    const uint64_t pairs = c->chunk_pairs_pre.size() > lin_end
-                               ? c->chunk_pairs_pre[lin_end] - c->chunk_pairs_pre[lin_begin]
-                               : pairs_in_chunks(c->L, lin_begin, lin_end);
+    const uint64_t pairs = run_pairs(c, lin_begin, lin_end);  // (in-window pairs under a window)
     const uint32_t T = (uint32_t)(c->LP / kTile);
     const uint32_t n_chunks = n * (n + 1) / 2;
     if (pairs > 0xFFFFFFFFull)
@@ -1319,6 +1490,10 @@ int run_enqueue(wld_ctx *c, float thr, uint32_t lin_begin, uint32_t lin_end, uns
     WLD_TRY(grow_staging(c, std::min<uint64_t>(pairs, c->opt_staging_rows)));
     WLD_TRY(ensure(c->seg_cnt, c->LP * T));
     WLD_TRY(ensure(c->seg_off, c->LP * T * sizeof(uint32_t)));
+    if (c->seg_clear) {  // a windowed list since the last clear: its unlisted tiles read as zero
+        HIP_TRY(hipMemsetAsync(c->seg_cnt.p, 0, c->LP * T, c->stream));
+        c->seg_clear = false;
+    }
     const size_t ct_bytes = c->chunk_total.bytes, cn_bytes = c->counters.bytes;
     WLD_TRY(ensure(c->chunk_total, std::max<size_t>(n_chunks, 1) * sizeof(uint32_t)));
     WLD_TRY(ensure(c->chunk_base, std::max<size_t>(n_chunks, 1) * sizeof(uint32_t)));
@@ -1341,8 +1516,15 @@ int run_enqueue(wld_ctx *c, float thr, uint32_t lin_begin, uint32_t lin_end, uns
             c->plog_cap = cnt;
         }
         memset(c->h_plog, 0xFF, (size_t)cnt * sizeof(unsigned long long));
-        launch_progress_init(ptr<unsigned>(c->chunk_left), lin_begin, cnt, n, (uint32_t)c->L, ptr<unsigned>(c->prog_n),
-                             c->stream);
+        if (c->tiles_windowed) {
+            launch_progress_init_window(ptr<unsigned>(c->chunk_left), lin_begin, cnt, n, ptr<uint32_t>(c->tiles),
+                                        c->n_tiles, ptr<unsigned>(c->prog_n), c->stream);
+            c->prog_expect = c->win_live_pre[lin_end] - c->win_live_pre[lin_begin];
+        } else {
+            launch_progress_init(ptr<unsigned>(c->chunk_left), lin_begin, cnt, n, (uint32_t)c->L,
+                                 ptr<unsigned>(c->prog_n), c->stream);
+            c->prog_expect = cnt;
+        }
         HIP_TRY(hipGetLastError());
         c->prog_pass = true;
     }
@@ -1357,7 +1539,7 @@ int run_enqueue(wld_ctx *c, float thr, uint32_t lin_begin, uint32_t lin_end, uns
 // the run, and counted in wld_run_stats.progress_filled — a pass that
 // completes logs every chunk (a refused tile fails the run at check_guard),
 // so a nonzero count is a lost tile_done count, which the tests look for.
-int drain_progress(wld_ctx *c, uint32_t lin_begin, uint32_t n_chunks) {
+int drain_progress(wld_ctx *c, uint32_t n_chunks) {
     uint32_t seen = 0;
     auto drain = [&] {
         while (seen < n_chunks) {
@@ -1382,8 +1564,8 @@ int drain_progress(wld_ctx *c, uint32_t lin_begin, uint32_t n_chunks) {
         // did not arrive, one report each (the sum is the range's pairs)
         uint64_t logged = 0;
         for (uint32_t k = 0; k < seen; ++k) logged += c->h_plog[k];
-        uint64_t rest = pairs_in_chunks(c->L, lin_begin, lin_begin + n_chunks) - std::min<uint64_t>(
-                            logged, pairs_in_chunks(c->L, lin_begin, lin_begin + n_chunks));
+        const uint64_t all = c->pend.pairs;  // the run's pairs (in-window ones under a window)
+        uint64_t rest = all - std::min<uint64_t>(logged, all);
         const uint32_t missing = n_chunks - seen;
         c->stats.progress_filled += missing;
         for (uint32_t k = 0; k < missing; ++k) {
@@ -1424,7 +1606,7 @@ int run_complete(wld_ctx *c, uint64_t *n_rows) {
     for (;;) {
         if (c->prog_pass) {
             c->prog_pass = false;  // a re-run after a staging overflow does not report again
-            WLD_TRY(drain_progress(c, r.lin_begin, lin_count));
+            WLD_TRY(drain_progress(c, c->prog_expect));
         }
         // the pass's end, not the stream's: on a shared stream (wld_set_stream)
         // the next context's run may already be queued behind it
@@ -1479,7 +1661,8 @@ int run_complete(wld_ctx *c, uint64_t *n_rows) {
     c->times_order_end = order_end;
     // (exact candidate pairs: the i8 pass, ref_sums_kernel, ref_compact_kernel)
     c->stats.pair_kernel_launches = c->n_tiles ? (c->ref_pairs_pass ? 3 : c->screened ? 2 : 1) : 0;
-    c->stats.tiles = c->n_tiles;
+    // (under a window: the tiles holding an in-window pair, without the launch order's padding)
+    c->stats.tiles = c->tiles_windowed ? c->n_tiles_listed : c->n_tiles;
     c->stats.screened = c->ref_pairs_pass ? 4 : c->screened ? (c->screened2 ? 3 : 1) : 0;
     c->stats.screen_fp6 = c->fp6_pass ? 1 : abandoned ? 2 : 0;
     c->stats.fp6_sampled = c->fp6_sampled ? 1 : 0;
@@ -1629,7 +1812,7 @@ int wld_dense(wld_ctx *c, float *d, float *d_prime, float *r2, uint8_t *valid) {
     const size_t L = c->L, LL = L * L;
     if (LL == 0) return WLD_OK;
     if (L > 8192) return fail(WLD_E_ARG, "wld_dense is for tests (n_sites <= 8192)");
-    WLD_TRY(build_tiles(c, 0, chunks_of(L)));
+    WLD_TRY(build_tiles(c, 0, chunks_of(L), false));  // every tile: wld_dense ignores the window
     DevBuf dd, ddp, dr2, dv;
     int st = WLD_OK;
     if ((st = ensure(dd, LL * 4)) || (st = ensure(ddp, LL * 4)) || (st = ensure(dr2, LL * 4)) || (st = ensure(dv, LL))) {
@@ -1705,7 +1888,7 @@ int run_host_range(wld_ctx *c, float r2_threshold, uint32_t lb, uint32_t le,
         uint32_t e = b;
         uint64_t pairs = 0;
         while (e < le) {
-            const uint64_t p1 = pairs_in_chunks(c->L, e, e + 1);
+            const uint64_t p1 = run_pairs(c, e, e + 1);  // (in-window pairs under a window)
             if (e > b && pairs + p1 > limit) break;
             pairs += p1;
             ++e;
@@ -1753,9 +1936,12 @@ int run_host_group(wld_ctx *g, float thr, const std::function<void(uint64_t)> *o
     // every shard's range before any thread starts: an early return must not
     // leave a joinable std::thread behind (std::terminate)
     std::vector<uint32_t> lb(G), le(G);
+    // (under a window: the partition balanced by in-window pairs, and their counts)
+    const bool win = window_on(g->members[0]);
     for (int k = 0; k < G; ++k) {
-        WLD_TRY(wld_shard_chunks(L, G, k, &lb[k], &le[k]));
-        pairs[k] = pairs_in_chunks(L, lb[k], le[k]);
+        if (win) WLD_TRY(wld_shard_chunks_window(g->members[0], G, k, &lb[k], &le[k]));
+        else WLD_TRY(wld_shard_chunks(L, G, k, &lb[k], &le[k]));
+        pairs[k] = run_pairs(g->members[0], lb[k], le[k]);
     }
     std::deque<uint64_t> events;  // chunk pair counts from the members, in completion order
     const std::function<void(uint64_t)> push = [&](uint64_t p) {

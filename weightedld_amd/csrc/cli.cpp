@@ -11,6 +11,10 @@
 //                      list of ordinals (repeats allowed) in this one process
 //                      (wld_create_multi); overrides --device
 //   --kernel K         auto | valu | mfma (default auto)
+//   --max-distance D   only pairs at most D apart in parent coordinates (VCF
+//   --max-sites K      POS, alignment columns) / at most K sites of interest
+//                      apart (wld_set_window; a distance window needs a
+//                      non-decreasing site map, else the library's message)
 #include <chrono>
 #include <cinttypes>
 #include <cmath>
@@ -189,6 +193,7 @@ struct Opt {
     int device = 0;
     std::vector<int> devices;  // --devices: a multi-device context
     int kernel = WLD_KERNEL_AUTO;
+    uint64_t max_distance = 0, max_sites = 0;  // --max-distance / --max-sites: wld_set_window (0: no limit)
 };
 
 void usage(FILE *f) {
@@ -221,7 +226,11 @@ void usage(FILE *f) {
             "        --vcf-input <vcf-input>              (addition) VCF input, WeightedLD.py handle_vcf semantics\n"
             "        --device <device>                    (addition) HIP device ordinal [default: 0]\n"
             "        --devices <devices>                  (addition) shard over G devices (0..G-1) or a list \"0,1,..\"\n"
-            "        --kernel <kernel>                    (addition) auto | valu | mfma [default: auto]\n");
+            "        --kernel <kernel>                    (addition) auto | valu | mfma [default: auto]\n"
+            "        --max-distance <max-distance>        (addition) only pairs at most this far apart in parent\n"
+            "                                             coordinates (VCF POS, alignment columns) [default: no limit]\n"
+            "        --max-sites <max-sites>              (addition) only pairs at most this many sites of interest\n"
+            "                                             apart [default: no limit]\n");
 }
 
 [[noreturn]] void arg_error(const char *msg, const char *arg) {
@@ -308,6 +317,11 @@ Opt parse(int argc, char **argv) {
                     at = e + 1;
                 }
             }
+        } else if (a == "--max-distance" || a == "--max-sites") {
+            const std::string name = a, v = need(name.c_str());
+            if (v.empty() || v.find_first_not_of("0123456789") != std::string::npos || v.size() > 19)
+                arg_error(("Invalid value for '" + name + "':").c_str(), v.c_str());
+            (name == "--max-distance" ? o.max_distance : o.max_sites) = strtoull(v.c_str(), nullptr, 10);
         } else if (a == "--kernel") {
             std::string k = need("--kernel");
             o.kernel = k == "valu" ? WLD_KERNEL_VALU : k == "mfma" ? WLD_KERNEL_MFMA : WLD_KERNEL_AUTO;
@@ -562,6 +576,10 @@ int main(int argc, char **argv) {
         if (opt.exact_sums) {
             int s2 = wld_set_option(ctx, WLD_OPT_REF_SUMS, 0);
             if (s2 != WLD_OK) die(s2, "wld_set_option");
+        }
+        if (opt.max_distance || opt.max_sites) {
+            int s2 = wld_set_window(ctx, opt.max_distance, opt.max_sites);
+            if (s2 != WLD_OK) die(s2, "wld_set_window");
         }
         return ctx;
     };

@@ -45,6 +45,12 @@ struct OrderArgs {
     // gather destination) records what it found here and skips the access
     // instead of faulting the context; run_complete turns it into WLD_E_STATE
     unsigned *guard;
+    // the run's window (wld_set_window; both null without one): win_hi[a] =
+    // the last in-window partner of site a ([LP], a itself where it has none
+    // and for padding sites), and the in-window pair count of every linear
+    // chunk (what tile_done logs instead of the chunk's geometric count)
+    const uint32_t *win_hi;
+    const uint32_t *win_pairs;
 };
 
 // report_guard bits (wld_run_stats.guard and the WLD_E_STATE message)
@@ -57,6 +63,11 @@ enum : unsigned {
 };
 __device__ inline void report_guard(const OrderArgs &o, unsigned bit) {
     if (o.guard) __hip_atomic_store(o.guard, bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+// The window's part of every row-emitting kernel's pass test: b is one of a's
+// in-window partners (a < b given; a < LP).  Uniform branch; no window, no load.
+__device__ __forceinline__ bool in_window(const OrderArgs &o, uint32_t a, uint32_t b) {
+    return !o.win_hi || b <= o.win_hi[a];
 }
 // a tile (ta << 16 | tb) the pair kernels may compute: ta <= tb < T_used
 __device__ inline bool tile_in_range(uint32_t tile, uint32_t L) {
@@ -297,6 +308,16 @@ bool launch_pair_mfma(const MfmaLaunch &m, const OrderArgs &o, const DenseArgs *
 // chunk into chunk_left[lin], prog_n = 0
 void launch_progress_init(unsigned *chunk_left, uint32_t lin_begin, uint32_t count, uint32_t n_chunk_rows, uint32_t L,
                           unsigned *prog_n, hipStream_t s);
+// the same under a window: the tiles of the run's list only (n_tiles entries,
+// kNoTile padding skipped); a chunk without a listed tile stays at 0 and is
+// never reported
+void launch_progress_init_window(unsigned *chunk_left, uint32_t lin_begin, uint32_t count, uint32_t n_chunk_rows,
+                                 const uint32_t *tiles, uint32_t n_tiles, unsigned *prog_n, hipStream_t s);
+// The window's per-site limits (window_plan.hpp limits, bit for bit): hi[a] =
+// the last b <= min(L - 1, a + K) (K == 0: L - 1) with pos[b] - pos[a] <= D
+// (D == 0: no limit; pos null: pos[i] = i), hi[a] = a for a in [L, LP)
+void launch_window_limits(const uint32_t *pos, uint32_t L, uint32_t LP, uint64_t D, uint64_t K, uint32_t *hi,
+                          hipStream_t s);
 // zeroes the run state (staging cursor, row total, every chunk total)
 void launch_run_init(unsigned long long *counters, uint32_t *chunk_total, uint32_t n_chunks, hipStream_t s);
 // the run's chunk scan as a launch of its own (ScanArgs; ticket unused)

@@ -194,6 +194,66 @@ void launch_progress_init(unsigned *chunk_left, uint32_t lin_begin, uint32_t cou
                        chunk_left, lin_begin, count, n_chunk_rows, T_used, prog_n);
 }
 
+// Under a window the run's list holds only the tiles with an in-window pair:
+// each listed tile of the range's chunks counts its kTileQuarters (the
+// countdowns zeroed before the launch).  A chunk without a listed tile stays
+// at 0: no tile_done ever reaches it, and it is never reported.
+__global__ __launch_bounds__(256) void progress_init_window_kernel(unsigned *__restrict__ chunk_left,
+                                                                    uint32_t lin_begin, uint32_t count,
+                                                                    uint32_t n_chunk_rows,
+                                                                    const uint32_t *__restrict__ tiles,
+                                                                    uint32_t n_tiles, unsigned *__restrict__ prog_n) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i == 0) *prog_n = 0;
+    if (i >= n_tiles) return;
+    const uint32_t tile = tiles[i];
+    if (tile == kNoTile) return;
+    const uint32_t row = (tile >> 16) / kTilesPerChunk, col = (tile & 0xFFFFu) / kTilesPerChunk;
+    if (row > col || col >= n_chunk_rows) return;
+    const uint32_t lin = chunk_linear(n_chunk_rows, row, col);
+    if (lin < lin_begin || lin - lin_begin >= count) return;  // (the list is the range's: never taken)
+    atomicAdd(&chunk_left[lin], kTileQuarters);
+}
+
+void launch_progress_init_window(unsigned *chunk_left, uint32_t lin_begin, uint32_t count, uint32_t n_chunk_rows,
+                                 const uint32_t *tiles, uint32_t n_tiles, unsigned *prog_n, hipStream_t s) {
+    (void)hipMemsetAsync(chunk_left + lin_begin, 0, (size_t)count * sizeof(unsigned), s);
+    hipLaunchKernelGGL(progress_init_window_kernel, dim3((std::max<uint32_t>(n_tiles, 1) + 255) / 256), dim3(256), 0, s,
+                       chunk_left, lin_begin, count, n_chunk_rows, tiles, n_tiles, prog_n);
+}
+
+// The window's per-site limits, one thread per site: the binary search of
+// window_plan.hpp limits on the resident site map (same bounds, same midpoint,
+// so the same hi bit for bit).
+__global__ __launch_bounds__(256) void window_limits_kernel(const uint32_t *__restrict__ pos, uint32_t L, uint32_t LP,
+                                                             uint64_t D, uint64_t K, uint32_t *__restrict__ hi) {
+    const uint32_t a = blockIdx.x * 256 + threadIdx.x;
+    if (a >= LP) return;
+    if (a >= L) {
+        hi[a] = a;
+        return;
+    }
+    uint32_t h = L - 1;
+    if (K && K < (uint64_t)(h - a)) h = a + (uint32_t)K;
+    if (D) {
+        const uint64_t lim = (uint64_t)(pos ? pos[a] : a) + (D < 0xFFFFFFFFull ? D : 0xFFFFFFFFull);
+        uint32_t lo = a, up = h;
+        while (lo < up) {
+            const uint32_t mid = lo + (up - lo + 1) / 2;
+            if ((uint64_t)(pos ? pos[mid] : mid) <= lim) lo = mid;
+            else up = mid - 1;
+        }
+        h = lo;
+    }
+    hi[a] = h;
+}
+
+void launch_window_limits(const uint32_t *pos, uint32_t L, uint32_t LP, uint64_t D, uint64_t K, uint32_t *hi,
+                          hipStream_t s) {
+    hipLaunchKernelGGL(window_limits_kernel, dim3((std::max<uint32_t>(LP, 1) + 255) / 256), dim3(256), 0, s, pos, L, LP,
+                       D, K, hi);
+}
+
 void launch_run_init(unsigned long long *counters, uint32_t *chunk_total, uint32_t n_chunks, hipStream_t s) {
     const unsigned blocks = (unsigned)std::min<size_t>((std::max<size_t>(n_chunks, 4) + 255) / 256, 2048);
     hipLaunchKernelGGL(run_init_kernel, dim3(blocks), dim3(256), 0, s, counters, chunk_total, n_chunks);

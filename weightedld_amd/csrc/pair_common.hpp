@@ -302,10 +302,12 @@ __device__ __forceinline__ void tile_done(const OrderArgs &o, uint32_t ta, uint3
                                           uint32_t quarters = kTileQuarters) {
     if (!o.chunk_left) return;
     const uint32_t row = ta / kTilesPerChunk, col = tb / kTilesPerChunk;
-    if (atomicSub(&o.chunk_left[chunk_linear(n_chunk_rows, row, col)], quarters) == quarters) {
+    const uint32_t lin = chunk_linear(n_chunk_rows, row, col);
+    if (atomicSub(&o.chunk_left[lin], quarters) == quarters) {
         const unsigned slot = atomicAdd(o.prog_n, 1u);
-        __hip_atomic_store(&o.prog_log[slot], (unsigned long long)chunk_pairs(o.L, row, col), __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_SYSTEM);
+        // (under a window: the chunk's in-window pairs)
+        const unsigned long long pairs = o.win_pairs ? o.win_pairs[lin] : chunk_pairs(o.L, row, col);
+        __hip_atomic_store(&o.prog_log[slot], pairs, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
 }
 

@@ -600,7 +600,7 @@ __device__ __forceinline__ void tile_epilogue(const SumFn &sum, const Acc &acc, 
                 dn.valid[k] = valid ? 1 : 0;
             }
         } else {
-            if (ok) pass |= 1u << i;  // lib.rs:660 strict '>'
+            if (ok && in_window(o, a, b)) pass |= 1u << i;  // lib.rs:660 strict '>'; the run's window
         }
     }
     if constexpr (MODE == kModeDense) return;

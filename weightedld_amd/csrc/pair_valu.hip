@@ -405,7 +405,8 @@ __global__ __launch_bounds__(256, MF ? (REF ? WLD_VALU_REF_WG : WLD_VALU_MF_WG) 
                 } else {
                     // lib.rs:660 strict '>' (a skipped sub-block's pairs provably fail;
                     // an empty slot's pairs alias slot 0's sub-block)
-                    if (valid && r2 > thr && us[j] && ((bits >> (4 * (al >> 4) + (bl >> 4))) & 1u))
+                    if (valid && r2 > thr && us[j] && ((bits >> (4 * (al >> 4) + (bl >> 4))) & 1u) &&
+                        in_window(o, a, b))
                         passmask[i] |= 1u << j;
                 }
             }
@@ -870,7 +871,8 @@ __global__ __launch_bounds__(256, LOOP ? WLD_REF_ITEML_WG : WLD_REF_ITEM_WG) voi
             res[e][0] = d;
             res[e][1] = dp;
             res[e][2] = r2;
-            if (has && a < b && b < L && ((okA4 >> (8 * e)) & 0xFFu) && okB && r2 > thr) passmask |= 1u << e;
+            if (has && a < b && b < L && ((okA4 >> (8 * e)) & 0xFFu) && okB && r2 > thr && in_window(o, a, b))
+                passmask |= 1u << e;
         }
         // ---- compaction: the tile's 64x64 pass bits, rows in b order ---------
         const bool own_row = tid < kTile && ((owned >> (tid >> 4)) & 1u);
@@ -1112,7 +1114,8 @@ __global__ __launch_bounds__(256) void ref_compact_kernel(RefRowsLaunch r, Order
                 const bool in = c0 + lane < total;
                 const uint32_t a = in ? o.st_a[i] : 0u, b = in ? o.st_b[i] : 0u;
                 const float d = in ? o.st_d[i] : 0.0f, dp = in ? o.st_dp[i] : 0.0f, r2 = in ? o.st_r2[i] : 0.0f;
-                const bool pass = in && r2 > r.thr;
+                // (the candidate pass staged in-window pairs only; a < L: nothing read through a bad row)
+                const bool pass = in && r2 > r.thr && a < o.L && in_window(o, a, b);
                 const uint64_t bal = __ballot(pass);
                 if (pass) {
                     const uint32_t pos = base + kept + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
