@@ -126,7 +126,8 @@ int wld_create(int device, wld_ctx **out);
  * concurrently, and return the rows in the reference order (shards
  * concatenated in descending shard order).  Options and the kernel choice
  * apply to every member; wld_last_stats reports member 0's kernel with the
- * group's pair/row totals.  Other device entry points fail with WLD_E_STATE
+ * group's pair/row totals.  wld_run_summary shards the same way and adds the
+ * members' summaries.  Other device entry points fail with WLD_E_STATE
  * on such a context.  With n_devices == 1 it returns a plain single-device
  * context (wld_create(devices[0], out)), on which every entry point works. */
 int wld_create_multi(const int *devices, int n_devices, wld_ctx **out);
@@ -495,6 +496,75 @@ typedef struct {
                                  accounting lost a count (the tests assert 0) */
 } wld_run_stats;
 int wld_last_stats(wld_ctx *ctx, wld_run_stats *out);
+
+/* ---- LD summaries: per-site LD scores and r2 decay by distance (not in the
+ * reference; what LD-decay curves and LD-score tools need from every pair) ----
+ *
+ * wld_run_summary evaluates every pair a < b of the linear chunk range
+ * [chunk_begin,chunk_end) (end 0 = all; a pair belongs to chunk (a/256, b/256)
+ * as in wld_run_chunks) that is in the context's current window
+ * (wld_set_window), and reduces the pairs on the device: no row is produced,
+ * staged or copied, so there is no 2^32 pairs-per-run limit and the result is
+ * O(n_sites + n_bins) numbers.  Every such pair falls into exactly one class:
+ *   none       single_weighted_ld_pair gives None (lib.rs:404-410: a site
+ *              without a major or minor symbol);
+ *   nonfinite  Some, but r2 is NaN or +-inf;
+ *   counted    Some and r2 finite.
+ * r2 is the f32 value the default row path (WLD_OPT_REF_SUMS 1) puts in the
+ * pair's row, bit for bit: the summary always sums in lib.rs's order.
+ * WLD_OPT_REF_SUMS, the kernel choice and the screen options do not apply, and
+ * no threshold applies.
+ *
+ * Outputs (library-allocated; release with wld_summary_free).  Site arrays
+ * are indexed by LOADED site index and have n_sites entries:
+ *   pairs, none_pairs, nonfinite_pairs, counted_pairs
+ *              pairs = none_pairs + nonfinite_pairs + counted_pairs
+ *                    = wld_window_pairs_in_chunks(begin, end);
+ *   r2_sum     sum of (double) r2 over the counted pairs;
+ *   score[i]   sum of (double) r2 over the counted pairs that contain site i
+ *              (each pair adds to both of its sites);
+ *   partners[i] the number of those pairs; sum_i partners[i] = 2 counted_pairs;
+ *   bin_pairs[k], bin_r2_sum[k]  (bin_width > 0 only, n_bins entries each; NULL
+ *              otherwise) the counted pairs with
+ *              k = min((pos[b] - pos[a]) / bin_width, n_bins - 1) and the sum of
+ *              their r2, pos[i] = site_map[i] or i without a map — the distance
+ *              the window uses; the last bin also takes everything beyond it;
+ *              sum_k bin_pairs[k] = counted_pairs;
+ *   kernel_ms  HIP-event time of the summary launch (device group: the
+ *              slowest member's).
+ * All counts are exact.  The f64 sums are NOT bitwise reproducible from run to
+ * run: tiles add to a destination with f64 atomics in whatever order they
+ * finish.  Every term is exact ((double) of an f32), so each sum is within the
+ * rounding of an any-order f64 sum of its terms: relative error at most about
+ * n 2^-53 for n nonnegative terms.  Summaries over disjoint chunk ranges add
+ * up to the whole run's (counts exactly, sums to that rounding).
+ *
+ * On a device group (wld_create_multi) the range is sharded as wld_run_host
+ * shards it (wld_shard_chunks / wld_shard_chunks_window), the members run
+ * concurrently and their summaries are added on the host in member order.
+ *
+ * WLD_E_ARG: n_bins > 1024; bin_width > 0 with n_bins == 0; bin_width > 0 on
+ * a site_map that descends (the rule of wld_set_window with a distance; the
+ * message names the first offending index); non-finite weights (a load that
+ * takes the row path's select loop); chunk_begin > chunk_end.  WLD_E_STATE:
+ * before a load, or while a run is in flight.  A summary changes nothing a
+ * later row run depends on, and wld_last_stats keeps describing the last row
+ * run.  No progress callback. */
+typedef struct {
+    uint64_t n_sites;
+    uint64_t bin_width;
+    uint32_t n_bins; /* entries of the bin arrays: 0 when bin_width == 0 */
+    uint64_t pairs, none_pairs, nonfinite_pairs, counted_pairs;
+    double r2_sum;
+    double *score;
+    uint32_t *partners;
+    uint64_t *bin_pairs;
+    double *bin_r2_sum;
+    double kernel_ms;
+} wld_summary;
+int wld_run_summary(wld_ctx *ctx, uint32_t chunk_begin, uint32_t chunk_end, uint64_t bin_width, uint32_t n_bins,
+                    wld_summary *out);
+void wld_summary_free(wld_summary *s);
 
 #ifdef __cplusplus
 }

@@ -71,6 +71,24 @@ class RunStats(ctypes.Structure):
     ]
 
 
+class Summary(ctypes.Structure):
+    _fields_ = [
+        ("n_sites", ctypes.c_uint64),
+        ("bin_width", ctypes.c_uint64),
+        ("n_bins", ctypes.c_uint32),
+        ("pairs", ctypes.c_uint64),
+        ("none_pairs", ctypes.c_uint64),
+        ("nonfinite_pairs", ctypes.c_uint64),
+        ("counted_pairs", ctypes.c_uint64),
+        ("r2_sum", ctypes.c_double),
+        ("score", ctypes.POINTER(ctypes.c_double)),
+        ("partners", ctypes.POINTER(ctypes.c_uint32)),
+        ("bin_pairs", ctypes.POINTER(ctypes.c_uint64)),
+        ("bin_r2_sum", ctypes.POINTER(ctypes.c_double)),
+        ("kernel_ms", ctypes.c_double),
+    ]
+
+
 PROGRESS_FN = ctypes.CFUNCTYPE(None, ctypes.c_uint64, ctypes.c_void_p)
 
 # name -> (restype, argtypes); every symbol include/weightedld.h declares.
@@ -143,6 +161,9 @@ SIGNATURES = {
     "wld_rows_copy_device": (_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "wld_dense": (_int, [_vp, _f32p, _f32p, _f32p, _u8p]),
     "wld_last_stats": (_int, [_vp, ctypes.POINTER(RunStats)]),
+    "wld_run_summary": (_int, [_vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint32,
+                               ctypes.POINTER(Summary)]),
+    "wld_summary_free": (None, [ctypes.POINTER(Summary)]),
 }
 
 _lib = None

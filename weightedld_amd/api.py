@@ -13,13 +13,13 @@ from collections import namedtuple
 
 import numpy as np
 
-from ._lib import (KERNEL_AUTO, KERNEL_MFMA, KERNEL_VALU, OPTIONS, PROGRESS_FN, Pairs, RunStats, WldError, check,
-                   lib)
+from ._lib import (KERNEL_AUTO, KERNEL_MFMA, KERNEL_VALU, OPTIONS, PROGRESS_FN, Pairs, RunStats, Summary, WldError,
+                   check, lib)
 
 __all__ = [
     "Symbol", "SymbolHistogram", "SiteSet", "LdStats", "PairStore", "read_fasta", "read_vcf",
     "is_site_of_interest", "henikoff_weights", "single_weighted_ld_pair", "all_weighted_ld_pairs",
-    "Context", "default_context", "KERNEL_AUTO", "KERNEL_VALU", "KERNEL_MFMA", "OPTIONS", "WldError",
+    "ld_summary", "LdSummary", "Context", "default_context", "KERNEL_AUTO", "KERNEL_VALU", "KERNEL_MFMA", "OPTIONS", "WldError",
 ]
 
 
@@ -198,6 +198,25 @@ class PairStore:
                    LdStats(float(self.r2[i]), float(self.d[i]), float(self.d_prime[i])))
 
     __iter__ = iter
+
+
+class LdSummary:
+    """wld_summary as numpy arrays and ints (Context.run_summary, ld_summary):
+    the class counts (pairs = none_pairs + nonfinite_pairs + counted_pairs),
+    r2_sum, per LOADED site score (sum of r2 over the site's counted pairs)
+    and partners (their number), and with bins bin_pairs / bin_r2_sum
+    (bin k: distances [k bin_width, (k + 1) bin_width), the last bin open
+    ended; None without bins)."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def mean_r2(self):
+        """Per-bin mean r2 (nan for an empty bin); None without bins."""
+        if self.bin_pairs is None:
+            return None
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(self.bin_pairs > 0, self.bin_r2_sum / self.bin_pairs, np.nan)
 
 
 # Live contexts, closed (newest first) by an exit handler while the HIP
@@ -401,6 +420,29 @@ class Context:
         check(lib().wld_run_host(self._h, r2_threshold, cb, None, ctypes.byref(out)), "wld_run_host")
         return _take_pairs(out)
 
+    def run_summary(self, bin_width=0, n_bins=0, chunk_begin=0, chunk_end=0):
+        """wld_run_summary: every in-window pair of the linear chunk range
+        (end 0 = all) reduced on the device to an LdSummary — no rows.  With
+        bin_width > 0 also the r2 decay histogram over n_bins distance bins."""
+        out = Summary()
+        check(lib().wld_run_summary(self._h, chunk_begin, chunk_end, int(bin_width or 0), int(n_bins or 0),
+                                    ctypes.byref(out)), "wld_run_summary")
+        L, nb = int(out.n_sites), int(out.n_bins)
+
+        def grab(p, n, dt):
+            return np.ctypeslib.as_array(p, shape=(n,)).astype(dt, copy=True) if n else np.zeros(0, dtype=dt)
+
+        res = LdSummary(pairs=int(out.pairs), none_pairs=int(out.none_pairs),
+                        nonfinite_pairs=int(out.nonfinite_pairs), counted_pairs=int(out.counted_pairs),
+                        r2_sum=float(out.r2_sum), score=grab(out.score, L, np.float64),
+                        partners=grab(out.partners, L, np.uint32),
+                        bin_width=int(out.bin_width), n_bins=nb,
+                        bin_pairs=grab(out.bin_pairs, nb, np.uint64) if nb else None,
+                        bin_r2_sum=grab(out.bin_r2_sum, nb, np.float64) if nb else None,
+                        kernel_ms=float(out.kernel_ms))
+        lib().wld_summary_free(ctypes.byref(out))
+        return res
+
     def stream_ptr(self):
         """The context's hipStream_t as an int (torch.cuda.ExternalStream)."""
         return int(lib().wld_stream(self._h) or 0)
@@ -538,6 +580,27 @@ def all_weighted_ld_pairs(site_set, weights, r2_threshold, progress_report=None,
                                           None if sm is None else _p(sm, ctypes.c_uint64), _p(w, ctypes.c_float),
                                           r2_threshold, cb, None, ctypes.byref(out)), "all_weighted_ld_pairs")
     return _take_pairs(out)
+
+
+def ld_summary(site_set, weights, bin_width=None, n_bins=None, max_distance=None, max_sites=None, ctx=None):
+    """Per-site LD scores and (bin_width, n_bins given) the r2 decay by
+    distance of every pair of site_set (not in the reference): loads the set
+    and runs Context.run_summary under the window max_distance / max_sites
+    (the context's own window is restored afterwards).  Returns an LdSummary
+    indexed by the set's own site index; distances are in site_map
+    coordinates."""
+    ctx = ctx or default_context()
+    w = np.ascontiguousarray(weights, dtype=np.float32)
+    if w.size != site_set.n_seqs():
+        raise ValueError("weights must have n_seqs entries")
+    before = ctx.window()
+    if max_distance is not None or max_sites is not None:
+        ctx.set_window(max_distance, max_sites)
+    try:
+        ctx.load(site_set.buffer, w, site_set.site_map)
+        return ctx.run_summary(bin_width or 0, n_bins or 0)
+    finally:
+        ctx.set_window(*before)
 
 
 def _take_pairs(out):

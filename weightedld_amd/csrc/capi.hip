@@ -24,6 +24,7 @@
 #include "common.hpp"
 #include "tile_order.hpp"
 #include "window_plan.hpp"
+#include "summary_plan.hpp"
 #include "kernels.hpp"
 
 using namespace wld;
@@ -229,6 +230,12 @@ struct wld_ctx {
     uint32_t n_tiles_listed = 0;         // its tiles without the XCD order's padding
     bool seg_clear = false;              // a windowed list was built: seg_cnt is zeroed before the next pass
 
+    // wld_run_summary: its accumulators (zeroed per call) and the two events
+    // around its launch (created at the first summary; the row path's events
+    // keep the last row run's times)
+    DevBuf sum_buf;
+    hipEvent_t ev_sum[2] = {};
+
     ~wld_ctx() {
         for (wld_ctx *m : members) delete m;
         if (!members.empty()) return;
@@ -237,10 +244,12 @@ struct wld_ctx {
         // buffers: it completes before they are freed
         if (stream && stream != own_stream) (void)hipStreamSynchronize(stream);
         DevBuf *all[] = {&keep, &htab, &htab_kept, &site_index, &raw, &wraw, &codes, &w_pad, &wstats, &site_ok, &site_map, &planes, &frag, &rcodes, &rw, &w6, &f6a, &f6b, &i8a, &i8b, &tiles, &cand, &f6_pairs, &fp6_probe_buf,
-                         &seg_cnt, &seg_off, &chunk_total, &chunk_base, &counters, &chunk_left, &prog_n, &win_hi, &win_pairs, &st_a, &st_b, &st_d,
+                         &seg_cnt, &seg_off, &chunk_total, &chunk_base, &counters, &chunk_left, &prog_n, &win_hi, &win_pairs, &sum_buf, &st_a, &st_b, &st_d,
                          &st_dp, &st_r2, &out_a, &out_b, &out_d, &out_dp, &out_r2};
         for (DevBuf *b : all) release(*b);
         for (auto &e : ev)
+            if (e) (void)hipEventDestroy(e);
+        for (auto &e : ev_sum)
             if (e) (void)hipEventDestroy(e);
         if (h_cnt) (void)hipHostFree(h_cnt);
         if (h_plog) (void)hipHostFree(h_plog);
@@ -251,8 +260,9 @@ struct wld_ctx {
 namespace {
 
 // Every single-device entry point starts here; a device group (wld_create_multi)
-// supports only wld_load, wld_run_host, wld_all_weighted_ld_pairs and the
-// option/kernel/stats calls, which dispatch to its members.
+// supports only wld_load, wld_run_host, wld_all_weighted_ld_pairs,
+// wld_run_summary and the option/kernel/stats calls, which dispatch to its
+// members.
 int set_dev(wld_ctx *c) {
     if (!c) return fail(WLD_E_ARG, "null context");
     if (!c->members.empty())
@@ -2044,6 +2054,184 @@ int wld_run_host(wld_ctx *c, float r2_threshold, wld_progress_fn progress, void 
         return run_host_group(c, r2_threshold, oc, out);
     }
     return run_host_range(c, r2_threshold, 0, chunks_of(c->L), oc, out);
+}
+
+namespace {
+// What wld_run_summary refuses, checked on a loaded single-device context
+// (every member of a group holds the same load).
+int summary_check(wld_ctx *c, uint64_t bin_width, uint32_t n_bins) {
+    if (n_bins > summary_plan::kMaxBins)
+        return fail(WLD_E_ARG, "wld_run_summary: n_bins %u exceeds %u", n_bins, summary_plan::kMaxBins);
+    if (bin_width && !n_bins) return fail(WLD_E_ARG, "wld_run_summary: bin_width %llu with n_bins 0",
+                                          (unsigned long long)bin_width);
+    if (c->safe)
+        return fail(WLD_E_ARG, "wld_run_summary needs finite weights (this load takes the select loop)");
+    if (bin_width && c->has_pos) {  // (the rule of a distance window: window_prepare)
+        const uint32_t *pos = c->pos_host.data();
+        const uint32_t i = window_plan::first_descent(pos, (uint32_t)c->L);
+        if (i < c->L)
+            return fail(WLD_E_ARG, "decay bins (bin_width %llu) need a non-decreasing site_map: "
+                                   "site_map[%u] = %u < site_map[%u] = %u",
+                        (unsigned long long)bin_width, i, pos[i], i - 1, pos[i - 1]);
+    }
+    return WLD_OK;
+}
+
+// The summary of the linear chunks [lb, le) on one device: the tile list of
+// the range under the window (build_tiles: the row path's cached list when it
+// covers the same range, else rebuilt — a windowed rebuild leaves seg_clear
+// set for the next row run), zeroed accumulators, one launch,
+// one copy back.  Touches no staging, segment count, chunk total, run counter
+// or row-path event.
+int summary_range(wld_ctx *c, uint32_t lb, uint32_t le, uint64_t bin_width, uint32_t n_bins,
+                  summary_plan::Summary *out) {
+    WLD_TRY(set_dev(c));
+    if (!c->loaded) return fail(WLD_E_STATE, "wld_run_summary before wld_load");
+    if (c->pend.active) return fail(WLD_E_STATE, "wld_run_summary during a run");
+    WLD_TRY(summary_check(c, bin_width, n_bins));
+    const size_t L = c->L, LP = c->LP, nb = bin_width ? n_bins : 0;
+    *out = summary_plan::Summary{};
+    out->score.assign(L, 0.0);
+    out->partners.assign(L, 0);
+    out->bin_pairs.assign(nb, 0);
+    out->bin_r2_sum.assign(nb, 0.0);
+    if (lb >= le) return WLD_OK;
+    WLD_TRY(ensure_ref_layout(c));
+    WLD_TRY(build_tiles(c, lb, le, true));
+    if (!c->n_tiles) return WLD_OK;  // (a window without a pair in the range)
+    for (auto &e : c->ev_sum)
+        if (!e) HIP_TRY(hipEventCreate(&e));
+    // {r2_sum, score[LP], bin_r2_sum[nb]} f64 | {counts[4], bin_pairs[nb]} u64 | partners[LP] u32
+    const size_t n_f64 = 1 + LP + nb, n_u64 = 4 + nb, bytes = 8 * (n_f64 + n_u64) + 4 * LP;
+    WLD_TRY(ensure(c->sum_buf, bytes));
+    double *d_f64 = ptr<double>(c->sum_buf);
+    unsigned long long *d_u64 = reinterpret_cast<unsigned long long *>(d_f64 + n_f64);
+    uint32_t *d_u32 = reinterpret_cast<uint32_t *>(d_u64 + n_u64);
+    HIP_TRY(hipMemsetAsync(c->sum_buf.p, 0, bytes, c->stream));
+    const SummaryArgs sa{d_u64, d_f64, d_f64 + 1, d_u32, nb ? d_u64 + 4 : nullptr, nb ? d_f64 + 1 + LP : nullptr,
+                         c->has_pos ? ptr<uint32_t>(c->site_map) : nullptr, bin_width, (uint32_t)nb};
+    const ValuLaunch v{ptr<uint8_t>(c->rcodes), ptr<float>(c->rw), ptr<uint8_t>(c->site_ok), ptr<uint32_t>(c->tiles),
+                       c->n_tiles, nullptr, (uint32_t)L, (uint32_t)c->NPr, chunk_rows_of(L), 0.0f, false, false, true,
+                       c->ref_cls, (uint32_t)(c->N % 8)};
+    OrderArgs o{};  // the window only
+    o.L = (uint32_t)L;
+    o.T = (uint32_t)(LP / kTile);
+    o.win_hi = c->tiles_windowed ? ptr<uint32_t>(c->win_hi) : nullptr;
+    HIP_TRY(hipEventRecord(c->ev_sum[0], c->stream));
+    launch_pair_summary(v, o, sa, c->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c->ev_sum[1], c->stream));
+    std::vector<unsigned char> h(bytes);
+    HIP_TRY(hipMemcpyAsync(h.data(), c->sum_buf.p, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    out->kernel_ms = event_ms(c->ev_sum[0], c->ev_sum[1]);
+    const double *h_f64 = reinterpret_cast<const double *>(h.data());
+    const uint64_t *h_u64 = reinterpret_cast<const uint64_t *>(h_f64 + n_f64);
+    const uint32_t *h_u32 = reinterpret_cast<const uint32_t *>(h_u64 + n_u64);
+    out->pairs = h_u64[0];
+    out->none_pairs = h_u64[1];
+    out->nonfinite_pairs = h_u64[2];
+    out->counted_pairs = h_u64[3];
+    out->r2_sum = h_f64[0];
+    std::copy(h_f64 + 1, h_f64 + 1 + L, out->score.begin());
+    std::copy(h_u32, h_u32 + L, out->partners.begin());
+    std::copy(h_f64 + 1 + LP, h_f64 + 1 + LP + nb, out->bin_r2_sum.begin());
+    std::copy(h_u64 + 4, h_u64 + 4 + nb, out->bin_pairs.begin());
+    // the kernel's own accounting against the host's plan
+    const uint64_t expect = run_pairs(c, lb, le);
+    if (out->pairs != expect || out->pairs != out->none_pairs + out->nonfinite_pairs + out->counted_pairs)
+        return fail(WLD_E_HIP, "internal: summary counted %llu pairs (%llu none, %llu nonfinite, %llu counted); "
+                               "the range holds %llu",
+                    (unsigned long long)out->pairs, (unsigned long long)out->none_pairs,
+                    (unsigned long long)out->nonfinite_pairs, (unsigned long long)out->counted_pairs,
+                    (unsigned long long)expect);
+    return WLD_OK;
+}
+
+// ... on a device group: member k takes its shard of the chunk sequence (as
+// run_host_group deals them) cut to [lb, le), on its own host thread; the
+// members' summaries are added in member order.
+int summary_group(wld_ctx *g, uint32_t lb, uint32_t le, uint64_t bin_width, uint32_t n_bins,
+                  summary_plan::Summary *out) {
+    const int G = (int)g->members.size();
+    wld_ctx *c0 = g->members[0];
+    std::vector<uint32_t> sb(G), se(G);
+    for (int k = 0; k < G; ++k) {  // every range before any thread starts
+        if (window_on(c0)) WLD_TRY(wld_shard_chunks_window(c0, G, k, &sb[k], &se[k]));
+        else WLD_TRY(wld_shard_chunks(c0->L, G, k, &sb[k], &se[k]));
+        sb[k] = std::max(sb[k], lb);
+        se[k] = std::max(sb[k], std::min(se[k], le));
+    }
+    std::vector<summary_plan::Summary> part(G);
+    std::vector<int> status(G, WLD_OK);
+    std::vector<std::string> msg(G);
+    std::vector<std::thread> th;
+    for (int k = 0; k < G; ++k)
+        th.emplace_back([&, k] {
+            status[k] = summary_range(g->members[k], sb[k], se[k], bin_width, n_bins, &part[k]);
+            if (status[k] != WLD_OK) msg[k] = wld_last_error();
+        });
+    for (auto &t : th) t.join();
+    for (int k = 0; k < G; ++k)
+        if (status[k] != WLD_OK)
+            return fail(status[k], "device %d (shard %d): %s", g->members[k]->device, k, msg[k].c_str());
+    *out = summary_plan::Summary{};
+    for (int k = 0; k < G; ++k) summary_plan::merge(*out, part[k]);
+    return WLD_OK;
+}
+}  // namespace
+
+int wld_run_summary(wld_ctx *c, uint32_t chunk_begin, uint32_t chunk_end, uint64_t bin_width, uint32_t n_bins,
+                    wld_summary *out) {
+    if (!out) return fail(WLD_E_ARG, "null out");
+    memset(out, 0, sizeof(*out));
+    if (!c) return fail(WLD_E_ARG, "null context");
+    wld_ctx *c0 = c->members.empty() ? c : c->members[0];
+    for (wld_ctx *m : c->members.empty() ? std::vector<wld_ctx *>{c} : c->members) {
+        if (!m->loaded) return fail(WLD_E_STATE, "wld_run_summary before wld_load");
+        if (m->pend.active) return fail(WLD_E_STATE, "wld_run_summary during a run");
+    }
+    WLD_TRY(summary_check(c0, bin_width, n_bins));
+    const uint32_t m = chunks_of(c0->L);
+    if (chunk_end == 0 || chunk_end > m) chunk_end = m;
+    if (chunk_begin > chunk_end) return fail(WLD_E_ARG, "chunk range [%u,%u) invalid", chunk_begin, chunk_end);
+    summary_plan::Summary s;
+    if (c->members.empty()) WLD_TRY(summary_range(c, chunk_begin, chunk_end, bin_width, n_bins, &s));
+    else WLD_TRY(summary_group(c, chunk_begin, chunk_end, bin_width, n_bins, &s));
+    const size_t L = c0->L, nb = bin_width ? n_bins : 0;
+    out->score = (double *)malloc(std::max<size_t>(L, 1) * sizeof(double));
+    out->partners = (uint32_t *)malloc(std::max<size_t>(L, 1) * sizeof(uint32_t));
+    if (nb) {
+        out->bin_pairs = (uint64_t *)malloc(nb * sizeof(uint64_t));
+        out->bin_r2_sum = (double *)malloc(nb * sizeof(double));
+    }
+    if (!out->score || !out->partners || (nb && (!out->bin_pairs || !out->bin_r2_sum))) {
+        wld_summary_free(out);
+        return fail(WLD_E_OOM, "host allocation of the summary (%zu sites, %zu bins) failed", L, nb);
+    }
+    std::copy(s.score.begin(), s.score.end(), out->score);
+    std::copy(s.partners.begin(), s.partners.end(), out->partners);
+    std::copy(s.bin_pairs.begin(), s.bin_pairs.end(), out->bin_pairs);
+    std::copy(s.bin_r2_sum.begin(), s.bin_r2_sum.end(), out->bin_r2_sum);
+    out->n_sites = L;
+    out->bin_width = bin_width;
+    out->n_bins = (uint32_t)nb;
+    out->pairs = s.pairs;
+    out->none_pairs = s.none_pairs;
+    out->nonfinite_pairs = s.nonfinite_pairs;
+    out->counted_pairs = s.counted_pairs;
+    out->r2_sum = s.r2_sum;
+    out->kernel_ms = s.kernel_ms;
+    return WLD_OK;
+}
+
+void wld_summary_free(wld_summary *s) {
+    if (!s) return;
+    free(s->score);
+    free(s->partners);
+    free(s->bin_pairs);
+    free(s->bin_r2_sum);
+    memset(s, 0, sizeof(*s));
 }
 
 int wld_all_weighted_ld_pairs(wld_ctx *c, const uint8_t *sites, size_t n_sites, size_t n_seqs,

@@ -15,6 +15,12 @@
 //   --max-sites K      POS, alignment columns) / at most K sites of interest
 //                      apart (wld_set_window; a distance window needs a
 //                      non-decreasing site map, else the library's message)
+//   --ld-score-output FILE   per-site LD score TSV (site, partners, ld_score)
+//   --decay-output FILE      r2 decay by distance TSV (bin_start, pairs, r2_sum,
+//   --decay-bin-width W      mean_r2), W in parent coordinates, B bins (default
+//   --decay-bins B           64; the last also takes every longer distance); one
+//                      device summary pass over every in-window pair serves
+//                      both files (wld_run_summary; no threshold applies)
 #include <chrono>
 #include <cinttypes>
 #include <cmath>
@@ -194,6 +200,8 @@ struct Opt {
     std::vector<int> devices;  // --devices: a multi-device context
     int kernel = WLD_KERNEL_AUTO;
     uint64_t max_distance = 0, max_sites = 0;  // --max-distance / --max-sites: wld_set_window (0: no limit)
+    std::string ld_score_output, decay_output;  // --ld-score-output / --decay-output: wld_run_summary
+    uint64_t decay_bin_width = 0, decay_bins = 64;
 };
 
 void usage(FILE *f) {
@@ -230,7 +238,15 @@ void usage(FILE *f) {
             "        --max-distance <max-distance>        (addition) only pairs at most this far apart in parent\n"
             "                                             coordinates (VCF POS, alignment columns) [default: no limit]\n"
             "        --max-sites <max-sites>              (addition) only pairs at most this many sites of interest\n"
-            "                                             apart [default: no limit]\n");
+            "                                             apart [default: no limit]\n"
+            "        --ld-score-output <ld-score-output>  (addition) Filename to write the per-site LD scores to (site,\n"
+            "                                             partners, ld_score: the sum of r2 with every in-window\n"
+            "                                             partner, no threshold), in Tab Separated Value format\n"
+            "        --decay-output <decay-output>        (addition) Filename to write the r2 decay by distance to\n"
+            "                                             (bin_start, pairs, r2_sum, mean_r2); needs --decay-bin-width\n"
+            "        --decay-bin-width <decay-bin-width>  (addition) width of a distance bin, in parent coordinates\n"
+            "        --decay-bins <decay-bins>            (addition) number of bins, at most 1024; the last one also\n"
+            "                                             takes every longer distance [default: 64]\n");
 }
 
 [[noreturn]] void arg_error(const char *msg, const char *arg) {
@@ -322,6 +338,15 @@ Opt parse(int argc, char **argv) {
             if (v.empty() || v.find_first_not_of("0123456789") != std::string::npos || v.size() > 19)
                 arg_error(("Invalid value for '" + name + "':").c_str(), v.c_str());
             (name == "--max-distance" ? o.max_distance : o.max_sites) = strtoull(v.c_str(), nullptr, 10);
+        } else if (a == "--ld-score-output") {
+            o.ld_score_output = need("--ld-score-output");
+        } else if (a == "--decay-output") {
+            o.decay_output = need("--decay-output");
+        } else if (a == "--decay-bin-width" || a == "--decay-bins") {
+            const std::string name = a, v = need(name.c_str());
+            if (v.empty() || v.find_first_not_of("0123456789") != std::string::npos || v.size() > 19)
+                arg_error(("Invalid value for '" + name + "':").c_str(), v.c_str());
+            (name == "--decay-bin-width" ? o.decay_bin_width : o.decay_bins) = strtoull(v.c_str(), nullptr, 10);
         } else if (a == "--kernel") {
             std::string k = need("--kernel");
             o.kernel = k == "valu" ? WLD_KERNEL_VALU : k == "mfma" ? WLD_KERNEL_MFMA : WLD_KERNEL_AUTO;
@@ -333,6 +358,12 @@ Opt parse(int argc, char **argv) {
     if (o.fasta_input.empty() && o.vcf_input.empty())
         arg_error("The following required arguments were not provided:", "--fasta-input <fasta-input>");
     if (!have_pair) arg_error("The following required arguments were not provided:", "--pair-output <pair-output>");
+    if (!o.decay_output.empty() && !o.decay_bin_width)
+        arg_error("The following required arguments were not provided:", "--decay-bin-width <decay-bin-width>");
+    if (o.decay_output.empty() && o.decay_bin_width)
+        arg_error("The argument '--decay-bin-width' needs", "--decay-output <decay-output>");
+    if (!o.decay_output.empty() && (o.decay_bins < 1 || o.decay_bins > 1024))
+        arg_error("Invalid value for '--decay-bins' (1 to 1024):", std::to_string(o.decay_bins).c_str());
     if (o.gpu_prepass && o.devices.size() > 1)
         arg_error("The argument '--gpu-prepass' cannot be used with", "--devices (the device pre-pass runs on one device)");
     return o;
@@ -470,6 +501,52 @@ int write_pair_stats(const std::string &path, const wld_pairs &p) {
     return ok ? WLD_OK : WLD_E_IO;
 }
 
+// --ld-score-output / --decay-output: one summary pass over every in-window
+// pair of the loaded set (wld_run_summary: same r2 as the pair TSV's rows, no
+// threshold), then the two TSVs.  parent[i]: the parent index of loaded site
+// i, as in the pair TSV.  Doubles print as %.9g; an empty bin's mean as nan.
+void write_summaries(const Opt &opt, wld_ctx *ctx, const std::vector<uint64_t> &parent) {
+    if (opt.ld_score_output.empty() && opt.decay_output.empty()) return;
+    using clk = std::chrono::steady_clock;
+    const auto sw = clk::now();
+    const bool decay = !opt.decay_output.empty();
+    wld_summary s;
+    const int st = wld_run_summary(ctx, 0, 0, decay ? opt.decay_bin_width : 0, decay ? (uint32_t)opt.decay_bins : 0, &s);
+    if (st != WLD_OK) die(st, "run_summary");
+    INFO("Summarized %s pairs (%s without a statistic) in %s", human((double)s.pairs).c_str(),
+         human((double)(s.none_pairs + s.nonfinite_pairs)).c_str(), fmt_duration(clk::now() - sw).c_str());
+    auto write = [&](const std::string &path, const std::string &text) {
+        INFO("Writing output to %s", debug_path(path).c_str());
+        FILE *f = fopen(path.c_str(), "wb");
+        const bool ok = f && fwrite(text.data(), 1, text.size(), f) == text.size();
+        if ((f && fclose(f) != 0) || !ok) {
+            fprintf(stderr, "Error: cannot write %s\n", path.c_str());
+            quit(1);
+        }
+    };
+    char line[160];
+    if (!opt.ld_score_output.empty()) {
+        std::string out = "site\tpartners\tld_score\n";
+        for (uint64_t i = 0; i < s.n_sites; ++i) {
+            snprintf(line, sizeof line, "%" PRIu64 "\t%u\t%.9g\n", parent[i], s.partners[i], s.score[i]);
+            out += line;
+        }
+        write(opt.ld_score_output, out);
+    }
+    if (decay) {
+        std::string out = "bin_start\tpairs\tr2_sum\tmean_r2\n";
+        for (uint32_t k = 0; k < s.n_bins; ++k) {
+            const int n = snprintf(line, sizeof line, "%" PRIu64 "\t%" PRIu64 "\t%.9g\t", (uint64_t)k * s.bin_width,
+                                   s.bin_pairs[k], s.bin_r2_sum[k]);
+            if (s.bin_pairs[k]) snprintf(line + n, sizeof line - n, "%.9g\n", s.bin_r2_sum[k] / (double)s.bin_pairs[k]);
+            else snprintf(line + n, sizeof line - n, "nan\n");
+            out += line;
+        }
+        write(opt.decay_output, out);
+    }
+    wld_summary_free(&s);
+}
+
 // (debug level only, so info-level output is the reference's: the LD pass's
 // progress_report calls — progress(0), then one per 256x256 chunk)
 void log_progress(const ProgressBar &pb) {
@@ -535,7 +612,11 @@ int run_gpu_prepass(const Opt &opt, wld_siteset *siteset, wld_ctx *ctx) {
             die(st, "all_weighted_ld_pairs");
         log_progress(pb);
     }
-    return finish(opt, ctx, pairs, clk::now() - sw, total_pairs);
+    const auto dur = clk::now() - sw;
+    std::vector<uint64_t> parent(L);
+    if (L && (st = wld_site_map_copy(ctx, parent.data())) != WLD_OK) die(st, "site_map_copy");
+    write_summaries(opt, ctx, parent);
+    return finish(opt, ctx, pairs, dur, total_pairs);
 }
 
 }  // namespace
@@ -640,7 +721,11 @@ int main(int argc, char **argv) {
         if (st != WLD_OK) die(st, "all_weighted_ld_pairs");
         log_progress(pb);
     }
-    const int rc = finish(opt, ctx, pairs, clk::now() - sw, total_pairs);
+    const auto dur = clk::now() - sw;
+    std::vector<uint64_t> parent(L);
+    for (size_t i = 0; i < L; ++i) parent[i] = wld_siteset_parent_site_index(filtered, i);
+    write_summaries(opt, ctx, parent);
+    const int rc = finish(opt, ctx, pairs, dur, total_pairs);
     wld_siteset_free(filtered);
     wld_siteset_free(siteset);
     return rc;

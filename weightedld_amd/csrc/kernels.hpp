@@ -119,6 +119,23 @@ struct DenseArgs {
     uint8_t *valid;
 };
 
+// The accumulators of a summary run (pair_summary.hip; wld_run_summary): all
+// zero before the launch, added to by at most one atomic per destination and
+// tile.  counts = {pairs, none, nonfinite, counted}; score/partners have LP
+// entries; the bin arrays n_bins (bin_width 0: no bins, both null).  pos: the
+// resident site_map (L entries; null: pos[i] = i), read only with bins.
+struct SummaryArgs {
+    unsigned long long *counts;
+    double *r2_sum;
+    double *score;
+    uint32_t *partners;
+    unsigned long long *bin_pairs;
+    double *bin_r2_sum;
+    const uint32_t *pos;
+    uint64_t bin_width;
+    uint32_t n_bins;
+};
+
 // encode.hip
 // site_index: nullptr, or the kept-site map of the device pre-pass (row s of the
 // filtered set = raw row site_index[s])
@@ -186,6 +203,12 @@ void launch_ref_rows(const RefRowsLaunch &r, const OrderArgs &o, hipStream_t s);
 void ref_layout_dims(size_t N, uint32_t *cls, uint32_t *tail, size_t *NPr);
 void launch_ref_layout(const uint8_t *codes, const float *w_pad, size_t LP, size_t NP, size_t N, uint8_t *rcodes,
                        float *rw, hipStream_t s);
+
+// pair_summary.hip
+// Every tile of v's list (v.ref: the lane-class layout, finite weights) summed
+// in lib.rs's order and reduced into s; o gives the window (win_hi) only —
+// nothing of the row path's run state is read or written.
+void launch_pair_summary(const ValuLaunch &v, const OrderArgs &o, const SummaryArgs &s, hipStream_t st);
 
 // pair_mfma.hip
 bool mfma_supported();
