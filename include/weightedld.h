@@ -127,8 +127,8 @@ int wld_create(int device, wld_ctx **out);
  * concatenated in descending shard order).  Options and the kernel choice
  * apply to every member; wld_last_stats reports member 0's kernel with the
  * group's pair/row totals.  wld_run_summary shards the same way and adds the
- * members' summaries.  Other device entry points fail with WLD_E_STATE
- * on such a context.  With n_devices == 1 it returns a plain single-device
+ * members' summaries.  Other device entry points (wld_run_prune among them)
+ * fail with WLD_E_STATE on such a context.  With n_devices == 1 it returns a plain single-device
  * context (wld_create(devices[0], out)), on which every entry point works. */
 int wld_create_multi(const int *devices, int n_devices, wld_ctx **out);
 int wld_n_devices(const wld_ctx *ctx); /* 1, or the member count of a multi-device context */
@@ -565,6 +565,71 @@ typedef struct {
 int wld_run_summary(wld_ctx *ctx, uint32_t chunk_begin, uint32_t chunk_end, uint64_t bin_width, uint32_t n_bins,
                     wld_summary *out);
 void wld_summary_free(wld_summary *s);
+
+/* ---- LD pruning: a greedy r2-independent site set with tags (not in the
+ * reference; PLINK's --indep-pairwise, bcftools +prune) ----
+ *
+ * Graph.  The vertices are the loaded sites 0..L-1.  {a, b} is an edge iff the
+ * context, as configured now (window, kernel choice, WLD_OPT_REF_SUMS and every
+ * other option), would return a row for that pair from
+ * wld_run_host(ctx, r2_threshold, ...): the pair is in the window,
+ * single_weighted_ld_pair gives Some, and r2 > r2_threshold strictly (NaN is
+ * never an edge).  A site without a statistic has no edge.
+ *
+ * Order.  priority is NULL (index order) or n_sites floats: site u comes
+ * before v iff priority[u] > priority[v], or they compare equal (-0.0 and 0.0
+ * do) and u < v.  +-inf are allowed; a NaN gives WLD_E_ARG naming the first
+ * offending index.  The host turns the order into ranks (0 = first) with a
+ * stable sort; the device compares ranks only.
+ *
+ * Result.  The kept set is what sequential greedy selection gives — the
+ * lexicographically first maximal independent set under the order: visit the
+ * sites by rank, keep a site iff none of its neighbours has been kept.
+ *   keep[i]  1 kept, 0 removed; a site without edges is kept;
+ *   tag[i]   i for a kept site; for a removed site the LOADED index of its kept
+ *            neighbour with the smallest rank (one always exists and ranks
+ *            before i);
+ *   n_kept   the number of kept sites; edges: the rows at this threshold and
+ *            window;
+ *   rounds   decide launches enqueued (0 iff edges == 0); depends on
+ *            scheduling, not reproducible;
+ *   pair_ms  HIP-event time of the row passes (pair phase + ordering, summed
+ *            over the batches); prune_ms: of the CSR build, the rounds and
+ *            the tags (wld_prune_times splits it).
+ * keep, tag, n_kept and edges are a function of the graph and the order alone:
+ * identical from run to run and independent of batch sizes
+ * (WLD_OPT_HOST_BATCH_PAIRS), staging capacity, the screen chosen and
+ * scheduling.  The device runs the parallel form of sequential greedy (rounds
+ * of separate launches over a CSR of each site's better-ranked neighbours;
+ * DESIGN.md 4.8) and copies back O(n_sites) numbers; no row leaves the device.
+ *
+ * The edges come from the row path: the chunk sequence runs in wld_run_host's
+ * batches, the rows' site columns staying on the device as loaded indices.
+ * Afterwards the context holds no rows (wld_rows_* return WLD_E_STATE until
+ * the next run, whose rows carry parent indices again) and wld_last_stats
+ * describes the last batch's row run.
+ *
+ * WLD_E_STATE: before a load, while a run is in flight, on a device group.
+ * WLD_E_ARG: a NaN priority; more than 2^31 - 1 edges (raise the threshold or
+ * narrow the window).  WLD_E_OOM: the edge buffers (12 bytes per edge) cannot
+ * be allocated; the context stays usable.  No progress callback.  Release
+ * keep/tag with wld_prune_free. */
+typedef struct {
+    uint64_t n_sites, n_kept, edges;   /* edges = rows at this threshold and window */
+    uint32_t rounds;                   /* decide launches enqueued; 0 iff edges == 0; not reproducible */
+    uint8_t  *keep;                    /* n_sites */
+    uint32_t *tag;                     /* n_sites, loaded indices */
+    double pair_ms, prune_ms;          /* HIP-event time: the row passes; CSR build + rounds + tags */
+} wld_prune;
+int  wld_run_prune(wld_ctx *ctx, float r2_threshold, const float *priority, wld_prune *out);
+/* The loaded set's site count — the length of priority, keep and tag (0 before
+ * a load; a device group: its members'). */
+size_t wld_loaded_sites(const wld_ctx *ctx);
+void wld_prune_free(wld_prune *p);
+/* The last wld_run_prune's prune_ms by phase (HIP-event time; 0 when it had no
+ * edge): the CSR build, the rounds (with the host's reads of the undecided
+ * count between them), the tags.  Any pointer may be NULL. */
+int wld_prune_times(wld_ctx *ctx, double *csr_ms, double *rounds_ms, double *tags_ms);
 
 #ifdef __cplusplus
 }

@@ -89,6 +89,19 @@ class Summary(ctypes.Structure):
     ]
 
 
+class Prune(ctypes.Structure):
+    _fields_ = [
+        ("n_sites", ctypes.c_uint64),
+        ("n_kept", ctypes.c_uint64),
+        ("edges", ctypes.c_uint64),
+        ("rounds", ctypes.c_uint32),
+        ("keep", ctypes.POINTER(ctypes.c_uint8)),
+        ("tag", ctypes.POINTER(ctypes.c_uint32)),
+        ("pair_ms", ctypes.c_double),
+        ("prune_ms", ctypes.c_double),
+    ]
+
+
 PROGRESS_FN = ctypes.CFUNCTYPE(None, ctypes.c_uint64, ctypes.c_void_p)
 
 # name -> (restype, argtypes); every symbol include/weightedld.h declares.
@@ -164,6 +177,11 @@ SIGNATURES = {
     "wld_run_summary": (_int, [_vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint32,
                                ctypes.POINTER(Summary)]),
     "wld_summary_free": (None, [ctypes.POINTER(Summary)]),
+    "wld_run_prune": (_int, [_vp, ctypes.c_float, _f32p, ctypes.POINTER(Prune)]),
+    "wld_prune_free": (None, [ctypes.POINTER(Prune)]),
+    "wld_loaded_sites": (_sz, [_vp]),
+    "wld_prune_times": (_int, [_vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+                               ctypes.POINTER(ctypes.c_double)]),
 }
 
 _lib = None

@@ -13,13 +13,13 @@ from collections import namedtuple
 
 import numpy as np
 
-from ._lib import (KERNEL_AUTO, KERNEL_MFMA, KERNEL_VALU, OPTIONS, PROGRESS_FN, Pairs, RunStats, Summary, WldError,
+from ._lib import (KERNEL_AUTO, KERNEL_MFMA, KERNEL_VALU, OPTIONS, PROGRESS_FN, Pairs, Prune, RunStats, Summary, WldError,
                    check, lib)
 
 __all__ = [
     "Symbol", "SymbolHistogram", "SiteSet", "LdStats", "PairStore", "read_fasta", "read_vcf",
     "is_site_of_interest", "henikoff_weights", "single_weighted_ld_pair", "all_weighted_ld_pairs",
-    "ld_summary", "LdSummary", "Context", "default_context", "KERNEL_AUTO", "KERNEL_VALU", "KERNEL_MFMA", "OPTIONS", "WldError",
+    "ld_summary", "LdSummary", "ld_prune", "LdPrune", "maf_priority", "Context", "default_context", "KERNEL_AUTO", "KERNEL_VALU", "KERNEL_MFMA", "OPTIONS", "WldError",
 ]
 
 
@@ -217,6 +217,36 @@ class LdSummary:
             return None
         with np.errstate(invalid="ignore", divide="ignore"):
             return np.where(self.bin_pairs > 0, self.bin_r2_sum / self.bin_pairs, np.nan)
+
+
+class LdPrune:
+    """wld_prune as numpy arrays and ints (Context.run_prune, ld_prune): keep
+    (bool per LOADED site), tag (uint32, loaded indices: a kept site's own
+    index, else its kept neighbour of the smallest rank), n_kept, edges (the
+    rows at the threshold and window), rounds, pair_ms and prune_ms.  From
+    ld_prune also kept_sites: the parent indices of the kept sites."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def maf_priority(site_set):
+    """The "maf" priority of ld_prune: per site minor / (major + minor) of
+    the counts of its major and minor symbols (wld_major_minor on the site's
+    histogram), in double, cast to float32; 0 for a site without both."""
+    buf = site_set.buffer
+    L = buf.shape[0]
+    hist = np.stack([(buf == s).sum(axis=1) for s in range(6)], axis=1).astype(np.uint64) if L else \
+        np.zeros((0, 6), dtype=np.uint64)
+    out = np.zeros(L, dtype=np.float32)
+    a, b = ctypes.c_int(), ctypes.c_int()
+    for i in range(L):
+        h = np.ascontiguousarray(hist[i])
+        check(lib().wld_major_minor(_p(h, ctypes.c_uint64), ctypes.byref(a), ctypes.byref(b)), "major_minor")
+        if a.value >= 0 and b.value >= 0:
+            major, minor = float(h[a.value]), float(h[b.value])
+            out[i] = np.float32(minor / (major + minor))
+    return out
 
 
 # Live contexts, closed (newest first) by an exit handler while the HIP
@@ -443,6 +473,39 @@ class Context:
         lib().wld_summary_free(ctypes.byref(out))
         return res
 
+    def run_prune(self, r2_threshold, priority=None):
+        """wld_run_prune: the greedy r2-independent set of the loaded sites at
+        this threshold under the context's window, as an LdPrune (keep, tag in
+        LOADED indices).  priority: None (index order) or one float per loaded
+        site, larger first, ties to the lower index; NaN is refused."""
+        pr = None
+        if priority is not None:
+            pr = np.ascontiguousarray(priority, dtype=np.float32)
+            if pr.ndim != 1:
+                raise ValueError("priority must be one float per loaded site")
+            n = int(lib().wld_loaded_sites(self._h))
+            if n and pr.size != n:  # (not loaded: the library refuses the call)
+                raise ValueError("priority has %d entries for %d loaded sites" % (pr.size, n))
+        out = Prune()
+        check(lib().wld_run_prune(self._h, r2_threshold, None if pr is None else _p(pr, ctypes.c_float),
+                                  ctypes.byref(out)), "wld_run_prune")
+        L = int(out.n_sites)
+
+        def grab(p, dt):
+            return np.ctypeslib.as_array(p, shape=(L,)).astype(dt, copy=True) if L else np.zeros(0, dtype=dt)
+
+        res = LdPrune(keep=grab(out.keep, np.uint8).astype(bool), tag=grab(out.tag, np.uint32), n_kept=int(out.n_kept),
+                      edges=int(out.edges), rounds=int(out.rounds), pair_ms=float(out.pair_ms),
+                      prune_ms=float(out.prune_ms))
+        lib().wld_prune_free(ctypes.byref(out))
+        return res
+
+    def prune_times(self):
+        """wld_prune_times: the last run_prune's prune_ms by phase, (csr_ms, rounds_ms, tags_ms)."""
+        t = [ctypes.c_double() for _ in range(3)]
+        check(lib().wld_prune_times(self._h, *[ctypes.byref(x) for x in t]), "wld_prune_times")
+        return tuple(float(x.value) for x in t)
+
     def stream_ptr(self):
         """The context's hipStream_t as an int (torch.cuda.ExternalStream)."""
         return int(lib().wld_stream(self._h) or 0)
@@ -601,6 +664,36 @@ def ld_summary(site_set, weights, bin_width=None, n_bins=None, max_distance=None
         return ctx.run_summary(bin_width or 0, n_bins or 0)
     finally:
         ctx.set_window(*before)
+
+
+def ld_prune(site_set, weights, r2_threshold, priority=None, max_distance=None, max_sites=None, ctx=None):
+    """LD pruning (not in the reference; PLINK --indep-pairwise, bcftools
+    +prune): loads site_set and runs Context.run_prune at r2_threshold under
+    the window max_distance / max_sites (the context's own window is restored
+    afterwards).  priority: None (index order), one float per site (larger
+    first, ties to the lower index), or "maf" (maf_priority).  Returns an
+    LdPrune indexed by the set's own site index, with kept_sites, the parent
+    indices of the kept sites."""
+    ctx = ctx or default_context()
+    w = np.ascontiguousarray(weights, dtype=np.float32)
+    if w.size != site_set.n_seqs():
+        raise ValueError("weights must have n_seqs entries")
+    if isinstance(priority, str):
+        if priority != "maf":
+            raise ValueError("priority must be None, an array or \"maf\"")
+        priority = maf_priority(site_set)
+    before = ctx.window()
+    if max_distance is not None or max_sites is not None:
+        ctx.set_window(max_distance, max_sites)
+    try:
+        sm = site_set.site_map
+        ctx.load(site_set.buffer, w, sm)
+        res = ctx.run_prune(r2_threshold, priority)
+    finally:
+        ctx.set_window(*before)
+    kept = np.flatnonzero(res.keep).astype(np.uint64)
+    res.kept_sites = kept if sm is None else sm[kept]
+    return res
 
 
 def _take_pairs(out):

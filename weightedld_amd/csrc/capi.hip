@@ -25,6 +25,7 @@
 #include "tile_order.hpp"
 #include "window_plan.hpp"
 #include "summary_plan.hpp"
+#include "prune_plan.hpp"
 #include "kernels.hpp"
 
 using namespace wld;
@@ -236,6 +237,14 @@ struct wld_ctx {
     DevBuf sum_buf;
     hipEvent_t ev_sum[2] = {};
 
+    // wld_run_prune: while it runs, the gathers leave loaded indices in
+    // out_a/out_b (no site_map); its four events (created at the first prune:
+    // before the CSR build, after it, after the rounds, after the tags) and
+    // the last prune's three phase times (wld_prune_times)
+    bool prune_run = false;
+    hipEvent_t ev_pr[4] = {};
+    double pr_ms[3] = {0.0, 0.0, 0.0};
+
     ~wld_ctx() {
         for (wld_ctx *m : members) delete m;
         if (!members.empty()) return;
@@ -250,6 +259,8 @@ struct wld_ctx {
         for (auto &e : ev)
             if (e) (void)hipEventDestroy(e);
         for (auto &e : ev_sum)
+            if (e) (void)hipEventDestroy(e);
+        for (auto &e : ev_pr)
             if (e) (void)hipEventDestroy(e);
         if (h_cnt) (void)hipHostFree(h_cnt);
         if (h_plog) (void)hipHostFree(h_plog);
@@ -1415,7 +1426,7 @@ int enqueue_pass(wld_ctx *c) {
         const uint64_t cap = std::min<uint64_t>(c->st_capacity, c->rows + c->rows / 4 + 4096);
         WLD_TRY(ensure_outputs(c, cap));
         launch_gather(o, ptr<uint32_t>(c->chunk_base), r.lin_begin, lin_count, chunk_rows_of(c->L), (uint32_t)c->L, 0,
-                      cn, c->out_a.bytes / 4, c->has_map ? ptr<uint32_t>(c->site_map) : nullptr,
+                      cn, c->out_a.bytes / 4, c->has_map && !c->prune_run ? ptr<uint32_t>(c->site_map) : nullptr,
                       ptr<uint32_t>(c->out_a), ptr<uint32_t>(c->out_b), ptr<float>(c->out_d), ptr<float>(c->out_dp),
                       ptr<float>(c->out_r2), c->stream);
         HIP_TRY(hipGetLastError());
@@ -1651,7 +1662,7 @@ int run_complete(wld_ctx *c, uint64_t *n_rows) {
     if (rows && lin_count && rows > c->gather_cap) {  // not gathered behind the scan
         WLD_TRY(ensure_outputs(c, rows));
         launch_gather(order_args(c), ptr<uint32_t>(c->chunk_base), r.lin_begin, lin_count, n, (uint32_t)c->L, rows,
-                      nullptr, rows, c->has_map ? ptr<uint32_t>(c->site_map) : nullptr, ptr<uint32_t>(c->out_a),
+                      nullptr, rows, c->has_map && !c->prune_run ? ptr<uint32_t>(c->site_map) : nullptr, ptr<uint32_t>(c->out_a),
                       ptr<uint32_t>(c->out_b), ptr<float>(c->out_d), ptr<float>(c->out_dp), ptr<float>(c->out_r2),
                       c->stream);
         HIP_TRY(hipGetLastError());
@@ -2232,6 +2243,214 @@ void wld_summary_free(wld_summary *s) {
     free(s->bin_pairs);
     free(s->bin_r2_sum);
     memset(s, 0, sizeof(*s));
+}
+
+namespace {
+// The device buffers of one wld_run_prune call, released when it returns on
+// every path: after WLD_E_OOM the context holds nothing of the call.
+struct PruneBufs {
+    DevBuf ea, eb, rank, off, cur, hp, state, words, keep, tag;
+    ~PruneBufs() {
+        for (DevBuf *b : {&ea, &eb, &rank, &off, &cur, &hp, &state, &words, &keep, &tag}) release(*b);
+    }
+};
+
+// Room for `need` edges in ea/eb, the first `have` kept (device to device).
+int grow_edges(wld_ctx *c, PruneBufs &pb, uint64_t &cap, uint64_t have, uint64_t need) {
+    if (need <= cap) return WLD_OK;
+    const uint64_t k = std::min<uint64_t>(std::max<uint64_t>(need, 2 * cap), prune_plan::kMaxEdges);
+    for (DevBuf *b : {&pb.ea, &pb.eb}) {
+        DevBuf nb;
+        WLD_TRY(ensure(nb, k * 4));
+        hipError_t e = hipSuccess;
+        if (have) e = hipMemcpyAsync(nb.p, b->p, have * 4, hipMemcpyDeviceToDevice, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) {
+            release(nb);
+            return fail(WLD_E_HIP, "wld_run_prune: edge buffer copy: %s", hipGetErrorString(e));
+        }
+        release(*b);
+        *b = nb;
+    }
+    cap = k;
+    return WLD_OK;
+}
+
+// launches per read of the undecided count (wld_run_prune's host loop)
+constexpr uint32_t kPruneRoundsPerRead = 8;
+}  // namespace
+
+int wld_run_prune(wld_ctx *c, float r2_threshold, const float *priority, wld_prune *out) {
+    if (!out) return fail(WLD_E_ARG, "null out");
+    memset(out, 0, sizeof(*out));
+    WLD_TRY(set_dev(c));
+    if (!c->loaded) return fail(WLD_E_STATE, "wld_run_prune before wld_load");
+    if (c->pend.active) return fail(WLD_E_STATE, "wld_run_prune during a run");
+    const size_t L = c->L;
+    if (priority) {
+        const size_t i = prune_plan::first_nan(priority, L);
+        if (i < L) return fail(WLD_E_ARG, "wld_run_prune: priority[%zu] is NaN", i);
+    }
+    const std::vector<uint32_t> rank = prune_plan::rank_of(priority, L);
+
+    // The edges: the rows of the chunk sequence at this threshold and window,
+    // in run_host_range's batches, their (a, b) gathered as loaded indices and
+    // appended device to device.  Whatever happens, the row path is handed
+    // back without rows (wld_rows_* must not give out loaded indices) and with
+    // no gather queued behind its next scan.
+    PruneBufs pb;
+    uint64_t cap = 0, m = 0;
+    double pair_ms = 0.0;
+    struct Restore {
+        wld_ctx *c;
+        ~Restore() {
+            c->prune_run = false;
+            c->have_rows = false;
+            c->spec_gather = false;
+        }
+    } restore{c};
+    c->prune_run = true;
+    const uint64_t limit = std::max<uint64_t>(1, c->opt_host_batch_pairs);
+    const uint32_t le = chunks_of(L);
+    for (uint32_t b = 0; b < le;) {
+        uint32_t e = b;
+        uint64_t pairs = 0;
+        while (e < le) {
+            const uint64_t p1 = run_pairs(c, e, e + 1);  // (in-window pairs under a window)
+            if (e > b && pairs + p1 > limit) break;
+            pairs += p1;
+            ++e;
+        }
+        uint64_t rows = 0;
+        WLD_TRY(run_chunks(c, r2_threshold, b, e, &rows));
+        materialize_times(c);
+        pair_ms += std::max(0.0, c->stats.pair_kernel_ms) + std::max(0.0, c->stats.order_ms);
+        if (m + rows > prune_plan::kMaxEdges)
+            return fail(WLD_E_ARG, "wld_run_prune: more than %llu edges (rows with r2 > %g in the window): raise the "
+                                   "threshold or narrow the window",
+                        (unsigned long long)prune_plan::kMaxEdges, (double)r2_threshold);
+        if (rows) {
+            WLD_TRY(grow_edges(c, pb, cap, m, m + rows));
+            HIP_TRY(hipMemcpyAsync(ptr<uint32_t>(pb.ea) + m, c->out_a.p, rows * 4, hipMemcpyDeviceToDevice, c->stream));
+            HIP_TRY(hipMemcpyAsync(ptr<uint32_t>(pb.eb) + m, c->out_b.p, rows * 4, hipMemcpyDeviceToDevice, c->stream));
+        }
+        m += rows;
+        b = e;
+    }
+    c->pr_ms[0] = c->pr_ms[1] = c->pr_ms[2] = 0.0;
+    out->keep = (uint8_t *)malloc(std::max<size_t>(L, 1));
+    out->tag = (uint32_t *)malloc(std::max<size_t>(L, 1) * sizeof(uint32_t));
+    if (!out->keep || !out->tag) {
+        wld_prune_free(out);
+        return fail(WLD_E_OOM, "host allocation of the pruned set (%zu sites) failed", L);
+    }
+    out->n_sites = L;
+    out->edges = m;
+    out->pair_ms = pair_ms;
+    if (m == 0) {  // no edge: every site is kept, no launch
+        for (size_t i = 0; i < L; ++i) {
+            out->keep[i] = 1;
+            out->tag[i] = (uint32_t)i;
+        }
+        out->n_kept = L;
+        return WLD_OK;
+    }
+
+    // CSR, rounds, tags.  words: {guard, n_kept, the undecided counts of a
+    // group of launches}
+    const uint32_t R = kPruneRoundsPerRead;
+    unsigned h_words[2 + kPruneRoundsPerRead];
+    int st = WLD_OK;
+    auto run = [&]() -> int {
+        WLD_TRY(ensure(pb.rank, L * 4));
+        WLD_TRY(ensure(pb.off, (L + 1) * 4));
+        WLD_TRY(ensure(pb.cur, L * 4));
+        WLD_TRY(ensure(pb.hp, m * 4));
+        WLD_TRY(ensure(pb.state, L * 4));
+        WLD_TRY(ensure(pb.words, sizeof h_words));
+        WLD_TRY(ensure(pb.keep, L));
+        WLD_TRY(ensure(pb.tag, L * 4));
+        for (auto &e : c->ev_pr)
+            if (!e) HIP_TRY(hipEventCreate(&e));
+        unsigned *words = ptr<unsigned>(pb.words);
+        const PruneArgs p{ptr<uint32_t>(pb.ea), ptr<uint32_t>(pb.eb), (uint32_t)m, (uint32_t)L, ptr<uint32_t>(pb.rank),
+                          ptr<uint32_t>(pb.off), ptr<uint32_t>(pb.cur), ptr<uint32_t>(pb.hp), ptr<uint32_t>(pb.state),
+                          words, words + 1, ptr<uint8_t>(pb.keep), ptr<uint32_t>(pb.tag)};
+        HIP_TRY(hipMemcpyAsync(pb.rank.p, rank.data(), L * 4, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemsetAsync(pb.off.p, 0, (L + 1) * 4, c->stream));
+        HIP_TRY(hipMemsetAsync(pb.state.p, 0, L * 4, c->stream));  // (kUndecided)
+        HIP_TRY(hipMemsetAsync(pb.words.p, 0, sizeof h_words, c->stream));
+        HIP_TRY(hipEventRecord(c->ev_pr[0], c->stream));
+        launch_prune_csr(p, c->stream);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(c->ev_pr[1], c->stream));
+        // Rounds: R launches, then one read of the last one's undecided count
+        // (a launch that finds its predecessor's at 0 returns at once).  Every
+        // launch decides at least the best-ranked undecided vertex, so L
+        // launches always suffice.
+        uint32_t rounds = 0;
+        for (;;) {
+            if (rounds) HIP_TRY(hipMemsetAsync(words + 2, 0, R * sizeof(unsigned), c->stream));
+            for (uint32_t k = 0; k < R; ++k) launch_prune_decide(p, k ? words + 2 + k - 1 : nullptr, words + 2 + k, c->stream);
+            rounds += R;
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(h_words, words, sizeof h_words, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            if (h_words[0]) break;  // (reported below)
+            if (h_words[2 + R - 1] == 0) break;
+            if ((uint64_t)rounds >= (uint64_t)L + R)
+                return fail(WLD_E_HIP, "internal: %u vertices undecided after %u rounds on %zu sites",
+                            h_words[2 + R - 1], rounds, L);
+        }
+        HIP_TRY(hipEventRecord(c->ev_pr[2], c->stream));
+        if (!h_words[0]) {
+            launch_prune_tags(p, c->stream);
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipEventRecord(c->ev_pr[3], c->stream));
+        HIP_TRY(hipMemcpyAsync(out->keep, pb.keep.p, L, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(out->tag, pb.tag.p, L * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(h_words, words, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (h_words[0])
+            return fail(WLD_E_STATE, "internal: the prune kernels refused an out-of-range index (guard 0x%x: %s%s%s%s)",
+                        h_words[0], h_words[0] & kPruneGuardEdge ? "edge endpoint " : "",
+                        h_words[0] & kPruneGuardFill ? "list cursor " : "", h_words[0] & kPruneGuardList ? "list entry " : "",
+                        h_words[0] & kPruneGuardTag ? "tag" : "");
+        out->rounds = rounds;
+        out->n_kept = h_words[1];
+        for (int k = 0; k < 3; ++k) c->pr_ms[k] = event_ms(c->ev_pr[k], c->ev_pr[k + 1]);
+        out->prune_ms = event_ms(c->ev_pr[0], c->ev_pr[3]);
+        return WLD_OK;
+    };
+    st = run();
+    if (st != WLD_OK) {
+        (void)hipStreamSynchronize(c->stream);  // nothing of the call is in flight when its buffers go
+        wld_prune_free(out);
+    }
+    return st;
+}
+
+void wld_prune_free(wld_prune *p) {
+    if (!p) return;
+    free(p->keep);
+    free(p->tag);
+    memset(p, 0, sizeof(*p));
+}
+
+size_t wld_loaded_sites(const wld_ctx *c) {
+    if (!c) return 0;
+    const wld_ctx *m = c->members.empty() ? c : c->members[0];
+    return m->loaded ? m->L : 0;
+}
+
+int wld_prune_times(wld_ctx *c, double *csr_ms, double *rounds_ms, double *tags_ms) {
+    if (!c) return fail(WLD_E_ARG, "null context");
+    if (!c->members.empty()) return fail(WLD_E_STATE, "wld_prune_times needs a single-device context");
+    if (csr_ms) *csr_ms = c->pr_ms[0];
+    if (rounds_ms) *rounds_ms = c->pr_ms[1];
+    if (tags_ms) *tags_ms = c->pr_ms[2];
+    return WLD_OK;
 }
 
 int wld_all_weighted_ld_pairs(wld_ctx *c, const uint8_t *sites, size_t n_sites, size_t n_seqs,

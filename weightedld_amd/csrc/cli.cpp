@@ -21,6 +21,12 @@
 //   --decay-bins B           64; the last also takes every longer distance); one
 //                      device summary pass over every in-window pair serves
 //                      both files (wld_run_summary; no threshold applies)
+//   --prune-output FILE      LD pruning TSV (site, kept, tag): the greedy set of
+//   --prune-r2 T             sites no two of which have r2 > T (in the window),
+//   --prune-priority P       visited by P = index (default) or maf (the larger
+//                      minor-allele fraction first, ties to the lower index);
+//                      tag: the kept site standing for a removed one
+//                      (wld_run_prune; parent indices as in the pair TSV)
 #include <chrono>
 #include <cinttypes>
 #include <cmath>
@@ -202,6 +208,9 @@ struct Opt {
     uint64_t max_distance = 0, max_sites = 0;  // --max-distance / --max-sites: wld_set_window (0: no limit)
     std::string ld_score_output, decay_output;  // --ld-score-output / --decay-output: wld_run_summary
     uint64_t decay_bin_width = 0, decay_bins = 64;
+    std::string prune_output;  // --prune-output / --prune-r2 / --prune-priority: wld_run_prune
+    bool have_prune_r2 = false, prune_maf = false;
+    float prune_r2 = 0.0f;
 };
 
 void usage(FILE *f) {
@@ -246,7 +255,13 @@ void usage(FILE *f) {
             "                                             (bin_start, pairs, r2_sum, mean_r2); needs --decay-bin-width\n"
             "        --decay-bin-width <decay-bin-width>  (addition) width of a distance bin, in parent coordinates\n"
             "        --decay-bins <decay-bins>            (addition) number of bins, at most 1024; the last one also\n"
-            "                                             takes every longer distance [default: 64]\n");
+            "                                             takes every longer distance [default: 64]\n"
+            "        --prune-output <prune-output>        (addition) Filename to write the LD-pruned site set to (site,\n"
+            "                                             kept, tag: the kept site that stands for a removed one);\n"
+            "                                             needs --prune-r2; obeys --max-distance and --max-sites\n"
+            "        --prune-r2 <prune-r2>                (addition) no two kept sites have r2 above this\n"
+            "        --prune-priority <prune-priority>    (addition) index | maf: the order in which sites are kept\n"
+            "                                             [default: index]\n");
 }
 
 [[noreturn]] void arg_error(const char *msg, const char *arg) {
@@ -347,6 +362,15 @@ Opt parse(int argc, char **argv) {
             if (v.empty() || v.find_first_not_of("0123456789") != std::string::npos || v.size() > 19)
                 arg_error(("Invalid value for '" + name + "':").c_str(), v.c_str());
             (name == "--decay-bin-width" ? o.decay_bin_width : o.decay_bins) = strtoull(v.c_str(), nullptr, 10);
+        } else if (a == "--prune-output") {
+            o.prune_output = need("--prune-output");
+        } else if (a == "--prune-r2") {
+            o.prune_r2 = parse_f32(need("--prune-r2").c_str(), "prune-r2");
+            o.have_prune_r2 = true;
+        } else if (a == "--prune-priority") {
+            const std::string k = need("--prune-priority");
+            if (k != "index" && k != "maf") arg_error("Invalid value for '--prune-priority':", k.c_str());
+            o.prune_maf = k == "maf";
         } else if (a == "--kernel") {
             std::string k = need("--kernel");
             o.kernel = k == "valu" ? WLD_KERNEL_VALU : k == "mfma" ? WLD_KERNEL_MFMA : WLD_KERNEL_AUTO;
@@ -364,6 +388,12 @@ Opt parse(int argc, char **argv) {
         arg_error("The argument '--decay-bin-width' needs", "--decay-output <decay-output>");
     if (!o.decay_output.empty() && (o.decay_bins < 1 || o.decay_bins > 1024))
         arg_error("Invalid value for '--decay-bins' (1 to 1024):", std::to_string(o.decay_bins).c_str());
+    if (!o.prune_output.empty() && !o.have_prune_r2)
+        arg_error("The following required arguments were not provided:", "--prune-r2 <prune-r2>");
+    if (o.prune_output.empty() && o.have_prune_r2)
+        arg_error("The argument '--prune-r2' needs", "--prune-output <prune-output>");
+    if (!o.prune_output.empty() && o.devices.size() > 1)
+        arg_error("The argument '--prune-output' cannot be used with", "--devices (pruning runs on one device)");
     if (o.gpu_prepass && o.devices.size() > 1)
         arg_error("The argument '--gpu-prepass' cannot be used with", "--devices (the device pre-pass runs on one device)");
     return o;
@@ -547,6 +577,52 @@ void write_summaries(const Opt &opt, wld_ctx *ctx, const std::vector<uint64_t> &
     wld_summary_free(&s);
 }
 
+// The "maf" priority of a site from its histogram: minor / (major + minor) of
+// the counts of wld_major_minor's symbols, in double, as a float; 0 for a site
+// without both.
+float maf_priority(const wld_siteset *s, size_t site) {
+    uint64_t h[6];
+    int major = WLD_NONE, minor = WLD_NONE;
+    if (wld_siteset_histogram(s, site, h) != WLD_OK || wld_major_minor(h, &major, &minor) != WLD_OK) return 0.0f;
+    if (major < 0 || minor < 0) return 0.0f;
+    return (float)((double)h[minor] / ((double)h[major] + (double)h[minor]));
+}
+
+// --prune-output: the greedy r2-independent site set of the loaded set at
+// --prune-r2 under the window (wld_run_prune), one line per loaded site in
+// loaded order.  parent[i] as in write_summaries; hist_set/hist_index: where
+// loaded site i's histogram is found (--prune-priority maf).
+void write_prune(const Opt &opt, wld_ctx *ctx, const std::vector<uint64_t> &parent, const wld_siteset *hist_set,
+                 const std::vector<size_t> &hist_index) {
+    if (opt.prune_output.empty()) return;
+    using clk = std::chrono::steady_clock;
+    const auto sw = clk::now();
+    std::vector<float> priority;
+    if (opt.prune_maf) {
+        priority.resize(parent.size());
+        for (size_t i = 0; i < parent.size(); ++i) priority[i] = maf_priority(hist_set, hist_index[i]);
+    }
+    wld_prune p;
+    const int st = wld_run_prune(ctx, opt.prune_r2, opt.prune_maf ? priority.data() : nullptr, &p);
+    if (st != WLD_OK) die(st, "run_prune");
+    INFO("Pruned %" PRIu64 " sites to %" PRIu64 " (%s pairs above r2 %g) in %s", p.n_sites, p.n_kept,
+         human((double)p.edges).c_str(), (double)opt.prune_r2, fmt_duration(clk::now() - sw).c_str());
+    INFO("Writing output to %s", debug_path(opt.prune_output).c_str());
+    std::string out = "site\tkept\ttag\n";
+    char line[96];
+    for (uint64_t i = 0; i < p.n_sites; ++i) {
+        snprintf(line, sizeof line, "%" PRIu64 "\t%u\t%" PRIu64 "\n", parent[i], (unsigned)p.keep[i], parent[p.tag[i]]);
+        out += line;
+    }
+    FILE *f = fopen(opt.prune_output.c_str(), "wb");
+    const bool ok = f && fwrite(out.data(), 1, out.size(), f) == out.size();
+    if ((f && fclose(f) != 0) || !ok) {
+        fprintf(stderr, "Error: cannot write %s\n", opt.prune_output.c_str());
+        quit(1);
+    }
+    wld_prune_free(&p);
+}
+
 // (debug level only, so info-level output is the reference's: the LD pass's
 // progress_report calls — progress(0), then one per 256x256 chunk)
 void log_progress(const ProgressBar &pb) {
@@ -616,6 +692,8 @@ int run_gpu_prepass(const Opt &opt, wld_siteset *siteset, wld_ctx *ctx) {
     std::vector<uint64_t> parent(L);
     if (L && (st = wld_site_map_copy(ctx, parent.data())) != WLD_OK) die(st, "site_map_copy");
     write_summaries(opt, ctx, parent);
+    // (a FASTA set has no site_map: a kept site's parent index is its index in the unfiltered set)
+    write_prune(opt, ctx, parent, siteset, std::vector<size_t>(parent.begin(), parent.end()));
     return finish(opt, ctx, pairs, dur, total_pairs);
 }
 
@@ -725,6 +803,9 @@ int main(int argc, char **argv) {
     std::vector<uint64_t> parent(L);
     for (size_t i = 0; i < L; ++i) parent[i] = wld_siteset_parent_site_index(filtered, i);
     write_summaries(opt, ctx, parent);
+    std::vector<size_t> self(L);
+    for (size_t i = 0; i < L; ++i) self[i] = i;
+    write_prune(opt, ctx, parent, filtered, self);
     const int rc = finish(opt, ctx, pairs, dur, total_pairs);
     wld_siteset_free(filtered);
     wld_siteset_free(siteset);

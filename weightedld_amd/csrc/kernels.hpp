@@ -355,6 +355,30 @@ void launch_gather(const OrderArgs &o, const uint32_t *chunk_base, uint32_t lin_
                    uint64_t out_cap, const uint32_t *site_map, uint32_t *out_a, uint32_t *out_b, float *out_d,
                    float *out_dp, float *out_r2, hipStream_t s);
 
+// prune.hip (wld_run_prune): the greedy r2-independent site set of an edge list.
+// ea/eb: m edges in loaded indices; rank: the order (a permutation of 0..L-1);
+// off [L + 1], cur [L], hp [m]: the directed CSR (off zero before
+// launch_prune_csr); state [L]: prune_plan's codes, kUndecided (0) before the
+// first round; guard, n_kept: zero before the first launch.
+struct PruneArgs {
+    const uint32_t *ea, *eb;
+    uint32_t m, L;
+    const uint32_t *rank;
+    uint32_t *off, *cur, *hp, *state;
+    unsigned *guard, *n_kept;
+    uint8_t *keep;
+    uint32_t *tag;
+};
+constexpr unsigned kPruneGuardEdge = 1, kPruneGuardFill = 2, kPruneGuardList = 4, kPruneGuardTag = 8;
+constexpr uint32_t kPruneSweeps = 4;  // sweeps over its vertices per decide launch
+// degrees, scan, fill: hp[off[v] .. off[v + 1]) = the neighbours ranking before v
+void launch_prune_csr(const PruneArgs &p, hipStream_t s);
+// one round; prev: the launch before's undecided count (null: unknown), at 0
+// the launch does nothing; left (zero before): the vertices it leaves undecided
+void launch_prune_decide(const PruneArgs &p, const unsigned *prev, unsigned *left, hipStream_t s);
+// keep[], tag[] and *n_kept from the final states
+void launch_prune_tags(const PruneArgs &p, hipStream_t s);
+
 // Linear index of chunk (row, col) in the reference's triu_index order
 // (lib.rs:623-632): rows descend, so row r starts at (n-1-r)(n-r)/2.
 __host__ __device__ inline uint32_t chunk_linear(uint32_t n, uint32_t row, uint32_t col) {
