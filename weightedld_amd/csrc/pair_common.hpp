@@ -215,6 +215,16 @@ __host__ __device__ __forceinline__ float r2_screen_terms_fg(float F0, float G0,
 // and t1 as in r2_screen_terms_xy / _fg (X0 Y1 - X1 Y0 = 2 num, error <= 2u
 // (X0 Y1 + X1 Y0)(1 + u) <= 4u T^2: 2u T2^2 after doubling).  Skip iff t1 <= 0
 // and mlo >= mloc.
+// The a site's other allele: with X1', Y1' summed over the sequences where a
+// is minor (SA' = T - SA, SA'B = SB - SAB; X1' = X0 - X1, Y1' = Y0 - Y1) the
+// function computes the same test with m1 and m2 exchanged: A2' = 2(T - SA),
+// so m1' = 2(T - SA) - R2 = m2 and m2' = T2r - A2' = 2SA - R2 = m1, both
+// still exact, and the product (m1 m2)(m3 m4) and the minimum are symmetric
+// in them, bit for bit.  The numerator X0 Y1' - X1' Y0 = -(X0 Y1 - X1 Y0)
+// enters by its magnitude, rounded within 2u (X0 Y1' + X1' Y0)(1 + u), which
+// the same 4u T^2 bounds (X1' <= X0, Y1' <= Y0).  So either channel of the a
+// site may be passed (the fp6 screen passes the minor one, the i8 screen the
+// major one); only the numerator's last ulp can differ between the two.
 __host__ __device__ __forceinline__ float r2_screen_terms_xy2(float X0, float Y0, float X1, float Y1, float R2,
                                                               float thr_c, float E, float &mlo) {
     const float X0r = X0 - R2;

@@ -43,6 +43,7 @@
 // Passing rows are compacted per tile in LDS (order.hip assembles the
 // reference order).
 #include <algorithm>
+#include <type_traits>
 #include <vector>
 
 #include "pair_common.hpp"
@@ -838,41 +839,46 @@ __global__ __launch_bounds__(64 * GroupShape<NPL>::kWaves, GroupShape<NPL>::kWgP
 
 // ---- fp6 screen (block-scaled MFMA, twice the i8 rate) ----------------------
 //
-// The one-plane screen's sums from v_mfma_scale_f32_16x16x128_f8f6f4 with fp6
-// (e2m3) operands on both sides, unit block scales: 128 sequences per
+// The one-plane screen's sums from v_mfma_f32_16x16x128_f8f6f4 with fp6 (e2m3)
+// A operands and fp4 (e2m1) B operands, no block scales: 128 sequences per
 // instruction at the cycles of the i8 kernel's 64.  Every weight is rounded
 // to its nearest e2m3 value at a common scale S (w6_k = fp6(S w_k), a multiple
-// of 1/8 in [0, 7.5]); A = w6 where the a site's symbol is major or minor
-// ("in", lib.rs:435) or major (lib.rs:430-432), two channels.  B holds one
-// 6-bit code per b symbol, 0 (neither), 8 (major) or 16 (minor), and each B
-// register is multiplied twice: read as e2m3 (blgp 2) the codes are 0 / 1.0 /
-// 2.0, read as e3m2 (blgp 3) 0 / 0.5 / 2.0 (tools/probes/fp6_dual_probe.hip)
-// — two independent channels from the same bytes, with no mask instruction.
-// Per pair the four accumulators (channel_a in / major x reading F / G) are
-//   F0 = 2T - SB, G0 = 2T - 1.5 SB, F1 = 2SA - SAB, G1 = 2SA - 1.5 SAB
-// (T, SA, SB, SAB: lib.rs:441-444's sums of the rounded weights).  Products
-// are exact and every sum is a multiple of 1/16 below 2^19, so the f32 MFMA
-// sums are exact, and so is every marginal the per-pair test forms from them
-// (r2_screen_terms_fg; R is put on the same grid): the screen's f32 bound
-// holds with R = sum_k |S w_k - w6_k| plus the reference's rounding, in the
-// same units (capi.hip fp6_prepare).  Operands come pre-packed from memory,
-// per 64-site tile and 128-sequence block kb one contiguous stage image:
-//   a6 [tile][kb][16-site block][channel in, major][1536 B] (12 KB): lane l =
+// of 1/8 in [0, 7.5]).  A holds two channels per a site and sequence: w6 where
+// the symbol is major or minor ("in", lib.rs:435) and w6 where it is minor.
+// B holds one fp4 nibble per b symbol, minor + 2 major (1.0 / 2.0, 0 neither),
+// and each B register is multiplied twice: raw (X) and masked to its minor
+// bit (Y, raw & 0x2222...).  Per pair the four accumulators (channel_a in /
+// minor x X / Y) are, with T, SB and the minor-a sums SA', SA'B (lib.rs:441-444's
+// sums of the rounded weights, SA' = T - SA, SA'B = SB - SAB),
+//   X0 = T + SB, Y0 = T - SB, X1 = SA' + SA'B, Y1 = SA' - SA'B.
+// The per-pair test (r2_screen_terms_xy2) is symmetric in the a site's two
+// alleles, so it takes the minor-a sums where it was derived for the major-a
+// ones (pair_common.hpp).  The minor channel is there for the clock, not the
+// count: the kernel runs power-limited (2.02 GHz on random data, 2.38 GHz on
+// all-zero images of the same shape, 20% less time: DESIGN.md Appendix A), and
+// an A image that is 0.60 instead of 0.75 nonzero costs less per MFMA (C4
+// -1.4%; a (major, minor) image, 0.45 nonzero but two more adds per pair and
+// two high-entropy channels, lost 1.2%).  Products are exact and every sum is
+// a multiple of 1/8 below 2^19, so the f32 MFMA sums are exact, and so is
+// every marginal the per-pair test forms from them (R is put on the same
+// grid): the screen's f32 bound holds with R = sum_k |S w_k - w6_k| plus the
+// reference's rounding, in the same units (capi.hip fp6_prepare).  Operands
+// come pre-packed from memory, per 64-site tile and 128-sequence block kb one
+// contiguous stage image:
+//   a6 [tile][kb][16-site block][channel in, minor][1536 B] (12 KB): lane l =
 //      site l & 15 of the block, sequences 32 (l >> 4) + j at bits 6j of six
 //      dwords, dwords 0-3 at 16 l, dwords 4-5 at 1024 + 8 l (one ds_read_b128
 //      and one ds_read_b64 fill the operand registers in place)
-//   b6 [tile][kb][16-site block][1536 B]: the b codes, same packing (6 KB)
-// One 64x64 tile per 4-wave workgroup, four per CU; per 128 sequences the
-// waves LDS-DMA the row tile's A image and the column tile's B image (18 1-KB
-// pieces) into a double-buffered 18 KB stage; wave w computes a rows 16w..
-// against the four column blocks (16 MFMAs per stage), then the screen
-// epilogue.
-// B operand: the b codes as fp4 (e2m1) nibbles of minor + 2 major (1.0 /
-// 2.0; 16 B per lane and block), the minor channel by one mask per dword (raw
-// & 0x2222...), accumulators X / Y (r2_screen_terms_xy2).  (Round 5 measured
-// the alternatives and removed them: 6-bit codes read twice as e2m3 / e3m2,
-// slower per MFMA and 1.5x the B bytes; a minor-bit plane copied into LDS
-// beside B, a larger stage; DESIGN.md Appendix A.)
+//   b6 [tile][kb][16-site block][1024 B]: the b codes' nibbles, sequences
+//      32 (l >> 4) + j at bits 4j of four dwords at 16 l (4 KB)
+// Single tiles (pair_fp6_screen_kernel): one 64x64 tile per 4-wave workgroup,
+// four per CU; per 128 sequences the waves LDS-DMA the row tile's A image and
+// the column tile's B image (16 1-KB pieces) into a double-buffered 16 KB
+// stage; wave w computes a rows 16w.. against the four column blocks (16
+// MFMAs per stage), then the screen epilogue.  Tile pairs: below.
+// (Round 5 measured the alternatives to fp4 B and removed them: 6-bit codes
+// read twice as e2m3 / e3m2, slower per MFMA and 1.5x the B bytes; a minor-bit
+// plane copied into LDS beside B, a larger stage; DESIGN.md Appendix A.)
 constexpr int kF6ABytes = 3072;                         // per 16-site block: A, two channels
 constexpr int kF6BBytes = 1024;                         // ... and B (fp4 codes)
 constexpr int kF6AStage = 4 * kF6ABytes;                // a tile's A image per 128 sequences
@@ -899,8 +905,12 @@ __global__ __launch_bounds__(256) void frag6_kernel(const uint8_t *__restrict__ 
     uint32_t ai[6] = {0, 0, 0, 0, 0, 0}, am[6] = {0, 0, 0, 0, 0, 0}, b[4] = {0, 0, 0, 0};
     for (uint32_t j = 0; j < 32; ++j) {
         const uint32_t k = k0 + j;
+#ifdef WLD_EXP_ZERO_IMG  // diagnostic: all-zero operand images, the same instruction stream
+        const uint32_t c = 0u, v = 0u;
+#else
         const uint32_t c = k < NP ? row[k] : 0u, v = k < NP ? w6[k] : 0u;
-        const uint32_t vi = (c & kCodeIn) ? v : 0u, vm = (c & kCodeMaj) ? v : 0u;
+#endif
+        const uint32_t vi = (c & kCodeIn) ? v : 0u, vm = (c & (kCodeIn | kCodeMaj)) == kCodeIn ? v : 0u;
         const uint32_t bit = 6 * j, d = bit >> 5, o = bit & 31;
         ai[d] |= vi << o;
         am[d] |= vm << o;
@@ -935,7 +945,7 @@ __device__ __forceinline__ v8i f6_ldb(const uint8_t *p, uint32_t lane) {
     const uint4 x = *reinterpret_cast<const uint4 *>(p + 16 * lane);
     return v8i{(int)x.x, (int)x.y, (int)x.z, (int)x.w, 0, 0, 0, 0};
 }
-// one B block's four MFMAs against the wave's A channels (in: ai, major: am):
+// one B block's four MFMAs against the wave's A channels (in: ai, minor: am):
 // acc[channel_a][0 / 1] = X / Y (B raw: minor + 2 major, B's minor bit)
 // Zero scale operands: the compiler selects the unscaled
 // v_mfma_f32_16x16x128_f8f6f4 (no per-block scales), whose sums equal the
@@ -1056,7 +1066,7 @@ __global__ __launch_bounds__(256, 4) void pair_fp6_screen_kernel(const uint8_t *
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     const uint64_t okA = ok_bits[ta], okB = ok_bits[tb];
-    v4f acc[4][2][2];  // [b block n][channel_a in / major][X, Y / F, G]
+    v4f acc[4][2][2];  // [b block n][channel_a in / minor][X, Y]
 #pragma unroll
     for (int n = 0; n < 4; ++n)
 #pragma unroll
@@ -1126,6 +1136,15 @@ constexpr uint32_t kF6Single = 0x8000u;  // (= tile_order::kSingleEntry)
 // on six waves, two workgroups per CU (+43%), and the full-tile bound on
 // packed f32 (+1%) (round 6); DESIGN.md Appendix A.)
 constexpr int kF6PStage = kF6AStage + 2 * kF6BStage;
+#ifdef WLD_EXP_CLOCK
+// diagnostic build: per workgroup (slot blockIdx.x % kF6ClockSlots) wave 0's
+// shader-clock and 100-MHz real-time counts around the stage loop
+constexpr uint32_t kF6ClockSlots = 8192;
+__device__ unsigned long long gF6Clock[2 * kF6ClockSlots];
+extern "C" int wld_debug_f6_clock(unsigned long long *out) {
+    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(gF6Clock), sizeof(gF6Clock));
+}
+#endif
 __global__ __launch_bounds__(256, 3) void pair_fp6_screen2w_kernel(
     const uint8_t *__restrict__ a6, const uint8_t *__restrict__ b6, const uint64_t *__restrict__ ok_bits,
     const uint32_t *__restrict__ pairs, uint32_t n_pairs, uint32_t NK, uint32_t L, uint32_t n_chunk_rows, float thr,
@@ -1184,28 +1203,25 @@ __global__ __launch_bounds__(256, 3) void pair_fp6_screen2w_kernel(
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         const uint64_t okA = ok_bits[ta], okB = ok_bits[tb];
         v4f acc[2][4][2][2];  // [row block 2 rp + j][b block n][channel_a][X, Y]
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int n = 0; n < 4; ++n)
-#pragma unroll
-                for (int x = 0; x < 2; ++x)
-#pragma unroll
-                    for (int y = 0; y < 2; ++y) acc[j][n][x][y] = v4f{0.0f, 0.0f, 0.0f, 0.0f};
         const uint32_t boff = kF6AStage + (idle ? 0u : half) * kF6BStage;  // this half's B image in a stage
         const uint32_t aoff = 2 * rp * kF6ABytes;                             // this wave's two A row blocks
-        for (uint32_t kb = 0; kb < NK; ++kb) {
+        // One stage.  The first (kFirst) is peeled: its 32 MFMAs take a
+        // constant-zero C, so no accumulator is zeroed beforehand (128 v_mov
+        // per wave and entry; C4 -0.8%, profiles/r07a/), and it holds the
+        // give-up test.  Returns false where the workgroup gives the pass up.
+        auto stage = [&](uint32_t kb, auto first) -> bool {
+            constexpr bool kFirst = decltype(first)::value;
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's copies of the stage landed
             __builtin_amdgcn_s_barrier();                     // ... and every other wave's; the other buffer is free
             asm volatile("" ::: "memory");
-            if (kb == 0) {
+            if (kFirst) {
                 if (sBail) {  // (uniform) give the pass up: drain this wave's copies, leave
                     if (tid == 0 && sBail == 1) {
                         atomicOr(sc.cand_count, kAbandonBit);
                         atomicOr(sc.cand_buckets, kAbandonBit);
                     }
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    return;
+                    return false;
                 }
                 // (every wave has left the previous entry's epilogue)
                 if (tid < 2) sCand[tid] = 0u, sMask[tid] = 0ull;
@@ -1223,34 +1239,51 @@ __global__ __launch_bounds__(256, 3) void pair_fp6_screen2w_kernel(
             // issued after the reads, measured no better: profiles/r06l/)
             const v8i ai0 = f6_ld24(g + aoff, lane), am0 = f6_ld24(g + aoff + 1536, lane);
             const v8i ai1 = f6_ld24(g + aoff + kF6ABytes, lane), am1 = f6_ld24(g + aoff + kF6ABytes + 1536, lane);
+            const v4f kZero = {0.0f, 0.0f, 0.0f, 0.0f};
             v8i bs[2] = {f6_ldb(g + boff, lane), f6_ldb(g + boff + kF6BBytes, lane)};
 #pragma unroll
             for (int n = 0; n < 4; ++n) {
                 v8i &b = bs[n & 1];
                 constexpr int kMinor = 0x22222222;  // fp4 1.0 (minor) nibbles; 2.0 (major) is 0x4
-                acc[0][n][0][0] = f6_mfma(ai0, b, acc[0][n][0][0]);
-                acc[0][n][1][0] = f6_mfma(am0, b, acc[0][n][1][0]);
-                acc[1][n][0][0] = f6_mfma(ai1, b, acc[1][n][0][0]);
-                acc[1][n][1][0] = f6_mfma(am1, b, acc[1][n][1][0]);
+                acc[0][n][0][0] = f6_mfma(ai0, b, kFirst ? kZero : acc[0][n][0][0]);
+                acc[0][n][1][0] = f6_mfma(am0, b, kFirst ? kZero : acc[0][n][1][0]);
+                acc[1][n][0][0] = f6_mfma(ai1, b, kFirst ? kZero : acc[1][n][0][0]);
+                acc[1][n][1][0] = f6_mfma(am1, b, kFirst ? kZero : acc[1][n][1][0]);
                 __builtin_amdgcn_sched_barrier(0);
                 b = v8i{b[0] & kMinor, b[1] & kMinor, b[2] & kMinor, b[3] & kMinor, 0, 0, 0, 0};
-                acc[0][n][0][1] = f6_mfma(ai0, b, acc[0][n][0][1]);
-                acc[0][n][1][1] = f6_mfma(am0, b, acc[0][n][1][1]);
-                acc[1][n][0][1] = f6_mfma(ai1, b, acc[1][n][0][1]);
-                acc[1][n][1][1] = f6_mfma(am1, b, acc[1][n][1][1]);
+                acc[0][n][0][1] = f6_mfma(ai0, b, kFirst ? kZero : acc[0][n][0][1]);
+                acc[0][n][1][1] = f6_mfma(am0, b, kFirst ? kZero : acc[0][n][1][1]);
+                acc[1][n][0][1] = f6_mfma(ai1, b, kFirst ? kZero : acc[1][n][0][1]);
+                acc[1][n][1][1] = f6_mfma(am1, b, kFirst ? kZero : acc[1][n][1][1]);
                 __builtin_amdgcn_sched_barrier(0);
                 if (n + 2 < 4) b = f6_ldb(g + boff + (n + 2) * kF6BBytes, lane);
                 __builtin_amdgcn_sched_barrier(0);
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // reads of this buffer done before the next barrier
             buf ^= 1;
+            return true;
+        };
+#ifdef WLD_EXP_CLOCK
+        const unsigned long long ck0 = clock64(), rt0 = wall_clock64();
+#endif
+        if (!stage(0, std::true_type{})) return;
+        for (uint32_t kb = 1; kb < NK; ++kb) stage(kb, std::false_type{});
+#ifdef WLD_EXP_CLOCK
+        if (tid == 0) {
+            gF6Clock[2 * (blockIdx.x % kF6ClockSlots)] = clock64() - ck0;
+            gF6Clock[2 * (blockIdx.x % kF6ClockSlots) + 1] = wall_clock64() - rt0;
         }
+#endif
         const F6Epi ep0{ta, tb, 2 * rp, lane, okA, okB, 2.0f * sc.Rf, thr * (1.0f - 0x1p-7f), sc.E, sc.mloc};
         const F6Epi ep1{ta, tb, 2 * rp + 1, lane, okA, okB, 2.0f * sc.Rf, thr * (1.0f - 0x1p-7f), sc.E, sc.mloc};
         const bool cand = !idle && (ep0.any(acc[0]) || ep1.any(acc[1]));
         if (cand) sCand[half] = 1u;  // (benign race: every writer stores 1)
         __syncthreads();
+#ifdef WLD_EXP_ZERO_IMG  // (every zero-image tile is a candidate: keep the reject path's work)
+        const bool mine = sCand[half] == 0x5EEDu;
+#else
         const bool mine = sCand[half] != 0;  // (uniform per half)
+#endif
         if (sc.probe) {  // the sample run: count, decide nothing
             if (ltid == 0 && !idle) {
                 if (mine) atomicAdd(sc.probe, 1u);
