@@ -17,7 +17,8 @@ HIP_SRCS := $(CSRC)/encode.hip $(CSRC)/prepass.hip $(CSRC)/pair_valu.hip $(CSRC)
             $(CSRC)/pair_mfma.hip $(CSRC)/prune.hip $(CSRC)/order.hip $(CSRC)/capi.hip
 CXX_SRCS := $(CSRC)/host.cpp
 HDRS := include/weightedld.h $(CSRC)/common.hpp $(CSRC)/kernels.hpp $(CSRC)/pair_common.hpp $(CSRC)/tile_order.hpp \
-        $(CSRC)/window_plan.hpp $(CSRC)/pair_valu_kernel.hpp $(CSRC)/summary_plan.hpp $(CSRC)/prune_plan.hpp
+        $(CSRC)/window_plan.hpp $(CSRC)/pair_valu_kernel.hpp $(CSRC)/summary_plan.hpp $(CSRC)/prune_plan.hpp \
+        $(CSRC)/screen_policy.hpp
 OBJDIR := build/obj
 OBJS := $(patsubst $(CSRC)/%.hip,$(OBJDIR)/%.o,$(HIP_SRCS)) $(patsubst $(CSRC)/%.cpp,$(OBJDIR)/%.o,$(CXX_SRCS))
 

@@ -288,6 +288,41 @@ def test_screen_auto_policy(W, ctxs):
     _same_rows(rows2[1], rows0[1])
 
 
+def test_screen_auto_policy_forgets(W, ctxs):
+    # What the auto policy learned (test_screen_auto_policy: 0.002 screens on
+    # one plane once, then on two) is forgotten by a new window, by the options
+    # that change its break-evens and by a load: the next run at 0.002 starts
+    # on the one-plane screen again (and re-learns, so each action meets a
+    # learned state).  The rows never change.
+    ctx = _ctx(ctxs, "mfma")
+    buf = synth(2000, 2000, 23)
+    w = W.henikoff_weights(W.SiteSet.from_buffer(buf))
+    ctx.load(buf, w)
+    ctx.set_option("screen_fp6", 0)  # the i8 tiers' policy, as in test_screen_auto_policy
+    thr = 0.002
+    n = ctx.run(thr)
+    assert ctx.stats()["screened"] == 1
+    assert ctx.run(thr) == n and ctx.stats()["screened"] == 3
+    ref_sums = ctx.get_option("ref_sums")
+
+    def window():
+        ctx.set_window(0, 1500)
+        ctx.set_window(0, 0)
+
+    def ref_sums_there_and_back():
+        ctx.set_option("ref_sums", 1 - ref_sums)
+        ctx.set_option("ref_sums", ref_sums)
+
+    for action in (window, ref_sums_there_and_back, lambda: ctx.set_option("screen", 1),
+                   lambda: ctx.set_option("screen_fp6", 0), lambda: ctx.load(buf, w)):
+        action()
+        assert ctx.run(thr) == n
+        st = ctx.stats()
+        assert st["screened"] == 1 and st["candidate_tiles"] * 2 > st["tiles"], st
+    compare_rows(ctx.rows(), O.all_pairs(buf, w, np.float32(thr)), np.float32(thr), buf=buf, w=w)
+    ctx.set_option("screen_fp6", 1)
+
+
 def test_two_plane_screen_at_low_threshold(W, ctxs):
     # BASELINE-style random data at thr 0.01 (r2 ~ 1/N, a few pairs per
     # hundred tiles pass): the one-plane screen's residual leaves most tiles

@@ -114,21 +114,9 @@ struct wld_ctx {
     // wld_set_option (include/weightedld.h)
     bool opt_prefilter = true, opt_tile_rows = false, opt_all_planes = false;
     int opt_screen = 1;  // WLD_OPT_SCREEN: 0 never, 1 auto (default), 2 always, 3 two-plane, 4 exact candidate pairs
-    // auto: the largest threshold at which the screen left > half the tiles,
-    // and at which the two-plane screen left > a fifth
-    float screen_bad_thr = -1.0f;
-    // auto: the largest threshold at which the fp6 screen left more than a
-    // sixteenth of the tiles (there and below, the i8 screen's tighter bound)
-    float fp6_bad_thr = -1.0f;
-    // auto: the smallest threshold at which the fp6 screen's sample run found
-    // few enough candidate tiles (there and above no sample run is needed)
-    float fp6_good_thr = INFINITY;
+    screen_policy::Learned learned;  // auto: the thresholds the passes so far have taught (screen_policy.hpp)
+    screen_policy::Plan pass;        // the last row pass's plan (its route as launched)
     DevBuf fp6_probe_buf;  // the sample run's two counts
-    float screen2_bad_thr = -1.0f;
-    // auto, lib.rs's order: the largest threshold at which the exact candidate
-    // pairs were more than a tenth of all pairs (then the full f32 kernel)
-    float ref_pairs_bad_thr = -1.0f;
-    bool ref_pairs_pass = false;  // the pass staged exact candidate pairs (ref_rows_kernel)
     bool opt_site_major = false, opt_valu_plain = false;
     bool opt_fused_scan = true;  // WLD_OPT_FUSED_SCAN: the chunk scan in the candidate launch's last workgroup
     int opt_test_guard = 0;      // WLD_OPT_TEST_GUARD (tests: a bucket count corrupted before the candidate launch)
@@ -161,7 +149,6 @@ struct wld_ctx {
     bool fp6_tried = false;   // fp6_prepare ran for this load
     bool fp6_sampled = false; // this pass's screen was chosen by a sample run (fp6_sample)
     bool fp6_ok = false;      // operands built for this load (the weights allow it)
-    bool fp6_pass = false;    // the last pass screened on fp6
     bool fp6_better = false;  // ... and its residual is within twice the i8 top digit's (auto)
     double fp6_rel = 0.0, i8_rel = 0.0;  // the two screens' residuals relative to their sums
     bool have_ref = false;   // rcodes/rw hold this load's layout
@@ -190,8 +177,6 @@ struct wld_ctx {
     uint32_t tiles_lb = ~0u, tiles_le = ~0u;  // linear chunk range the tile list covers
     uint32_t n_tiles = 0;
     bool have_rows = false;
-    bool screened = false;  // the last pass ran a screen
-    bool screened2 = false; // ... on two digit planes
     uint64_t rows = 0;
     // the gather goes into the stream behind the scan, before the host has
     // seen the row count, when the previous run had rows:
@@ -205,7 +190,6 @@ struct wld_ctx {
     // are asked for (materialize_times; ~3 hipEventElapsedTime calls the N>1
     // step loop, which never reads them, does not pay)
     bool times_pending = false;
-    bool times_screened = false;
     int times_order_end = 4;
     // per-chunk progress (wld_run_host with a callback): the run's chunk
     // countdowns and log slot counter on the device, the log in mapped pinned
@@ -299,7 +283,7 @@ void materialize_times(wld_ctx *c) {
     c->times_pending = false;
     c->stats.pair_kernel_ms = event_ms(c->ev[2], c->ev[3]);
     c->stats.order_ms = event_ms(c->ev[3], c->ev[c->times_order_end]);
-    c->stats.screen_ms = c->times_screened ? event_ms(c->ev[2], c->ev[6]) : 0.0;
+    c->stats.screen_ms = screen_policy::ran_screen(c->pass.route) ? event_ms(c->ev[2], c->ev[6]) : 0.0;
 }
 
 // fixed-point exponent for the MFMA weight planes: max|w| * 2^shift must fit
@@ -431,8 +415,7 @@ int common_load(wld_ctx *c, const uint8_t *d_sites, const float *d_w, const uint
     const size_t L = c->L, N = c->N;
     // a new data set: the auto screen policy (thresholds learned on the last
     // one) starts over; the reference-order layout is rebuilt when needed
-    c->screen_bad_thr = c->screen2_bad_thr = c->ref_pairs_bad_thr = c->fp6_bad_thr = -1.0f;
-    c->fp6_good_thr = INFINITY;
+    c->learned.reset();
     c->have_ref = false;
     c->LP = round_up(std::max<size_t>(L, 1), kChunk);
     c->NP = round_up(std::max<size_t>(N, 1), kSeqPad);
@@ -779,87 +762,89 @@ double ref_extra_residual(const wld_ctx *c) {
     return r * (1.0 + 1e-9) + 1.0;  // slack for this evaluation's own rounding
 }
 
-// Enqueues the pair kernel(s) of a pass; *screened tells whether the MFMA
-// screen ran (then ev[6] separates it from the candidate launch).
+// The policy's view of the context and of a pass at thr (screen_policy.hpp).
+struct PolicyInputs {
+    screen_policy::Options opt;
+    screen_policy::LoadFacts load;
+    screen_policy::PassFacts pass;
+};
+PolicyInputs policy_inputs(const wld_ctx *c, float thr, bool dense) {
+    return {{c->opt_screen, c->opt_fp6, c->opt_ref_sums, c->opt_prefilter, c->opt_i8_pairs},
+            {c->kernel == WLD_KERNEL_MFMA, c->use_frag, c->wst.nonneg != 0, c->NP, c->plane_mask, c->fp6_ok,
+             c->fp6_better},
+            {c->f6_n_pairs != 0, c->n_tiles, thr, dense, c->prog_pass, c->pend.count_out != nullptr}};
+}
+
+// The tile list on the reference-order f32 kernel (lane-class layout: after ensure_ref_layout).
+ValuLaunch ref_valu_launch(wld_ctx *c, float thr) {
+    return ValuLaunch{ptr<uint8_t>(c->rcodes), ptr<float>(c->rw), ptr<uint8_t>(c->site_ok), ptr<uint32_t>(c->tiles),
+                      c->n_tiles, nullptr, (uint32_t)c->L, (uint32_t)c->NPr, chunk_rows_of(c->L), thr, c->safe, false,
+                      true, c->ref_cls, (uint32_t)(c->N % 8)};
+}
+
+// What every MFMA launch of the tile list at thr needs (the pass and the fp6 sample run).
+MfmaLaunch mfma_base(wld_ctx *c, float thr) {
+    MfmaLaunch m{};
+    m.wplanes = ptr<int8_t>(c->planes);
+    m.tiles = ptr<uint32_t>(c->tiles);
+    m.n_tiles = c->n_tiles;
+    m.L = (uint32_t)c->L;
+    m.NP = (uint32_t)c->NP;
+    m.LP = (uint32_t)c->LP;
+    m.n_chunk_rows = chunk_rows_of(c->L);
+    m.thr = thr;
+    m.nonneg = c->wst.nonneg;
+    m.fp6 = &c->f6;
+    m.f6_pairs = c->f6_n_pairs ? ptr<uint32_t>(c->f6_pairs) : nullptr;
+    m.f6_n_pairs = c->f6_n_pairs;
+    return m;
+}
+
+// Enqueues the pair kernel(s) of a pass on the route the screen policy
+// decides; *pass receives the plan as launched (where a screen ran, ev[6]
+// separates it from the candidate launch).
 // With scan given, a screen fuses the run's chunk scan into its last
 // workgroup or the candidate launch's (then the caller launches no scan).
-int launch_pairs(wld_ctx *c, float thr, const OrderArgs &o, const DenseArgs *dense, bool *screened = nullptr,
-                 const ScanArgs *scan = nullptr, bool *scan_fused = nullptr) {
+int launch_pairs(wld_ctx *c, float thr, const OrderArgs &o, const DenseArgs *dense,
+                 screen_policy::Plan *pass = nullptr, const ScanArgs *scan = nullptr, bool *scan_fused = nullptr) {
+    using screen_policy::Route;
     bool fused = false;  // the run's chunk scan ran inside a launch (the caller launches none)
-    const uint32_t n = chunk_rows_of(c->L);
-    bool sc = false;
-    c->fp6_pass = false;
     c->stats.ref_sums = c->opt_ref_sums ? 1 : 0;
-    c->ref_pairs_pass = false;
+    const PolicyInputs in = policy_inputs(c, thr, dense != nullptr);
+    screen_policy::Plan plan = screen_policy::decide(in.opt, in.load, in.pass, c->learned);
     ValuLaunch rv{};
     if (c->opt_ref_sums) {
         WLD_TRY(ensure_ref_layout(c));
-        rv = ValuLaunch{ptr<uint8_t>(c->rcodes), ptr<float>(c->rw), ptr<uint8_t>(c->site_ok), ptr<uint32_t>(c->tiles),
-                        c->n_tiles, nullptr, (uint32_t)c->L, (uint32_t)c->NPr, n, thr, c->safe, false, true,
-                        c->ref_cls, (uint32_t)(c->N % 8)};
+        rv = ref_valu_launch(c, thr);
     }
-    // reference order without a screen in front (no positive threshold, the
-    // f32 kernel, dense stats, or the auto policy's full-kernel thresholds):
-    // every tile on the reference-order f32 kernel
-    const bool ref_screen = c->opt_ref_sums && c->kernel == WLD_KERNEL_MFMA && !dense && c->use_frag &&
-                            c->opt_prefilter && thr > 0.0f && c->opt_screen != 0;
+    // the i8 screen on tile pairs (WLD_OPT_I8_PAIRS): its images built at the
+    // first pass that needs them, and used only while they hold the top
+    // active plane (else single tiles)
+    if (plan.i8_images) {
+        if (!c->i8img_ok) WLD_TRY(i8img_prepare(c));
+        plan.route = screen_policy::settle_i8(plan.route, c->i8s.digit_plane, c->plane_mask);
+    }
     // (a full run on the item kernel fuses the scan into its last workgroup)
     if (scan && !dense) rv.scan = *scan;
-    if (c->opt_ref_sums && !ref_screen) {
+    if (plan.route == Route::F32RefOrder) {
         fused = launch_pair_valu(rv, o, dense, c->stream);
-    } else if (c->kernel == WLD_KERNEL_MFMA) {
-        MfmaLaunch m{};
+    } else if (plan.route == Route::F32Plain) {
+        launch_pair_valu(ValuLaunch{ptr<uint8_t>(c->codes), ptr<float>(c->w_pad), ptr<uint8_t>(c->site_ok),
+                                    ptr<uint32_t>(c->tiles), c->n_tiles, nullptr, (uint32_t)c->L, (uint32_t)c->NP,
+                                    chunk_rows_of(c->L), thr, c->safe, c->opt_valu_plain, false, 0, 0},
+                         o, dense, c->stream);
+    } else {
+        MfmaLaunch m = mfma_base(c, thr);
         m.codes = ptr<uint8_t>(c->codes);
         m.frag = c->use_frag ? ptr<uint8_t>(c->frag) : nullptr;
         m.frag_b = c->use_frag ? ptr<uint8_t>(c->frag) + c->LP * c->NP : nullptr;
-        m.wplanes = ptr<int8_t>(c->planes);
-        m.tiles = ptr<uint32_t>(c->tiles);
-        m.n_tiles = c->n_tiles;
-        m.L = (uint32_t)c->L;
-        m.NP = (uint32_t)c->NP;
-        m.LP = (uint32_t)c->LP;
-        m.n_chunk_rows = n;
-        m.thr = thr;
         m.shift = c->shift;
         m.plane_mask = c->plane_mask;
-        m.nonneg = c->wst.nonneg;
-        // both need a positive threshold to reject anything
-        m.prefilter = c->opt_prefilter && thr > 0.0f;
-        // auto: below a threshold at which the screen left more than half the
-        // tiles as candidates, every tile goes straight to the full kernel
-        m.screen = m.prefilter && (c->opt_screen == 2 || c->opt_screen == 3 ||
-                                   (c->opt_screen == 1 && thr > c->screen_bad_thr));
-        // ... where the one-plane screen proved ineffective, the two-plane one
-        // (>= 3 active planes), unless it proved ineffective too; in lib.rs's
-        // order the exact candidate pairs instead (below)
-        if (m.prefilter && !m.screen && c->opt_screen == 1 && !ref_screen && thr > c->screen2_bad_thr)
-            m.screen = m.screen2 = true;
-        if (c->opt_screen == 3) m.screen2 = true;
-        if (m.screen2 && __builtin_popcount(c->plane_mask & 15) < 3) {
-            m.screen2 = false;  // one or two active planes: the one-plane screen or the full kernel
-            m.screen = c->opt_screen == 2 || c->opt_screen == 3;
-        }
-        c->screened2 = m.screen && m.screen2;
+        m.route = plan.route;
+        m.bound_test = plan.bound_test;
+        m.fp6_bail = plan.fp6_bail;
+        m.i8img = &c->i8s;
         for (int t = 0; t < 3; ++t) m.resid[t] = c->wst.resid[t];
-        // the one-plane screen on fp6 x fp4 MFMA where the load allows it
-        const bool fp6_auto = c->opt_fp6 == 1 || c->opt_fp6 == 3;
-        m.fp6 = c->fp6_ok && (c->opt_fp6 == 2 || (fp6_auto && c->fp6_better && thr > c->fp6_bad_thr))
-                    ? &c->f6 : nullptr;
-        // auto: past a sixteenth of the tiles as candidates the fp6 screen
-        // gives the pass up and run_complete re-runs it on the i8 screen (not
-        // with per-chunk progress, which a re-run does not report again, nor
-        // with a caller's count word, which a collective may read before the
-        // re-run rewrites it)
-        m.fp6_bail = fp6_auto && !c->prog_pass && !c->pend.count_out ? std::max<uint32_t>(c->n_tiles / 16, 1) : 0;
-        m.f6_pairs = c->f6_n_pairs ? ptr<uint32_t>(c->f6_pairs) : nullptr;
-        m.f6_n_pairs = c->f6_n_pairs;
-        // the i8 one-plane screen on tile pairs (WLD_OPT_I8_PAIRS): its images
-        // built at the first pass that needs them
-        if (!dense && m.prefilter && m.screen && !m.screen2 && !m.fp6 && c->opt_i8_pairs && c->f6_n_pairs &&
-            c->use_frag && c->wst.nonneg && c->NP <= 16384) {
-            if (!c->i8img_ok) WLD_TRY(i8img_prepare(c));
-            m.i8img = &c->i8s;
-        }
         for (int p = 0; p < 4; ++p) m.dsum[p] = c->wst.dsum[p];
         m.cand_list = ptr<uint32_t>(c->cand);
         // this pass's candidate set (the scan zeroes the other one, enqueue_pass)
@@ -870,34 +855,21 @@ int launch_pairs(wld_ctx *c, float thr, const OrderArgs &o, const DenseArgs *den
         m.test_guard = c->opt_test_guard;
         if (scan && !dense) m.scan = *scan;
         RefRowsLaunch rr{};
-        if (ref_screen) {
+        if (c->opt_ref_sums) {  // lib.rs's order behind the integer kernel: the candidates' sums, the bound's slack
             m.ref_valu = &rv;
             m.r_extra_q = ref_extra_residual(c);
-            // where the screen does not pay: every tile on all planes, the
-            // pairs the bound cannot reject summed one by one in lib.rs's
-            // order, unless that proved to be most pairs (then the full kernel)
-            if (!m.screen && ((c->opt_screen == 1 && thr > c->ref_pairs_bad_thr) || c->opt_screen == 4)) {
+            if (plan.route == Route::CandidatePairs) {
                 rr = RefRowsLaunch{ptr<uint8_t>(c->rcodes), ptr<float>(c->rw), (uint32_t)c->NPr, c->ref_cls,
-                                   (uint32_t)(c->N % 8), n, thr, nullptr, nullptr, nullptr, ScanArgs{}};
+                                   (uint32_t)(c->N % 8), m.n_chunk_rows, thr, nullptr, nullptr, nullptr, ScanArgs{}};
                 m.ref_rows = &rr;
-                c->ref_pairs_pass = true;
             }
         }
-        if (ref_screen && !m.screen && !m.ref_rows) {
-            fused = launch_pair_valu(rv, o, nullptr, c->stream);  // the policy sends this threshold to the full kernel
-        } else {
-            sc = launch_pair_mfma(m, o, dense, c->stream, c->ev[6]);
-            fused = sc && scan && !dense;  // (a screen's candidate launch, or the candidate pairs' compaction)
-            c->fp6_pass = sc && m.fp6 && !m.screen2 && !m.ref_rows;  // (launch_pair_mfma's one-plane screen branch)
-        }
-    } else {
-        launch_pair_valu(ValuLaunch{ptr<uint8_t>(c->codes), ptr<float>(c->w_pad), ptr<uint8_t>(c->site_ok),
-                                    ptr<uint32_t>(c->tiles), c->n_tiles, nullptr, (uint32_t)c->L, (uint32_t)c->NP, n,
-                                    thr, c->safe, c->opt_valu_plain, false, 0, 0},
-                         o, dense, c->stream);
+        launch_pair_mfma(m, o, dense, c->stream, c->ev[6]);
+        // (a screen's candidate launch, or the candidate pairs' compaction)
+        fused = screen_policy::ran_screen(plan.route) && scan && !dense;
     }
     HIP_TRY(hipGetLastError());
-    if (screened) *screened = sc;
+    if (pass) *pass = plan;
     if (scan_fused) *scan_fused = fused;
     return WLD_OK;
 }
@@ -990,8 +962,7 @@ int wld_set_option(wld_ctx *c, int option, int64_t value) {
         case WLD_OPT_SCREEN:
             if (value < 0 || value > 4) return fail(WLD_E_ARG, "WLD_OPT_SCREEN takes 0 to 4");
             c->opt_screen = (int)value;
-            c->screen_bad_thr = c->screen2_bad_thr = c->ref_pairs_bad_thr = c->fp6_bad_thr = -1.0f;
-            c->fp6_good_thr = INFINITY;
+            c->learned.reset();
             break;
         case WLD_OPT_TILE_ORDER:
             c->opt_tile_rows = value != 0;
@@ -1007,8 +978,7 @@ int wld_set_option(wld_ctx *c, int option, int64_t value) {
         case WLD_OPT_VALU_PLAIN: c->opt_valu_plain = value != 0; break;
         case WLD_OPT_REF_SUMS:
             c->opt_ref_sums = value != 0;
-            c->screen_bad_thr = c->screen2_bad_thr = c->ref_pairs_bad_thr = c->fp6_bad_thr = -1.0f;
-            c->fp6_good_thr = INFINITY;  // the policy's break-even differs
+            c->learned.reset();  // the policy's break-even differs
             break;
         case WLD_OPT_STAGING_ROWS:
             if (value < 1) return fail(WLD_E_ARG, "WLD_OPT_STAGING_ROWS must be >= 1");
@@ -1029,8 +999,7 @@ int wld_set_option(wld_ctx *c, int option, int64_t value) {
         case WLD_OPT_SCREEN_FP6:
             if (value < 0 || value > 3) return fail(WLD_E_ARG, "WLD_OPT_SCREEN_FP6 takes 0 to 3");
             c->opt_fp6 = (int)value;
-            c->screen_bad_thr = c->screen2_bad_thr = c->ref_pairs_bad_thr = c->fp6_bad_thr = -1.0f;
-            c->fp6_good_thr = INFINITY;  // another screen's break-even
+            c->learned.reset();  // another screen's break-even
             break;
         default: return fail(WLD_E_ARG, "unknown option %d", option);
     }
@@ -1072,8 +1041,7 @@ int wld_set_window(wld_ctx *c, uint64_t max_distance, uint64_t max_sites) {
     }
     c->tiles_lb = c->tiles_le = ~0u;  // the tile lists follow the window
     // the auto screen policy learned its thresholds on another set of tiles
-    c->screen_bad_thr = c->screen2_bad_thr = c->ref_pairs_bad_thr = c->fp6_bad_thr = -1.0f;
-    c->fp6_good_thr = INFINITY;
+    c->learned.reset();
     return WLD_OK;
 }
 
@@ -1398,14 +1366,14 @@ int enqueue_pass(wld_ctx *c) {
     c->h_cnt[2] = c->h_cnt[3] = 0;
     c->h_cnt[4] = 0;  // the guard word
     HIP_TRY(hipEventRecord(c->ev[2], c->stream));
-    c->screened = c->screened2 = false;
+    c->pass = screen_policy::Plan{};  // (a range without tiles launches nothing: no screen ran)
     // the scan is fused into the launch after a screen for ranges up to 4096
     // chunks (C4: 3,160, ~10 us in one 256-thread workgroup); a larger range
     // (C5: 19,306 chunks, ~70 us fused) gets the 1024-thread scan kernel
     const bool fuse_scan = c->opt_fused_scan && lin_count && lin_count <= 4096;
     bool scan_fused = false;
     if (c->n_tiles)
-        WLD_TRY(launch_pairs(c, r.thr, o, nullptr, &c->screened, fuse_scan ? &sa : nullptr, &scan_fused));
+        WLD_TRY(launch_pairs(c, r.thr, o, nullptr, &c->pass, fuse_scan ? &sa : nullptr, &scan_fused));
     if (lin_count) c->cand_set ^= 1;  // this pass's scan (fused or below) zeroes the other set
     HIP_TRY(hipEventRecord(c->ev[3], c->stream));
     if (lin_count && !scan_fused) {  // else the last workgroup of the pair launch ran it
@@ -1445,34 +1413,17 @@ int enqueue_pass(wld_ctx *c) {
 // candidates the threshold (and any lower one) goes to the i8 screen, else it
 // (and any higher one) stays on fp6 with no further sample.  Small lists
 // (fewer than 2,048 tiles) take the pass itself as the test, as before.
-// Only where the pass would run the one-plane screen (launch_pairs: the
-// screen policy, no dense stats); on the context's own stream when the
-// caller lent it one and the fp6 operands were built before this run (the
-// probe reads only them), so the read-back does not wait for the caller's
-// earlier work on the borrowed stream.
+// Only where the pass would screen on fp6 (screen_policy::wants_sample).  On
+// the context's own stream when the caller lent it one and the fp6 operands
+// were built before this run (the probe reads only them), so the read-back
+// does not wait for the caller's earlier work on the borrowed stream (ADVICE
+// r5).
 int fp6_sample(wld_ctx *c, float thr, bool operands_fresh) {
-    if (c->opt_fp6 != 1 || !c->fp6_ok || !c->fp6_better || !(thr > c->fp6_bad_thr) || thr >= c->fp6_good_thr)
-        return WLD_OK;
-    if (c->kernel != WLD_KERNEL_MFMA || !c->use_frag || !c->opt_prefilter || !(thr > 0.0f) || c->opt_screen == 0 ||
-        c->n_tiles < 2048)
-        return WLD_OK;
-    if (!(c->opt_screen == 2 || c->opt_screen == 3 || (c->opt_screen == 1 && thr > c->screen_bad_thr)))
-        return WLD_OK;  // no one-plane screen at this threshold: nothing to decide
+    const PolicyInputs in = policy_inputs(c, thr, false);
+    if (!screen_policy::wants_sample(in.opt, in.load, in.pass, c->learned)) return WLD_OK;
     const hipStream_t s = !operands_fresh && c->own_stream ? c->own_stream : c->stream;
     WLD_TRY(ensure(c->fp6_probe_buf, 2 * sizeof(unsigned)));
-    MfmaLaunch m{};
-    m.wplanes = ptr<int8_t>(c->planes);
-    m.tiles = ptr<uint32_t>(c->tiles);
-    m.n_tiles = c->n_tiles;
-    m.L = (uint32_t)c->L;
-    m.NP = (uint32_t)c->NP;
-    m.LP = (uint32_t)c->LP;
-    m.n_chunk_rows = chunk_rows_of(c->L);
-    m.thr = thr;
-    m.nonneg = c->wst.nonneg;
-    m.fp6 = &c->f6;
-    m.f6_pairs = c->f6_n_pairs ? ptr<uint32_t>(c->f6_pairs) : nullptr;
-    m.f6_n_pairs = c->f6_n_pairs;
+    const MfmaLaunch m = mfma_base(c, thr);
     const uint32_t entries = m.f6_pairs ? m.f6_n_pairs : m.n_tiles;
     const uint32_t stride = std::max<uint32_t>(1, std::min<uint32_t>(64, entries / 256));
     launch_fp6_probe(m, ptr<unsigned>(c->fp6_probe_buf), stride, s);
@@ -1481,10 +1432,7 @@ int fp6_sample(wld_ctx *c, float thr, bool operands_fresh) {
     HIP_TRY(hipMemcpyAsync(h, c->fp6_probe_buf.p, sizeof(h), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     c->fp6_sampled = true;
-    if ((uint64_t)h[0] * 16 > h[1])
-        c->fp6_bad_thr = std::max(c->fp6_bad_thr, thr);
-    else
-        c->fp6_good_thr = std::min(c->fp6_good_thr, thr);
+    screen_policy::learn(c->learned, screen_policy::Sample{thr, h[0], h[1]});
     return WLD_OK;
 }
 
@@ -1643,7 +1591,8 @@ int run_complete(wld_ctx *c, uint64_t *n_rows) {
             // one) screens on i8 from now on, this pass included
             if (abandoned) return fail(WLD_E_HIP, "internal: a re-run pass was abandoned again");
             abandoned = true;
-            c->fp6_bad_thr = std::max(c->fp6_bad_thr, r.thr);
+            screen_policy::learn(c->learned,
+                                 screen_policy::Outcome{c->pass.route, r.thr, true, 0, c->n_tiles, 0, r.pairs});
             WLD_TRY(enqueue_pass(c));
             continue;
         }
@@ -1656,7 +1605,9 @@ int run_complete(wld_ctx *c, uint64_t *n_rows) {
     const uint64_t rows = h[1];
     // (exact candidate pairs: the cursor counts the candidates staged, the
     // chunk totals the rows kept)
-    if (c->ref_pairs_pass ? h[0] < h[1] : h[0] != h[1])
+    const screen_policy::Route route = c->pass.route;
+    const bool screened = screen_policy::ran_screen(route), cand_pairs = route == screen_policy::Route::CandidatePairs;
+    if (cand_pairs ? h[0] < h[1] : h[0] != h[1])
         return fail(WLD_E_HIP, "internal: staging cursor %llu vs chunk total %llu", h[0], h[1]);
     int order_end = c->gather_cap ? 5 : c->ev_end;  // with no rows (and no gather enqueued) it ends at the scan
     if (rows && lin_count && rows > c->gather_cap) {  // not gathered behind the scan
@@ -1680,41 +1631,17 @@ int run_complete(wld_ctx *c, uint64_t *n_rows) {
     c->stats.rows = rows;
     c->times_pending = true;  // (pair_kernel_ms, order_ms, screen_ms: materialize_times)
     c->times_order_end = order_end;
-    // (exact candidate pairs: the i8 pass, ref_sums_kernel, ref_compact_kernel)
-    c->stats.pair_kernel_launches = c->n_tiles ? (c->ref_pairs_pass ? 3 : c->screened ? 2 : 1) : 0;
+    c->stats.pair_kernel_launches = c->n_tiles ? screen_policy::stat_launches(route) : 0;
     // (under a window: the tiles holding an in-window pair, without the launch order's padding)
     c->stats.tiles = c->tiles_windowed ? c->n_tiles_listed : c->n_tiles;
-    c->stats.screened = c->ref_pairs_pass ? 4 : c->screened ? (c->screened2 ? 3 : 1) : 0;
-    c->stats.screen_fp6 = c->fp6_pass ? 1 : abandoned ? 2 : 0;
+    c->stats.screened = screen_policy::stat_screened(route);
+    c->stats.screen_fp6 = screen_policy::stat_screen_fp6(route) ? 1 : abandoned ? 2 : 0;
     c->stats.fp6_sampled = c->fp6_sampled ? 1 : 0;
-    c->stats.candidate_pairs = c->ref_pairs_pass ? h[0] : 0;
-    // auto: a threshold at which even the i8 screen leaves more than half the
-    // tiles is not screened from now on (nor any lower one): the screen costs a
-    // third of the full three-plane kernel, the candidates as much again; in
-    // lib.rs's order the exact candidate pairs take over there (a screened
-    // tile with one uncertain 16x16 sub-block costs ~0.12 us on the f32
-    // kernel: half the C4 tiles ~3 ms over the 0.9 ms screen, about the exact
-    // candidate pairs' cost)
-    // ... and one at which the two-plane screen (0.8 of the full kernel's
-    // time at BASELINE config 4, archive/profiles_r01_r03/r02s2/) leaves more than a fifth
-    // goes to the full kernel (the exact mode; lib.rs's order takes the two-
-    // plane screen only when asked, WLD_OPT_SCREEN 3)
-    // ... the fp6 screen first hands over to the i8 one (a tighter bound at
-    // twice the cost) once it leaves more than a sixteenth of the tiles (or,
-    // in auto, gives the pass up on reaching that many: the loop above)
-    if (c->fp6_pass && h[2] * 16 > c->n_tiles) {
-        c->fp6_bad_thr = std::max(c->fp6_bad_thr, r.thr);
-    } else if (c->screened && !c->ref_pairs_pass && !c->screened2 && h[2] * 2 > c->n_tiles) {
-        c->screen_bad_thr = std::max(c->screen_bad_thr, r.thr);
-    }
-    if (c->screened && c->screened2 && h[2] * 5 > c->n_tiles) c->screen2_bad_thr = std::max(c->screen2_bad_thr, r.thr);
-    // exact candidate pairs, each summed alone in lib.rs's order (~1 ms per
-    // million at C4 size): past a tenth of all pairs the full f32 kernel
-    // (27.8 ms for every tile at C4) is cheaper
-    if (c->ref_pairs_pass && h[0] * 10 > r.pairs) c->ref_pairs_bad_thr = std::max(c->ref_pairs_bad_thr, r.thr);
-    c->times_screened = c->screened;
-    c->stats.candidate_tiles = c->screened ? h[2] : c->n_tiles;
-    c->stats.candidate_blocks = c->screened && !c->ref_pairs_pass ? h[3] : 16 * (uint64_t)c->n_tiles;
+    c->stats.candidate_pairs = cand_pairs ? h[0] : 0;
+    // auto: what this pass's counts teach the policy (screen_policy.hpp: the break-evens)
+    screen_policy::learn(c->learned, screen_policy::Outcome{route, r.thr, false, h[2], c->n_tiles, h[0], r.pairs});
+    c->stats.candidate_tiles = screened ? h[2] : c->n_tiles;
+    c->stats.candidate_blocks = screened && !cand_pairs ? h[3] : 16 * (uint64_t)c->n_tiles;
     if (n_rows) *n_rows = rows;
     return WLD_OK;
 }
@@ -1768,7 +1695,8 @@ int wld_run_after(wld_ctx *c, wld_ctx *prev) {
     // ev[6] separates a screened pass's screen from its candidate launch;
     // ev[3] follows the pair kernel(s) (enqueue_pass)
     if (c->stream == prev->stream) return WLD_OK;  // one stream: already in order
-    HIP_TRY(hipStreamWaitEvent(c->stream, prev->screened ? prev->ev[6] : prev->ev[3], 0));
+    const bool screened = screen_policy::ran_screen(prev->pass.route);
+    HIP_TRY(hipStreamWaitEvent(c->stream, screened ? prev->ev[6] : prev->ev[3], 0));
     return WLD_OK;
 }
 
@@ -2121,9 +2049,7 @@ int summary_range(wld_ctx *c, uint32_t lb, uint32_t le, uint64_t bin_width, uint
     HIP_TRY(hipMemsetAsync(c->sum_buf.p, 0, bytes, c->stream));
     const SummaryArgs sa{d_u64, d_f64, d_f64 + 1, d_u32, nb ? d_u64 + 4 : nullptr, nb ? d_f64 + 1 + LP : nullptr,
                          c->has_pos ? ptr<uint32_t>(c->site_map) : nullptr, bin_width, (uint32_t)nb};
-    const ValuLaunch v{ptr<uint8_t>(c->rcodes), ptr<float>(c->rw), ptr<uint8_t>(c->site_ok), ptr<uint32_t>(c->tiles),
-                       c->n_tiles, nullptr, (uint32_t)L, (uint32_t)c->NPr, chunk_rows_of(L), 0.0f, false, false, true,
-                       c->ref_cls, (uint32_t)(c->N % 8)};
+    const ValuLaunch v = ref_valu_launch(c, 0.0f);  // (finite weights: summary_check)
     OrderArgs o{};  // the window only
     o.L = (uint32_t)L;
     o.T = (uint32_t)(LP / kTile);

@@ -6,6 +6,8 @@
 #include <cstdint>
 #include <vector>
 
+#include "screen_policy.hpp"
+
 namespace wld {
 
 // ---- layout constants (see DESIGN.md "Data layout in HBM") ----
@@ -281,9 +283,8 @@ struct MfmaLaunch {
     int shift;
     unsigned plane_mask;
     int nonneg;
-    bool prefilter;  // thr > 0: skip pairs r2_bound_skip rejects
-    bool screen;     // with the prefilter: one-plane screen, then candidates
-    bool screen2;    // the screen on the top two digit planes (>= 3 active planes)
+    screen_policy::Route route;  // the pass's path (screen_policy.hpp): IntAll, a screen, or CandidatePairs
+    bool bound_test;             // thr > 0: skip pairs r2_bound_skip rejects
     uint64_t resid[3];
     uint64_t dsum[4];
     uint32_t *cand_list;   // 32 n_tiles entries: 16 buckets of tiles, then 16 of their sub-block bits
@@ -305,25 +306,25 @@ struct MfmaLaunch {
     // with a screen: the run's scan, fused into the screen's or the candidate
     // launch's last workgroup when scan.ticket is set
     ScanArgs scan;
-    // the one-plane screen on fp6 x fp4 MFMA instead of i8 (null: the i8 screen)
+    // Fp6Screen (and the sample run): the fp6 operands
     const Fp6Screen *fp6;
     // ... gives up past this many candidate tiles (0: never; kAbandonBit)
     uint32_t fp6_bail;
     // ... its tile-pair list (pair_fp6_screen2w_kernel; XCD-ordered, kNoTile padded)
     const uint32_t *f6_pairs;
     uint32_t f6_n_pairs;
-    // the i8 one-plane screen on the tile-pair list with pre-multiplied
-    // operands (null: the per-tile LDS kernel)
+    // I8PairScreen: the pre-multiplied operands of the top active plane
     const I8Screen *i8img = nullptr;
 };
 // The fp6 screen's sample run over every stride-th entry of its list: probe[0]
 // = the sampled tiles holding a pair its bound cannot reject, probe[1] = the
 // sampled tiles (m as for the pass; nothing else is written)
 void launch_fp6_probe(const MfmaLaunch &m, unsigned *probe, uint32_t stride, hipStream_t s);
-// Enqueues the MFMA pair kernel(s) of one pass; returns true when a screen
-// (one- or two-plane) ran (then screen_done, if given, is recorded between
-// the two launches).
-bool launch_pair_mfma(const MfmaLaunch &m, const OrderArgs &o, const DenseArgs *dense, hipStream_t s,
+// Enqueues the MFMA pair kernel(s) of one pass by m.route; where a screen runs
+// (screen_policy::ran_screen; never for dense stats or site-major, which the
+// policy sends to IntAll) screen_done, if given, is recorded between the two
+// launches.
+void launch_pair_mfma(const MfmaLaunch &m, const OrderArgs &o, const DenseArgs *dense, hipStream_t s,
                       hipEvent_t screen_done);
 
 // order.hip

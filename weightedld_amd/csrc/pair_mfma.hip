@@ -1661,11 +1661,11 @@ void launch_fp6_probe(const MfmaLaunch &m, unsigned *probe, uint32_t stride, hip
     launch_fp6_screen(m, ok_bits, OrderArgs{}, sc, sc.probe_stride, s);
 }
 
-bool launch_pair_mfma(const MfmaLaunch &m, const OrderArgs &o, const DenseArgs *dense, hipStream_t s,
+void launch_pair_mfma(const MfmaLaunch &m, const OrderArgs &o, const DenseArgs *dense, hipStream_t s,
                       hipEvent_t screen_done) {
+    using screen_policy::Route;
     const DenseArgs dn = dense ? *dense : DenseArgs{nullptr, nullptr, nullptr, nullptr};
     const uint64_t *ok_bits = reinterpret_cast<const uint64_t *>(m.wplanes + okbits_offset(m.NP));
-    const bool prefilter = !dense && m.prefilter && m.thr > 0.0f;
     ScreenArgs sc{0.0,         0.0f,         0.0f,      0.0f,        0, m.nonneg, m.cand_list, m.cand_count,
                   m.cand_list + 16 * (size_t)m.n_tiles, m.cand_work, m.cand_buckets, m.n_tiles, 0, ScanArgs{}};
     if (!m.frag) {  // site-major kernel (all three planes)
@@ -1673,13 +1673,13 @@ bool launch_pair_mfma(const MfmaLaunch &m, const OrderArgs &o, const DenseArgs *
         if (dense)
             hipLaunchKernelGGL((pair_mfma_rows_kernel<kModeDense>), g, b, 0, s, m.codes, m.wplanes, ok_bits, m.tiles,
                                m.L, m.NP, m.n_chunk_rows, m.thr, m.shift, o, dn, sc);
-        else if (prefilter)
+        else if (m.bound_test)
             hipLaunchKernelGGL((pair_mfma_rows_kernel<kModePrefilter>), g, b, 0, s, m.codes, m.wplanes, ok_bits,
                                m.tiles, m.L, m.NP, m.n_chunk_rows, m.thr, m.shift, o, dn, sc);
         else
             hipLaunchKernelGGL((pair_mfma_rows_kernel<kModeAll>), g, b, 0, s, m.codes, m.wplanes, ok_bits, m.tiles,
                                m.L, m.NP, m.n_chunk_rows, m.thr, m.shift, o, dn, sc);
-        return false;
+        return;
     }
     // the nonzero digit planes in ascending order, 2 bits each; no plane is
     // all zero only if some weight is nonzero, which the caller guarantees
@@ -1694,106 +1694,119 @@ bool launch_pair_mfma(const MfmaLaunch &m, const OrderArgs &o, const DenseArgs *
     if (n == 4) idx = 0 | (1 << 2) | (2 << 4) | (3 << 6);
     if (dense) {
         launch_lds_planes<kModeDense>(n, m, ok_bits, m.tiles, m.n_tiles, nullptr, m.n_tiles, idx, o, dn, sc, s);
-        return false;
+        return;
     }
-    if (!prefilter) {
+    // IntAll with nothing to reject by (ahead of the switch, where this
+    // instantiation has always come first: the kernels' order in the code
+    // object follows their first use here)
+    if (!m.bound_test) {
         launch_lds_planes<kModeAll>(n, m, ok_bits, m.tiles, m.n_tiles, nullptr, m.n_tiles, idx, o, dn, sc, s);
-        return false;
+        return;
     }
-    if (m.ref_rows) {
-        // candidate pairs, then each summed alone in lib.rs's order;
-        // screen_done separates the two launches, and the second runs the
-        // chunk scan.  The bound's residual is the reference's rounding
-        // (r_extra_q), which at these thresholds dwarfs what the lowest digit
-        // plane adds (2^-16 of the weights against ~1e-4 at N = 2000): with
-        // three or more active planes the top two suffice (2/3 of the MFMA
-        // work), the planes below bounded by resid as in the two-plane screen;
-        // sums in fixed-point units either way
-        if (n >= 3) {
-            const uint32_t lo = top - 1;
-            sc.R = (double)m.resid[lo - 1] + m.r_extra_q;
-            launch_lds<kModeRefPairs, 2>(m, ok_bits, m.tiles, m.n_tiles, nullptr, m.n_tiles, lo | (top << 2), o, dn,
-                                          sc, s);
-        } else {
-            sc.R = m.r_extra_q;
-            launch_lds_planes<kModeRefPairs>(n, m, ok_bits, m.tiles, m.n_tiles, nullptr, m.n_tiles, idx, o, dn, sc,
-                                             s);
+    // a screen runs (and a candidate launch after it, which takes the run's
+    // scan).  lib.rs's order on the f32 kernel: candidates as 16-row-block
+    // items (buckets 0-3 of capacity 4 n_tiles: the 16 n_tiles list entries)
+    const auto begin_screen = [&] {
+        sc.scan = m.scan;
+        if (m.ref_valu && !m.ref_valu->safe) {
+            sc.rb_items = 1;
+            sc.cand_cap = 4 * m.n_tiles;
         }
-        if (screen_done) (void)hipEventRecord(screen_done, s);
-        RefRowsLaunch rr = *m.ref_rows;
-        rr.slices = m.cand_list;
-        rr.slice_count = m.cand_count;
-        rr.work = m.cand_work;
-        rr.scan = m.scan;
-        launch_ref_rows(rr, o, s);
-        return true;
+    };
+    switch (m.route) {
+        case Route::F32Plain:
+        case Route::F32RefOrder: return;  // (launch_pair_valu's: never sent here)
+        case Route::CandidatePairs: {
+            // candidate pairs, then each summed alone in lib.rs's order;
+            // screen_done separates the two launches, and the second runs the
+            // chunk scan.  The bound's residual is the reference's rounding
+            // (r_extra_q), which at these thresholds dwarfs what the lowest digit
+            // plane adds (2^-16 of the weights against ~1e-4 at N = 2000): with
+            // three or more active planes the top two suffice (2/3 of the MFMA
+            // work), the planes below bounded by resid as in the two-plane screen;
+            // sums in fixed-point units either way
+            if (n >= 3) {
+                const uint32_t lo = top - 1;
+                sc.R = (double)m.resid[lo - 1] + m.r_extra_q;
+                launch_lds<kModeRefPairs, 2>(m, ok_bits, m.tiles, m.n_tiles, nullptr, m.n_tiles, lo | (top << 2), o,
+                                              dn, sc, s);
+            } else {
+                sc.R = m.r_extra_q;
+                launch_lds_planes<kModeRefPairs>(n, m, ok_bits, m.tiles, m.n_tiles, nullptr, m.n_tiles, idx, o, dn,
+                                                 sc, s);
+            }
+            if (screen_done) (void)hipEventRecord(screen_done, s);
+            RefRowsLaunch rr = *m.ref_rows;
+            rr.slices = m.cand_list;
+            rr.slice_count = m.cand_count;
+            rr.work = m.cand_work;
+            rr.scan = m.scan;
+            launch_ref_rows(rr, o, s);
+            return;
+        }
+        case Route::IntAll:
+            launch_lds_planes<kModePrefilter>(n, m, ok_bits, m.tiles, m.n_tiles, nullptr, m.n_tiles, idx, o, dn, sc,
+                                              s);
+            return;
+        case Route::TwoPlaneScreen: {
+            // Two-plane screen (low thresholds, where the top plane's residual
+            // leaves most tiles undecided; three or more active planes): planes
+            // lo = top - 1 and top, sums in units of plane lo, the planes below
+            // lo bounded by resid[lo - 1] (top >= 2 with three or more active
+            // planes, so lo >= 1).  Per pair r2_bound_skip in f64; candidates
+            // then get every plane as below.
+            begin_screen();
+            const uint32_t lo = top - 1;
+            sc.R = ldexp((double)m.resid[lo - 1] + m.r_extra_q, -8 * (int)lo);
+            sc.Rf = (float)sc.R;
+            if ((double)sc.Rf < sc.R) sc.Rf = nextafterf(sc.Rf, INFINITY);
+            sc.f32 = 0;
+            launch_lds<kModeScreen, 2>(m, ok_bits, m.tiles, m.n_tiles, nullptr, m.n_tiles, lo | (top << 2), o, dn, sc,
+                                       s);
+            break;
+        }
+        case Route::Fp6Screen:
+            begin_screen();
+            fp6_screen_args(m, sc);
+            sc.bail = m.fp6_bail;
+            launch_fp6_screen(m, ok_bits, o, sc, 1, s);
+            break;
+        case Route::I8PairScreen:
+        case Route::I8TileScreen:
+            // One-plane screen: the top plane alone over every tile, the
+            // residual of the lower planes bounded by R (in top-digit units:
+            // exact, a power-of-two scaling of an integer below 2^53);
+            // candidate tiles then get every plane.  With one nonzero plane
+            // (equal weights, e.g. --unweighted) the screen's sums are exact
+            // (R = 0): it only moves the per-pair work to the cheap f32 bound,
+            // and the candidate launch (two-plane instantiation) adds an
+            // all-zero plane.
+            begin_screen();
+            sc.R = ldexp((top > 0 ? (double)m.resid[top - 1] : 0.0) + m.r_extra_q, -8 * (int)top);
+            if (n == 1) idx = top | ((top == 0 ? 1u : 0u) << 2);
+            sc.Rf = (float)sc.R;
+            if ((double)sc.Rf < sc.R) sc.Rf = nextafterf(sc.Rf, INFINITY);
+            // 2: doubled sums (NP <= 16384), 1: halved sums with f64 fallback, 0: f64
+            sc.f32 = m.nonneg ? (m.NP <= kScrF32MaxNP ? 2 : m.NP <= kScreenF32MaxNP ? 1 : 0) : 0;
+            if (m.route == Route::I8PairScreen) {
+                // tile pairs, wide waves, pre-multiplied operands (doubled
+                // sums): the xy2 epilogue on exact marginals needs R2 = 2 R on
+                // the integer grid (rounded up: a larger residual bound is
+                // still one)
+                sc.Rf = (float)(std::ceil(2.0 * sc.R) / 2.0);
+                screen_consts((float)(2 * m.dsum[top]), 2.0f * sc.Rf, sc.E, sc.mloc);
+                hipLaunchKernelGGL(pair_i8_screen2w_kernel, dim3(m.f6_n_pairs), dim3(256), 0, s, m.i8img->a8,
+                                   m.i8img->b8, ok_bits, m.f6_pairs, m.f6_n_pairs, (uint32_t)(m.NP / 64), m.L,
+                                   m.n_chunk_rows, m.thr, o, sc);
+                break;
+            }
+            // every doubled one-plane T <= 2 sum_k |d_top,k| <= 256 NP <= 2^22 (exact in f32)
+            if (sc.f32 == 2) screen_consts((float)(2 * m.dsum[top]), 2.0f * sc.Rf, sc.E, sc.mloc);
+            launch_lds<kModeScreen, 1>(m, ok_bits, m.tiles, m.n_tiles, nullptr, m.n_tiles, top, o, dn, sc, s);
+            break;
     }
-    if (!m.screen) {
-        launch_lds_planes<kModePrefilter>(n, m, ok_bits, m.tiles, m.n_tiles, nullptr, m.n_tiles, idx, o, dn, sc, s);
-        return false;
-    }
-    sc.scan = m.scan;  // from here on a screen runs (and a candidate launch after it)
-    // lib.rs's order on the f32 kernel: candidates as 16-row-block items
-    // (buckets 0-3 of capacity 4 n_tiles: the 16 n_tiles list entries)
-    if (m.ref_valu && !m.ref_valu->safe) {
-        sc.rb_items = 1;
-        sc.cand_cap = 4 * m.n_tiles;
-    }
-    // Screen: the top plane alone over every tile, the residual of the lower
-    // planes bounded by R (in top-digit units: exact, a power-of-two scaling
-    // of an integer below 2^53); candidate tiles then get every plane.  With
-    // one nonzero plane (equal weights, e.g. --unweighted) the screen's sums
-    // are exact (R = 0): it only moves the per-pair work to the cheap f32
-    // bound, and the candidate launch (two-plane instantiation) adds an
-    // all-zero plane.
-    if (m.screen2 && n >= 3) {
-        // Two-plane screen (low thresholds, where the top plane's residual
-        // leaves most tiles undecided): planes lo = top - 1 and top, sums in
-        // units of plane lo, the planes below lo bounded by resid[lo - 1]
-        // (top >= 2 with three or more active planes, so lo >= 1).  Per pair
-        // r2_bound_skip in f64; candidates then get every plane as below.
-        const uint32_t lo = top - 1;
-        sc.R = ldexp((double)m.resid[lo - 1] + m.r_extra_q, -8 * (int)lo);
-        sc.Rf = (float)sc.R;
-        if ((double)sc.Rf < sc.R) sc.Rf = nextafterf(sc.Rf, INFINITY);
-        sc.f32 = 0;
-        launch_lds<kModeScreen, 2>(m, ok_bits, m.tiles, m.n_tiles, nullptr, m.n_tiles, lo | (top << 2), o, dn, sc, s);
-        if (screen_done) (void)hipEventRecord(screen_done, s);
-        launch_candidates(m, n, idx, ok_bits, o, dn, sc, s);
-        return true;
-    }
-    if (m.fp6) {
-        fp6_screen_args(m, sc);
-        sc.bail = m.fp6_bail;
-        launch_fp6_screen(m, ok_bits, o, sc, 1, s);
-        if (screen_done) (void)hipEventRecord(screen_done, s);
-        launch_candidates(m, n, idx, ok_bits, o, dn, sc, s);
-        return true;
-    }
-    sc.R = ldexp((top > 0 ? (double)m.resid[top - 1] : 0.0) + m.r_extra_q, -8 * (int)top);
-    if (n == 1) idx = top | ((top == 0 ? 1u : 0u) << 2);
-    sc.Rf = (float)sc.R;
-    if ((double)sc.Rf < sc.R) sc.Rf = nextafterf(sc.Rf, INFINITY);
-    // 2: doubled sums (NP <= 16384), 1: halved sums with f64 fallback, 0: f64
-    sc.f32 = m.nonneg ? (m.NP <= kScrF32MaxNP ? 2 : m.NP <= kScreenF32MaxNP ? 1 : 0) : 0;
-    if (sc.f32 == 2 && m.i8img && m.f6_pairs && m.i8img->digit_plane == top) {
-        // tile pairs, wide waves, pre-multiplied operands: the xy2 epilogue on
-        // exact marginals needs R2 = 2 R on the integer grid (rounded up: a
-        // larger residual bound is still one)
-        sc.Rf = (float)(std::ceil(2.0 * sc.R) / 2.0);
-        screen_consts((float)(2 * m.dsum[top]), 2.0f * sc.Rf, sc.E, sc.mloc);
-        hipLaunchKernelGGL(pair_i8_screen2w_kernel, dim3(m.f6_n_pairs), dim3(256), 0, s, m.i8img->a8, m.i8img->b8,
-                           ok_bits, m.f6_pairs, m.f6_n_pairs, (uint32_t)(m.NP / 64), m.L, m.n_chunk_rows, m.thr, o, sc);
-        if (screen_done) (void)hipEventRecord(screen_done, s);
-        launch_candidates(m, n, idx, ok_bits, o, dn, sc, s);
-        return true;
-    }
-    // every doubled one-plane T <= 2 sum_k |d_top,k| <= 256 NP <= 2^22 (exact in f32)
-    if (sc.f32 == 2) screen_consts((float)(2 * m.dsum[top]), 2.0f * sc.Rf, sc.E, sc.mloc);
-    launch_lds<kModeScreen, 1>(m, ok_bits, m.tiles, m.n_tiles, nullptr, m.n_tiles, top, o, dn, sc, s);
     if (screen_done) (void)hipEventRecord(screen_done, s);
     launch_candidates(m, n, idx, ok_bits, o, dn, sc, s);
-    return true;
 }
 
 }  // namespace wld
