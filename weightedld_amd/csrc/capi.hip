@@ -27,6 +27,7 @@
 #include "summary_plan.hpp"
 #include "prune_plan.hpp"
 #include "kernels.hpp"
+#include "fp6_scale.hpp"
 
 using namespace wld;
 
@@ -139,7 +140,7 @@ struct wld_ctx {
     DevBuf raw, wraw, codes, w_pad, wstats, site_ok, site_map, planes, frag;
     DevBuf rcodes, rw;       // WLD_OPT_REF_SUMS: codes and weights in lane-class order (ref_layout_kernel)
     // the fp6 screen (fp6_prepare): weight codes, packed operands, constants
-    DevBuf w6, f6a, f6b;
+    DevBuf w6, f6a, f6b, f6marg;  // (f6marg: the per-site marginals of the complement-coded images)
     Fp6Screen f6{};
     // the i8 one-plane screen's pre-multiplied images (i8img_prepare, at the
     // first pass that screens on i8 with them)
@@ -236,7 +237,7 @@ struct wld_ctx {
         // work queued on a borrowed stream (wld_set_stream) may still use the
         // buffers: it completes before they are freed
         if (stream && stream != own_stream) (void)hipStreamSynchronize(stream);
-        DevBuf *all[] = {&keep, &htab, &htab_kept, &site_index, &raw, &wraw, &codes, &w_pad, &wstats, &site_ok, &site_map, &planes, &frag, &rcodes, &rw, &w6, &f6a, &f6b, &i8a, &i8b, &tiles, &cand, &f6_pairs, &fp6_probe_buf,
+        DevBuf *all[] = {&keep, &htab, &htab_kept, &site_index, &raw, &wraw, &codes, &w_pad, &wstats, &site_ok, &site_map, &planes, &frag, &rcodes, &rw, &w6, &f6a, &f6b, &f6marg, &i8a, &i8b, &tiles, &cand, &f6_pairs, &fp6_probe_buf,
                          &seg_cnt, &seg_off, &chunk_total, &chunk_base, &counters, &chunk_left, &prog_n, &win_hi, &win_pairs, &sum_buf, &st_a, &st_b, &st_d,
                          &st_dp, &st_r2, &out_a, &out_b, &out_d, &out_dp, &out_r2};
         for (DevBuf *b : all) release(*b);
@@ -300,28 +301,12 @@ int weight_shift(float maxabs, int planes) {
 
 double ref_extra_residual(const wld_ctx *c);
 
-// e2m3 (fp6) encoding of a value in [0, 7.5] rounded to the nearest grid
-// point, ties to the even code: sign 0, exponent bias 1, 3 mantissa bits.
-// The grid steps by 1/8 below 2, by 1/4 in [2, 4) and by 1/2 from 4; within
-// each the code's parity is the grid index's, so round-half-even on the index
-// (nearbyint) is ties-to-even on the code (an index rounding up to the next
-// binade's first point lands on its even code, m = 0).
-uint32_t fp6_code(double x, double *rounded) {
-    x = std::min(std::max(x, 0.0), 7.5);
-    const double step = x < 2.0 ? 0.125 : x < 4.0 ? 0.25 : 0.5;
-    const double v = std::min(std::nearbyint(x / step) * step, 7.5);
-    *rounded = v;
-    if (v < 1.0) return (uint32_t)(v * 8.0);                             // e = 0 (subnormal), m = 8v
-    if (v < 2.0) return 8u + (uint32_t)((v - 1.0) * 8.0);                // e = 1
-    if (v < 4.0) return 16u + (uint32_t)((v * 0.5 - 1.0) * 8.0);         // e = 2
-    return 24u + (uint32_t)((v * 0.25 - 1.0) * 8.0);                     // e = 3
-}
-
 // The fp6 screen's operands for this load (pair_mfma.hip): nonnegative
 // finite weights, NP <= 16384 (its f32 test on doubled sums), the i8 kernel's
-// fragment layout in use.  The weights are rounded to e2m3 at the common
-// scale S (of 51 candidates in [3.75, 7.5] / max w) that minimises the L1
-// rounding residual; R (in fp6 units) bounds each pass's 2x2-cell L1 distance
+// fragment layout in use.  The weights are rounded to e2m3 (fp6_scale.hpp) at
+// the common scale S whose L1 rounding residual is within 1% of the smallest
+// of its candidates' and whose codes have the fewest set mantissa bits
+// (fp6_choose_scale); R (in fp6 units) bounds each pass's 2x2-cell L1 distance
 // between the screen's sums and the sums the candidate launch computes: the
 // rounding, plus the fixed point's 0.5 per sequence (exact mode) and lib.rs's
 // f32 summation (9 gamma_m sum w, ref_extra_residual) — both added, so one
@@ -338,17 +323,7 @@ int fp6_prepare(wld_ctx *c) {
     double wmax = 0.0, wsum = 0.0;
     for (size_t k = 0; k < c->N; ++k) wmax = std::max(wmax, (double)w[k]), wsum += (double)w[k];
     if (!(wmax > 0.0) || !std::isfinite(wsum)) return WLD_OK;
-    double best_r = INFINITY, best_s = 0.0;
-    for (int f = 0; f <= 50; ++f) {
-        const double S = 7.5 * (0.5 + 0.01 * f) / wmax;
-        double r = 0.0, v;
-        for (size_t k = 0; k < c->N; ++k) {
-            fp6_code(S * w[k], &v);
-            r += std::fabs(S * w[k] - v);
-        }
-        if (r / S < best_r) best_r = r / S, best_s = S;
-    }
-    const double S = best_s;
+    const double S = fp6_choose_scale(w.data(), c->N, wmax).S;
     std::vector<uint8_t> codes(c->NP, 0);
     double r6 = 0.0, sum6 = 0.0, v;
     for (size_t k = 0; k < c->N; ++k) {
@@ -360,6 +335,7 @@ int fp6_prepare(wld_ctx *c) {
     const double extra = S * (9.0 * gamma * wsum + 0.5 * (double)c->N * std::ldexp(1.0, -c->shift) * (1.0 + 9.0 * gamma));
     c->f6.R = (r6 + extra) * (1.0 + 1e-9) + 1e-9 * sum6;
     c->f6.Tg = (float)(2.0 * sum6);  // exact: a multiple of 1/8 below 2^21
+    c->f6.W6 = (float)sum6;          // ... and so is the sum itself (the complement coding's W6)
     c->f6.NK = (uint32_t)((c->NP + 127) / 128);
     c->fp6_rel = c->f6.R / std::max(sum6, 1e-300);
     // the i8 top digit's: its residual (and the reference's rounding) against
@@ -372,13 +348,16 @@ int fp6_prepare(wld_ctx *c) {
     WLD_TRY(ensure(c->w6, c->NP));
     WLD_TRY(ensure(c->f6a, fp6_a_bytes(c->LP, c->NP)));
     WLD_TRY(ensure(c->f6b, fp6_b_bytes(c->LP, c->NP)));
+    WLD_TRY(ensure(c->f6marg, 2 * c->LP * sizeof(float)));
+    // (codes: zero past N, which the complement coding needs, pair_mfma.hip frag6_kernel)
     HIP_TRY(hipMemcpyAsync(c->w6.p, codes.data(), c->NP, hipMemcpyHostToDevice, c->stream));
     launch_frag6(ptr<uint8_t>(c->codes), ptr<uint8_t>(c->w6), c->LP, c->NP, ptr<uint8_t>(c->f6a), ptr<uint8_t>(c->f6b),
-                 c->stream);
+                 ptr<float>(c->f6marg), c->stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->f6.a6 = ptr<uint8_t>(c->f6a);
     c->f6.b6 = ptr<uint8_t>(c->f6b);
+    c->f6.marg = ptr<float>(c->f6marg);
     c->fp6_ok = true;
     c->fp6_better = c->fp6_rel <= std::max(2.0 * c->i8_rel, 0.02);
     return WLD_OK;

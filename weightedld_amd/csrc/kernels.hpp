@@ -246,18 +246,26 @@ constexpr uint32_t kRefRowsGrid = 2048;
 
 // The fp6 screen's operands (pair_mfma.hip frag6_kernel) and constants: R
 // (residual bound of the rounded weights plus the reference's rounding) and
-// Tg (>= every doubled T), in the units of the fp6 weights (capi.hip).
+// Tg (>= every doubled T), in the units of the fp6 weights (capi.hip).  The
+// images are complement-coded (missing / minor), so the screen also takes the
+// per-site marginals marg[2 s] = sum_k w6_k [s missing], marg[2 s + 1] = sum_k
+// w6_k [s minor] (LP sites) and W6 = sum_k w6_k, all exact multiples of 1/8
+// below 2^17, from which its epilogue restores the direct coding's sums
+// (pair_common.hpp f6c_direct).
 struct Fp6Screen {
     const uint8_t *a6, *b6;
+    const float *marg;
+    float W6;
     uint32_t NK;  // 128-sequence blocks
     double R;
     float Tg;
 };
 size_t fp6_a_bytes(size_t LP, size_t NP);
 size_t fp6_b_bytes(size_t LP, size_t NP);
-// w6: NP fp6 (e2m3) codes of the rounded weights (0 for padding)
+// w6: NP fp6 (e2m3) codes of the rounded weights (0 for padding: a padded
+// sequence reads as missing and must weigh nothing); marg: 2 LP floats
 void launch_frag6(const uint8_t *codes, const uint8_t *w6, size_t LP, size_t NP, uint8_t *a6, uint8_t *b6,
-                  hipStream_t s);
+                  float *marg, hipStream_t s);
 
 // The i8 one-plane screen's pre-multiplied operand images (pair_mfma.hip
 // pair_i8_screen2w_kernel; capi.hip i8img_prepare): A = the top weight digit

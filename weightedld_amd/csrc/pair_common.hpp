@@ -214,7 +214,9 @@ __host__ __device__ __forceinline__ float r2_screen_terms_fg(float F0, float G0,
 // and R2 on the 1/8 grid below 2^19: the marginals are exact; the numerator
 // and t1 as in r2_screen_terms_xy / _fg (X0 Y1 - X1 Y0 = 2 num, error <= 2u
 // (X0 Y1 + X1 Y0)(1 + u) <= 4u T^2: 2u T2^2 after doubling).  Skip iff t1 <= 0
-// and mlo >= mloc.
+// and mlo >= mloc.  (The fp6 screen's images are complement coded, missing /
+// minor in place of in / minor + 2 major; its epilogue first restores these
+// X0, Y0, X1, Y1 exactly, f6c_direct below, so nothing here changes.)
 // The a site's other allele: with X1', Y1' summed over the sequences where a
 // is minor (SA' = T - SA, SA'B = SB - SAB; X1' = X0 - X1, Y1' = Y0 - Y1) the
 // function computes the same test with m1 and m2 exchanged: A2' = 2(T - SA),
@@ -234,6 +236,37 @@ __host__ __device__ __forceinline__ float r2_screen_terms_xy2(float X0, float Y0
     mlo = fminf(fminf(m1, m2), fminf(m3, m4));
     const float nub = fmaf(2.0f, fabsf(fmaf(X0, Y1, -(X1 * Y0))), E);
     return fmaf(nub, nub, -(thr_c * ((m1 * m2) * (m3 * m4))));
+}
+// The fp6 screen's complement coding (pair_mfma.hip frag6_kernel): the A
+// channels hold w6 [missing] and w6 [minor], the B nibbles 2.0 for missing,
+// 1.0 for minor and 0 for major, so the MFMAs sum mostly zero products where
+// the direct coding (in / minor x minor + 2 major) summed mostly nonzero
+// ones.  With P = sum_k w6_k (miss | minor of a)_k (miss | minor of b)_k the
+// accumulators are aX = 2 P00 + P01, aY = P01, bX = 2 P10 + P11, bY = P11.
+// Per sequence [in a] = 1 - [miss a] and [minor b] + 2 [major b] = 2 - 2 [miss
+// b] - [minor b], so with the per-site marginals M_s = sum_k w6_k [s missing],
+// m_s = sum_k w6_k [s minor] and W6 = sum_k w6_k (fp6_marginals_kernel, once
+// per load) the direct coding's accumulators are
+//   X0 = aX + (2 (W6 - M_a) + (-2 M_b - m_b))    Y0 = m_b - aY
+//   X1 = 2 m_a - bX                              Y1 = bY.
+// Exact in f32: w6 is a multiple of 1/8 <= 7.5 and at most 16384 sequences
+// carry one, so W6, M, m and every P are multiples of 1/8 below 2^17, and
+// every operand, intermediate and result above is a multiple of 1/8 of
+// magnitude below 2^19 (|2 (W6 - M_a)|, |2 M_b + m_b| < 2^18, their sum's and
+// aX's < 2^18 + 2^17): 22 significant bits at most, no rounding anywhere, in
+// any order of evaluation.  So r2_screen_terms_xy2 receives the X0, Y0, X1,
+// Y1 the direct coding's MFMAs summed, bit for bit, and every verdict is the
+// same (tests/cpp/f6_complement_check.cpp).  The a row's term and the b
+// column's are formed once per row / column of a lane's pairs:
+__host__ __device__ __forceinline__ float f6c_row_term(float W6, float Ma) { return 2.0f * (W6 - Ma); }
+__host__ __device__ __forceinline__ float f6c_col_term(float Mb, float mb) { return fmaf(-2.0f, Mb, -mb); }
+// (aX, aY, bX) -> (X0, Y0, X1) in place; row = f6c_row_term of a, col =
+// f6c_col_term of b, ma2 = 2 m_a
+__host__ __device__ __forceinline__ void f6c_direct(float &x0, float &y0, float &x1, float row, float col, float ma2,
+                                                    float mb) {
+    x0 = x0 + (row + col);
+    y0 = mb - y0;
+    x1 = ma2 - x1;
 }
 __host__ __device__ __forceinline__ float r2_screen_violation(float T, float A, float B, float AB, float R,
                                                               float thr_c) {

@@ -843,29 +843,50 @@ __global__ __launch_bounds__(64 * GroupShape<NPL>::kWaves, GroupShape<NPL>::kWgP
 // A operands and fp4 (e2m1) B operands, no block scales: 128 sequences per
 // instruction at the cycles of the i8 kernel's 64.  Every weight is rounded
 // to its nearest e2m3 value at a common scale S (w6_k = fp6(S w_k), a multiple
-// of 1/8 in [0, 7.5]).  A holds two channels per a site and sequence: w6 where
-// the symbol is major or minor ("in", lib.rs:435) and w6 where it is minor.
-// B holds one fp4 nibble per b symbol, minor + 2 major (1.0 / 2.0, 0 neither),
-// and each B register is multiplied twice: raw (X) and masked to its minor
-// bit (Y, raw & 0x2222...).  Per pair the four accumulators (channel_a in /
-// minor x X / Y) are, with T, SB and the minor-a sums SA', SA'B (lib.rs:441-444's
-// sums of the rounded weights, SA' = T - SA, SA'B = SB - SAB),
-//   X0 = T + SB, Y0 = T - SB, X1 = SA' + SA'B, Y1 = SA' - SA'B.
-// The per-pair test (r2_screen_terms_xy2) is symmetric in the a site's two
-// alleles, so it takes the minor-a sums where it was derived for the major-a
-// ones (pair_common.hpp).  The minor channel is there for the clock, not the
-// count: the kernel runs power-limited (2.02 GHz on random data, 2.38 GHz on
-// all-zero images of the same shape, 20% less time: DESIGN.md Appendix A), and
-// an A image that is 0.60 instead of 0.75 nonzero costs less per MFMA (C4
+// of 1/8 in [0, 7.5]; S by fp6_scale.hpp's rule).  The images are complement
+// coded: they hold the rare symbols, so that most products are zero.  A
+// holds two channels per a site and sequence: w6 where the symbol is missing
+// (not "in", lib.rs:435) and w6 where it is minor.  B holds one fp4 nibble
+// per b symbol, 2.0 (0x4) missing, 1.0 (0x2) minor, 0 major, and each B
+// register is multiplied twice: raw (X) and masked to its minor bit (Y, raw
+// & 0x2222...).  With P = sum_k w6_k (miss | minor of a)(miss | minor of b)
+// the four accumulators (channel_a x X / Y) are
+//   aX = 2 P00 + P01, aY = P01, bX = 2 P10 + P11, bY = P11,
+// and the epilogue restores from them and the per-site marginals M_s = sum_k
+// w6_k [s missing], m_s = sum_k w6_k [s minor] and W6 = sum_k w6_k
+// (fp6_marginals_kernel, once per load) the sums of the direct coding (A "in"
+// and minor, B minor + 2 major), exactly (f6c_rebuild; pair_common.hpp
+// f6c_direct has the argument):
+//   X0 = T + SB = aX + 2 (W6 - M_a) - 2 M_b - m_b,   Y0 = T - SB = m_b - aY,
+//   X1 = SA' + SA'B = 2 m_a - bX,                     Y1 = SA' - SA'B = bY
+// (T, SB and the minor-a sums SA' = T - SA, SA'B = SB - SAB: lib.rs:441-444's
+// sums of the rounded weights).  The per-pair test (r2_screen_terms_xy2) is
+// symmetric in the a site's two alleles, so it takes the minor-a sums where
+// it was derived for the major-a ones (pair_common.hpp), and it sees the same
+// X0, Y0, X1, Y1, bit for bit, as under the direct coding: every verdict and
+// candidate set is unchanged.  The coding is there for the clock, not the
+// count: the kernel runs power-limited (2.03 GHz on random data under the
+// direct coding, 2.39 GHz on all-zero images of the same shape, 20% less
+// time: DESIGN.md §4.1, Appendix A), and what the operands' values cost in
+// the matrix pipe is the pool.  On C4's symbols (missing 0.1, minor 0.3,
+// major 0.6) the direct coding's four product streams are 0.81 / 0.27 / 0.27
+// / 0.09 nonzero, the complement coding's 0.04 / 0.03 / 0.12 / 0.09, at the
+// same operand switching and the same stage loop (round 9: C4 -2.7% to
+// -3.5%; with the weights on a zero-mantissa code, fp6_scale.hpp, -8.4%;
+// profiles/r09a/).  Real alignments miss far less than 10%, which empties
+// the missing channel further.  (Round 7, on the direct coding: a minor
+// channel in place of a major one, an A image 0.60 instead of 0.75 nonzero,
 // -1.4%; a (major, minor) image, 0.45 nonzero but two more adds per pair and
-// two high-entropy channels, lost 1.2%).  Products are exact and every sum is
-// a multiple of 1/8 below 2^19, so the f32 MFMA sums are exact, and so is
-// every marginal the per-pair test forms from them (R is put on the same
-// grid): the screen's f32 bound holds with R = sum_k |S w_k - w6_k| plus the
-// reference's rounding, in the same units (capi.hip fp6_prepare).  Operands
+// two high-entropy channels, +1.2%.)  Products are exact and every sum is a
+// multiple of 1/8 below 2^19, so the f32 MFMA sums are exact, and so is every
+// marginal the per-pair test forms from them (R is put on the same grid): the
+// screen's f32 bound holds with R = sum_k |S w_k - w6_k| plus the reference's
+// rounding, in the same units (capi.hip fp6_prepare).  Padded sequences (N <=
+// k < NP) read as missing in both operands and weigh nothing because their
+// w6 is 0 (frag6_kernel).  Operands
 // come pre-packed from memory, per 64-site tile and 128-sequence block kb one
 // contiguous stage image:
-//   a6 [tile][kb][16-site block][channel in, minor][1536 B] (12 KB): lane l =
+//   a6 [tile][kb][16-site block][channel missing, minor][1536 B] (12 KB): lane l =
 //      site l & 15 of the block, sequences 32 (l >> 4) + j at bits 6j of six
 //      dwords, dwords 0-3 at 16 l, dwords 4-5 at 1024 + 8 l (one ds_read_b128
 //      and one ds_read_b64 fill the operand registers in place)
@@ -875,7 +896,9 @@ __global__ __launch_bounds__(64 * GroupShape<NPL>::kWaves, GroupShape<NPL>::kWgP
 // four per CU; per 128 sequences the waves LDS-DMA the row tile's A image and
 // the column tile's B image (16 1-KB pieces) into a double-buffered 16 KB
 // stage; wave w computes a rows 16w.. against the four column blocks (16
-// MFMAs per stage), then the screen epilogue.  Tile pairs: below.
+// MFMAs per stage), then the screen epilogue.  The tile's marginals (64 a
+// sites and 64 b sites x {M, m}, 1 KB; the tile pairs' 1.5 KB) are copied into
+// LDS beside the first stage and read after the loop.  Tile pairs: below.
 // (Round 5 measured the alternatives to fp4 B and removed them: 6-bit codes
 // read twice as e2m3 / e3m2, slower per MFMA and 1.5x the B bytes; a minor-bit
 // plane copied into LDS beside B, a larger stage; DESIGN.md Appendix A.)
@@ -910,7 +933,12 @@ __global__ __launch_bounds__(256) void frag6_kernel(const uint8_t *__restrict__ 
 #else
         const uint32_t c = k < NP ? row[k] : 0u, v = k < NP ? w6[k] : 0u;
 #endif
-        const uint32_t vi = (c & kCodeIn) ? v : 0u, vm = (c & (kCodeIn | kCodeMaj)) == kCodeIn ? v : 0u;
+        // channel 0: w6 [missing] (ai keeps the operand slot's name).  A
+        // padded sequence (N <= k < NP) has code 0 and so reads as missing in
+        // A and in B: it contributes nothing only because w6[k] = 0 there
+        // (fp6_prepare zero-fills the codes past N; fp6_marginals_kernel
+        // relies on the same), and past NP the operand is 0 outright.
+        const uint32_t vi = (c & kCodeIn) ? 0u : v, vm = (c & (kCodeIn | kCodeMaj)) == kCodeIn ? v : 0u;
         const uint32_t bit = 6 * j, d = bit >> 5, o = bit & 31;
         ai[d] |= vi << o;
         am[d] |= vm << o;
@@ -918,8 +946,10 @@ __global__ __launch_bounds__(256) void frag6_kernel(const uint8_t *__restrict__ 
             ai[d + 1] |= vi >> (32 - o);
             am[d + 1] |= vm >> (32 - o);
         }
-        // fp4 nibble j: 0, 2 (1.0: minor), 4 (2.0: major)
-        b[j >> 3] |= ((c & kCodeIn) ? ((c & kCodeMaj) ? 4u : 2u) : 0u) << (4 * (j & 7));
+        // fp4 nibble j: 4 (2.0: missing), 2 (1.0: minor), 0 (major)
+#ifndef WLD_EXP_ZERO_IMG
+        if (k < NP) b[j >> 3] |= ((c & kCodeIn) ? ((c & kCodeMaj) ? 0u : 2u) : 4u) << (4 * (j & 7));
+#endif
     }
     uint8_t *pa = a6 + tk * kF6AStage + blk * kF6ABytes, *pm = pa + 1536;
     uint8_t *pb = b6 + tk * kF6BStage + blk * kF6BBytes;
@@ -928,6 +958,39 @@ __global__ __launch_bounds__(256) void frag6_kernel(const uint8_t *__restrict__ 
     *reinterpret_cast<uint4 *>(pm + 16 * lane) = make_uint4(am[0], am[1], am[2], am[3]);
     *reinterpret_cast<uint2 *>(pm + 1024 + 8 * lane) = make_uint2(am[4], am[5]);
     *reinterpret_cast<uint4 *>(pb + 16 * lane) = make_uint4(b[0], b[1], b[2], b[3]);
+}
+
+// The complement coding's per-site marginals (pair_common.hpp f6c_direct):
+// marg[2 s] = M_s = sum_k w6_k [s missing], marg[2 s + 1] = m_s = sum_k w6_k
+// [s minor], one wave per site, summed as integers (8 x the e2m3 value, <= 60
+// per sequence, NP <= 16384: below 2^20) and converted once, so both are the
+// exact multiples of 1/8 the images' products sum to.
+__global__ __launch_bounds__(256) void fp6_marginals_kernel(const uint8_t *__restrict__ codes,
+                                                             const uint8_t *__restrict__ w6, uint32_t LP, uint32_t NP,
+                                                             float *__restrict__ marg) {
+    const uint32_t site = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (site >= LP) return;  // (uniform per wave)
+    const uint8_t *row = codes + (size_t)site * NP;
+    uint32_t miss = 0, minor = 0;
+    for (uint32_t k = lane; k < NP; k += 64) {
+#ifdef WLD_EXP_ZERO_IMG
+        const uint32_t c = kCodeIn | kCodeMaj, q = 0u;
+#else
+        const uint32_t c = row[k], q = w6[k];
+#endif
+        const uint32_t e = q >> 3, v8 = e ? (8u + (q & 7u)) << (e - 1) : q;  // 8 x the e2m3 value
+        miss += (c & kCodeIn) ? 0u : v8;
+        minor += (c & (kCodeIn | kCodeMaj)) == kCodeIn ? v8 : 0u;
+    }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+        miss += __shfl_xor(miss, d);
+        minor += __shfl_xor(minor, d);
+    }
+    if (lane == 0) {
+        marg[2 * (size_t)site] = 0.125f * (float)miss;
+        marg[2 * (size_t)site + 1] = 0.125f * (float)minor;
+    }
 }
 
 namespace {
@@ -945,8 +1008,8 @@ __device__ __forceinline__ v8i f6_ldb(const uint8_t *p, uint32_t lane) {
     const uint4 x = *reinterpret_cast<const uint4 *>(p + 16 * lane);
     return v8i{(int)x.x, (int)x.y, (int)x.z, (int)x.w, 0, 0, 0, 0};
 }
-// one B block's four MFMAs against the wave's A channels (in: ai, minor: am):
-// acc[channel_a][0 / 1] = X / Y (B raw: minor + 2 major, B's minor bit)
+// one B block's four MFMAs against the wave's A channels (missing: ai, minor: am):
+// acc[channel_a][0 / 1] = X / Y (B raw: 2 missing + minor, B's minor bit)
 // Zero scale operands: the compiler selects the unscaled
 // v_mfma_f32_16x16x128_f8f6f4 (no per-block scales), whose sums equal the
 // unit-scaled (E8M0 0x7F) v_mfma_scale form's bit for bit and which issues
@@ -958,7 +1021,7 @@ __device__ __forceinline__ v4f f6_mfma(const v8i &a, const v8i &b, const v4f &c)
 }
 __device__ __forceinline__ void f6_block_mfma(v4f (&acc)[2][2], const v8i &ai, const v8i &am, const v8i &b) {
     constexpr int kOne = 0;
-    constexpr int kMinor = 0x22222222;  // fp4 1.0 (minor) nibbles; 2.0 (major) is 0x4
+    constexpr int kMinor = 0x22222222;  // fp4 1.0 (minor) nibbles; 2.0 (missing) is 0x4
     const v8i bmin = {b[0] & kMinor, b[1] & kMinor, b[2] & kMinor, b[3] & kMinor, 0, 0, 0, 0};
     acc[0][0] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(ai, b, acc[0][0], 2, 4, 0, kOne, 0, kOne);
     acc[0][1] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(ai, bmin, acc[0][1], 2, 4, 0, kOne, 0, kOne);
@@ -1019,17 +1082,49 @@ struct F6Epi {
         return mk;
     }
 };
+// The complement coding's accumulators of one wave's 16 rows x 64 columns
+// (acc[n] = b block n; the wave is row block wq of its tile) turned in place
+// into the direct coding's X0, Y0, X1, Y1, which F6Epi takes: exact, so bit
+// for bit what MFMAs on "in" / minor x minor + 2 major images would have
+// summed (pair_common.hpp f6c_direct).  sA / sB: the row tile's and the
+// column tile's 64 x {M, m} in LDS (staged with the entry's first stage, read
+// only here: 12 sites per lane, no register held across the stage loop).
+__device__ __forceinline__ void f6c_rebuild(v4f (&acc)[4][2][2], const float2 *sA, const float2 *sB, uint32_t wq,
+                                            uint32_t lane, float W6) {
+    float col[4], mb[4];
+#pragma unroll
+    for (int n = 0; n < 4; ++n) {
+        const float2 b = sB[(lane & 15) + 16 * n];
+        col[n] = f6c_col_term(b.x, b.y);
+        mb[n] = b.y;
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const float2 a = sA[16 * wq + 4 * (lane >> 4) + e];
+        const float row = f6c_row_term(W6, a.x), ma2 = 2.0f * a.y;
+#pragma unroll
+        for (int n = 0; n < 4; ++n) {
+            float x0 = acc[n][0][0][e], y0 = acc[n][0][1][e], x1 = acc[n][1][0][e];
+            f6c_direct(x0, y0, x1, row, col[n], ma2, mb[n]);
+            acc[n][0][0][e] = x0;
+            acc[n][0][1][e] = y0;
+            acc[n][1][0][e] = x1;
+        }
+    }
+}
 }  // namespace
 
 // one 64x64 tile per 4-wave workgroup, four per CU (tile lists past 2^15
 // tile columns, and WLD_OPT_FP6_PAIRS_MIN_TILES's smaller lists)
 __global__ __launch_bounds__(256, 4) void pair_fp6_screen_kernel(const uint8_t *__restrict__ a6,
                                                                   const uint8_t *__restrict__ b6,
+                                                                  const float2 *__restrict__ marg, float W6,
                                                                   const uint64_t *__restrict__ ok_bits,
                                                                   const uint32_t *__restrict__ tiles, uint32_t n_tiles,
                                                                   uint32_t NK, uint32_t L, uint32_t n_chunk_rows,
                                                                   float thr, OrderArgs o, ScreenArgs sc) {
     __shared__ __attribute__((aligned(16))) uint8_t smem[2 * kF6Stage];
+    __shared__ float2 sMarg[2 * kTile];  // {M, m} of the row tile's sites, then the column tile's
     __shared__ unsigned long long sMask;
     __shared__ uint32_t sBail;
     if (!sc.probe && blockIdx.x == 0 && threadIdx.x == 0) *sc.cand_work = 0u;  // for the launch after it
@@ -1050,6 +1145,9 @@ __global__ __launch_bounds__(256, 4) void pair_fp6_screen_kernel(const uint8_t *
             glds16_s(p < kF6AStage / 1024 ? a + p * 1024 : b + (p - kF6AStage / 1024) * kF6BBytes, lane16, gb + p * 1024);
     };
     issue(0, 0);
+    // the tile's marginals, in flight with the first stage (published by its
+    // barrier, read by the epilogue)
+    if (tid < 2 * kTile) sMarg[tid] = marg[(tid < kTile ? ta : tb) * kTile + (tid & (kTile - 1))];
     // the give-up test: read by thread 0 while the first stage is in flight,
     // published to the other waves by the first stage barrier (one decision
     // for the workgroup; the LDS write completes before this wave reaches
@@ -1066,7 +1164,7 @@ __global__ __launch_bounds__(256, 4) void pair_fp6_screen_kernel(const uint8_t *
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     const uint64_t okA = ok_bits[ta], okB = ok_bits[tb];
-    v4f acc[4][2][2];  // [b block n][channel_a in / minor][X, Y]
+    v4f acc[4][2][2];  // [b block n][channel_a missing / minor][X, Y]
 #pragma unroll
     for (int n = 0; n < 4; ++n)
 #pragma unroll
@@ -1094,6 +1192,7 @@ __global__ __launch_bounds__(256, 4) void pair_fp6_screen_kernel(const uint8_t *
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // reads of this buffer done before the next barrier
         buf ^= 1;
     }
+    f6c_rebuild(acc, sMarg, sMarg + kTile, wave, lane, W6);
     const F6Epi ep{ta, tb, wave, lane, okA, okB, 2.0f * sc.Rf, thr * (1.0f - 0x1p-7f), sc.E, sc.mloc};
     const bool cand = ep.any(acc);
     if (sc.probe) {  // the sample run: count, decide nothing
@@ -1146,10 +1245,12 @@ extern "C" int wld_debug_f6_clock(unsigned long long *out) {
 }
 #endif
 __global__ __launch_bounds__(256, 3) void pair_fp6_screen2w_kernel(
-    const uint8_t *__restrict__ a6, const uint8_t *__restrict__ b6, const uint64_t *__restrict__ ok_bits,
+    const uint8_t *__restrict__ a6, const uint8_t *__restrict__ b6, const float2 *__restrict__ marg, float W6,
+    const uint64_t *__restrict__ ok_bits,
     const uint32_t *__restrict__ pairs, uint32_t n_pairs, uint32_t NK, uint32_t L, uint32_t n_chunk_rows, float thr,
     OrderArgs o, ScreenArgs sc) {
     __shared__ __attribute__((aligned(16))) uint8_t smem[2 * kF6PStage];
+    __shared__ float2 sMarg[3 * kTile];  // {M, m} of the row tile's sites, then each half's column tile's
     __shared__ unsigned long long sMask[2];
     __shared__ uint32_t sBail, sCand[2];
     if (!sc.probe && blockIdx.x == 0 && threadIdx.x == 0) *sc.cand_work = 0u;  // for the launch after it
@@ -1192,6 +1293,13 @@ __global__ __launch_bounds__(256, 3) void pair_fp6_screen2w_kernel(
         const uint32_t ta = entry >> 16, tb0 = entry & 0x7FFFu;
         const bool single = (entry & kF6Single) != 0, idle = single && half;  // (uniform per wave)
         const uint32_t tb = tb0 + (idle ? 0u : half);
+        // the entry's marginals (1.5 KB), in flight with the first stage,
+        // published by its barrier and read by the epilogue alone (a single
+        // entry's second column tile is its first, as its B image)
+        if (tid < 3 * kTile) {
+            const uint32_t t = tid < kTile ? ta : tb0 + ((tid >= 2 * kTile && !single) ? 1u : 0u);
+            sMarg[tid] = marg[t * kTile + (tid & (kTile - 1))];
+        }
         if (tid == 0) {  // the give-up test (as the single-tile kernel)
             uint32_t v = 0;
             if (sc.bail) {
@@ -1244,7 +1352,7 @@ __global__ __launch_bounds__(256, 3) void pair_fp6_screen2w_kernel(
 #pragma unroll
             for (int n = 0; n < 4; ++n) {
                 v8i &b = bs[n & 1];
-                constexpr int kMinor = 0x22222222;  // fp4 1.0 (minor) nibbles; 2.0 (major) is 0x4
+                constexpr int kMinor = 0x22222222;  // fp4 1.0 (minor) nibbles; 2.0 (missing) is 0x4
                 acc[0][n][0][0] = f6_mfma(ai0, b, kFirst ? kZero : acc[0][n][0][0]);
                 acc[0][n][1][0] = f6_mfma(am0, b, kFirst ? kZero : acc[0][n][1][0]);
                 acc[1][n][0][0] = f6_mfma(ai1, b, kFirst ? kZero : acc[1][n][0][0]);
@@ -1276,6 +1384,10 @@ __global__ __launch_bounds__(256, 3) void pair_fp6_screen2w_kernel(
 #endif
         const F6Epi ep0{ta, tb, 2 * rp, lane, okA, okB, 2.0f * sc.Rf, thr * (1.0f - 0x1p-7f), sc.E, sc.mloc};
         const F6Epi ep1{ta, tb, 2 * rp + 1, lane, okA, okB, 2.0f * sc.Rf, thr * (1.0f - 0x1p-7f), sc.E, sc.mloc};
+        if (!idle) {
+            f6c_rebuild(acc[0], sMarg, sMarg + kTile * (1 + half), 2 * rp, lane, W6);
+            f6c_rebuild(acc[1], sMarg, sMarg + kTile * (1 + half), 2 * rp + 1, lane, W6);
+        }
         const bool cand = !idle && (ep0.any(acc[0]) || ep1.any(acc[1]));
         if (cand) sCand[half] = 1u;  // (benign race: every writer stores 1)
         __syncthreads();
@@ -1478,10 +1590,12 @@ __global__ __launch_bounds__(256, 3) void pair_i8_screen2w_kernel(
 }
 
 void launch_frag6(const uint8_t *codes, const uint8_t *w6, size_t LP, size_t NP, uint8_t *a6, uint8_t *b6,
-                  hipStream_t s) {
+                  float *marg, hipStream_t s) {
     const size_t n = LP / 16 * ((NP + 127) / 128) * 64;
     hipLaunchKernelGGL(frag6_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, codes, w6, (uint32_t)LP,
                        (uint32_t)NP, a6, b6);
+    hipLaunchKernelGGL(fp6_marginals_kernel, dim3((unsigned)((LP + 3) / 4)), dim3(256), 0, s, codes, w6, (uint32_t)LP,
+                       (uint32_t)NP, marg);
 }
 
 // Site-major variant (one tile per workgroup, codes read straight into
@@ -1639,12 +1753,14 @@ void launch_fp6_screen(const MfmaLaunch &m, const uint64_t *ok_bits, const Order
     if (m.f6_pairs) {
         // (a tile group per workgroup, the XCD-ordered group list)
         hipLaunchKernelGGL(pair_fp6_screen2w_kernel, dim3((m.f6_n_pairs + stride - 1) / stride), dim3(256), 0, s,
-                           m.fp6->a6, m.fp6->b6, ok_bits, m.f6_pairs, m.f6_n_pairs, m.fp6->NK, m.L, m.n_chunk_rows,
+                           m.fp6->a6, m.fp6->b6, reinterpret_cast<const float2 *>(m.fp6->marg), m.fp6->W6, ok_bits,
+                           m.f6_pairs, m.f6_n_pairs, m.fp6->NK, m.L, m.n_chunk_rows,
                            m.thr, o, sc);
     } else {
         // (one tile per workgroup, the XCD-ordered list)
         hipLaunchKernelGGL(pair_fp6_screen_kernel, dim3((m.n_tiles + stride - 1) / stride), dim3(256), 0, s,
-                           m.fp6->a6, m.fp6->b6, ok_bits, m.tiles, m.n_tiles, m.fp6->NK, m.L, m.n_chunk_rows, m.thr,
+                           m.fp6->a6, m.fp6->b6, reinterpret_cast<const float2 *>(m.fp6->marg), m.fp6->W6, ok_bits,
+                           m.tiles, m.n_tiles, m.fp6->NK, m.L, m.n_chunk_rows, m.thr,
                            o, sc);
     }
 }
