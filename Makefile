@@ -18,7 +18,7 @@ HIP_SRCS := $(CSRC)/encode.hip $(CSRC)/prepass.hip $(CSRC)/pair_valu.hip $(CSRC)
 CXX_SRCS := $(CSRC)/host.cpp
 HDRS := include/weightedld.h $(CSRC)/common.hpp $(CSRC)/kernels.hpp $(CSRC)/pair_common.hpp $(CSRC)/tile_order.hpp \
         $(CSRC)/window_plan.hpp $(CSRC)/pair_valu_kernel.hpp $(CSRC)/summary_plan.hpp $(CSRC)/prune_plan.hpp \
-        $(CSRC)/screen_policy.hpp $(CSRC)/fp6_scale.hpp
+        $(CSRC)/screen_policy.hpp $(CSRC)/fp6_scale.hpp $(CSRC)/fp6_pack.hpp
 OBJDIR := build/obj
 OBJS := $(patsubst $(CSRC)/%.hip,$(OBJDIR)/%.o,$(HIP_SRCS)) $(patsubst $(CSRC)/%.cpp,$(OBJDIR)/%.o,$(CXX_SRCS))
 

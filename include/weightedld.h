@@ -239,6 +239,15 @@ int wld_set_kernel(wld_ctx *ctx, int kernel);
  *                      the codes) pre-multiplied once per load (3 bytes per
  *                      site and sequence); 0: one tile per workgroup, the
  *                      operands formed per stage.  Same rows.
+ *   WLD_OPT_FP6_A4     1 (default, auto): where every rounded weight of a load
+ *                      is also an fp4 (e2m1) value (0, 0.5, 1, 1.5, 2, 3, 4, 6:
+ *                      unit weights, Henikoff weights of a large alignment) the
+ *                      fp6 screen's A operand image is built as fp4, two thirds
+ *                      of the bytes and four operand registers instead of six
+ *                      at the same MFMA rate; 0: always fp6.  Every product is
+ *                      exact either way: same sums, candidates and rows.
+ *                      Setting it discards the built images (the next run that
+ *                      may screen on fp6 rebuilds them).
  *   WLD_OPT_TEST_GUARD 0 (default); 1 (tests only): before each candidate
  *                      launch the last candidate bucket's count is set one
  *                      past its capacity, so the launch meets an entry outside
@@ -261,6 +270,7 @@ int wld_set_kernel(wld_ctx *ctx, int kernel);
 #define WLD_OPT_TEST_GUARD 14
 #define WLD_OPT_FP6_PAIRS_MIN_TILES 15
 #define WLD_OPT_I8_PAIRS 16
+#define WLD_OPT_FP6_A4 17
 int wld_set_option(wld_ctx *ctx, int option, int64_t value);
 int wld_get_option(wld_ctx *ctx, int option, int64_t *value);
 
@@ -494,8 +504,16 @@ typedef struct {
                                  host made up from the chunk pair counts because the pass's log lacked
                                  their entries once it had completed; 0 unless the kernels' chunk
                                  accounting lost a count (the tests assert 0) */
+    int fp6_a4;              /* 1: the pass screened on fp6 (screen_fp6 == 1) with the fp4 A image (WLD_OPT_FP6_A4) */
 } wld_run_stats;
 int wld_last_stats(wld_ctx *ctx, wld_run_stats *out);
+/* The fp6 screen's weight codes of the loaded set (tests, diagnostics): the
+ * e2m3 code of every sequence's rounded weight into codes[n_seqs], and
+ * *fits_fp4 = 1 when every one is also an fp4 (e2m1) value, which is when
+ * WLD_OPT_FP6_A4 builds the A image as fp4.  WLD_E_STATE where the load has no
+ * fp6 operands (negative weights, more than 16,384 sequences, the VALU kernel,
+ * or WLD_OPT_SCREEN_FP6 0 and no run since).  Single-device contexts. */
+int wld_fp6_weight_codes(wld_ctx *ctx, uint8_t *codes, int *fits_fp4);
 
 /* ---- LD summaries: per-site LD scores and r2 decay by distance (not in the
  * reference; what LD-decay curves and LD-score tools need from every pair) ----

@@ -26,7 +26,7 @@ KERNEL_AUTO, KERNEL_VALU, KERNEL_MFMA = 0, 1, 2
 # wld_set_option ids (include/weightedld.h)
 OPTIONS = {"prefilter": 1, "screen": 2, "tile_order": 3, "all_planes": 4, "mfma_layout": 5, "valu_plain": 6,
            "staging_rows": 7, "host_batch_pairs": 8, "ref_sums": 11, "fused_scan": 12, "screen_fp6": 13,
-           "test_guard": 14, "fp6_pairs_min_tiles": 15, "i8_pairs": 16}
+           "test_guard": 14, "fp6_pairs_min_tiles": 15, "i8_pairs": 16, "fp6_a4": 17}
 
 
 class WldError(RuntimeError):
@@ -68,6 +68,7 @@ class RunStats(ctypes.Structure):
         ("screen_fp6", ctypes.c_int),
         ("fp6_sampled", ctypes.c_int),
         ("progress_filled", ctypes.c_uint64),
+        ("fp6_a4", ctypes.c_int),
     ]
 
 
@@ -174,6 +175,7 @@ SIGNATURES = {
     "wld_rows_copy_device": (_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "wld_dense": (_int, [_vp, _f32p, _f32p, _f32p, _u8p]),
     "wld_last_stats": (_int, [_vp, ctypes.POINTER(RunStats)]),
+    "wld_fp6_weight_codes": (_int, [_vp, _u8p, ctypes.POINTER(_int)]),
     "wld_run_summary": (_int, [_vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint32,
                                ctypes.POINTER(Summary)]),
     "wld_summary_free": (None, [ctypes.POINTER(Summary)]),

@@ -321,13 +321,20 @@ class Context:
     def set_option(self, name, value):
         """wld_set_option: name is a key of OPTIONS ("prefilter", "screen",
         "tile_order", "all_planes", "mfma_layout", "valu_plain", "staging_rows",
-        "host_batch_pairs", "ref_sums", "fused_scan"); only "ref_sums" changes a result."""
+        "host_batch_pairs", "ref_sums", "fused_scan", "screen_fp6", "fp6_a4", ...); only "ref_sums" changes a result."""
         check(lib().wld_set_option(self._h, OPTIONS[name], int(value)), "wld_set_option")
 
     def get_option(self, name):
         v = ctypes.c_int64()
         check(lib().wld_get_option(self._h, OPTIONS[name], ctypes.byref(v)), "wld_get_option")
         return int(v.value)
+
+    def fp6_weight_codes(self, n_seqs):
+        """(e2m3 codes of the loaded set's n_seqs rounded weights, whether all
+        are e2m1 values: the "fp6_a4" image's condition) (wld_fp6_weight_codes)."""
+        codes, fits = np.zeros(n_seqs, dtype=np.uint8), ctypes.c_int()
+        check(lib().wld_fp6_weight_codes(self._h, _p(codes, ctypes.c_uint8), ctypes.byref(fits)), "wld_fp6_weight_codes")
+        return codes, bool(fits.value)
 
     def set_window(self, max_distance=None, max_sites=None):
         """wld_set_window: later runs compute only the pairs a < b with

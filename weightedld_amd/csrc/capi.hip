@@ -131,6 +131,7 @@ struct wld_ctx {
     int64_t opt_fp6_pairs_min = 0;  // (tile pairs at every list size: profiles/r05ar/)
     bool opt_i8_pairs = true;    // WLD_OPT_I8_PAIRS: the i8 screen on tile pairs (pre-multiplied images)
     int opt_fp6 = 1;             // WLD_OPT_SCREEN_FP6: 0 off, 1 auto, 2 whenever it applies, 3 auto without the sample run
+    bool opt_fp6_a4 = true;      // WLD_OPT_FP6_A4: the fp6 screen's A image as fp4 where the weight codes fit e2m1
     bool opt_ref_sums = true;  // WLD_OPT_REF_SUMS: lib.rs's own f32 summation order (default)
     uint64_t opt_staging_rows = 1ull << 25, opt_host_batch_pairs = 1ull << 31;
 
@@ -141,6 +142,7 @@ struct wld_ctx {
     DevBuf rcodes, rw;       // WLD_OPT_REF_SUMS: codes and weights in lane-class order (ref_layout_kernel)
     // the fp6 screen (fp6_prepare): weight codes, packed operands, constants
     DevBuf w6, f6a, f6b, f6marg;  // (f6marg: the per-site marginals of the complement-coded images)
+    DevBuf w4;                    // the weights' e2m1 codes, where the A image is fp4 (Fp6Screen::a4)
     Fp6Screen f6{};
     // the i8 one-plane screen's pre-multiplied images (i8img_prepare, at the
     // first pass that screens on i8 with them)
@@ -237,7 +239,7 @@ struct wld_ctx {
         // work queued on a borrowed stream (wld_set_stream) may still use the
         // buffers: it completes before they are freed
         if (stream && stream != own_stream) (void)hipStreamSynchronize(stream);
-        DevBuf *all[] = {&keep, &htab, &htab_kept, &site_index, &raw, &wraw, &codes, &w_pad, &wstats, &site_ok, &site_map, &planes, &frag, &rcodes, &rw, &w6, &f6a, &f6b, &f6marg, &i8a, &i8b, &tiles, &cand, &f6_pairs, &fp6_probe_buf,
+        DevBuf *all[] = {&keep, &htab, &htab_kept, &site_index, &raw, &wraw, &codes, &w_pad, &wstats, &site_ok, &site_map, &planes, &frag, &rcodes, &rw, &w6, &w4, &f6a, &f6b, &f6marg, &i8a, &i8b, &tiles, &cand, &f6_pairs, &fp6_probe_buf,
                          &seg_cnt, &seg_off, &chunk_total, &chunk_base, &counters, &chunk_left, &prog_n, &win_hi, &win_pairs, &sum_buf, &st_a, &st_b, &st_d,
                          &st_dp, &st_r2, &out_a, &out_b, &out_d, &out_dp, &out_r2};
         for (DevBuf *b : all) release(*b);
@@ -310,7 +312,11 @@ double ref_extra_residual(const wld_ctx *c);
 // between the screen's sums and the sums the candidate launch computes: the
 // rounding, plus the fixed point's 0.5 per sequence (exact mode) and lib.rs's
 // f32 summation (9 gamma_m sum w, ref_extra_residual) — both added, so one
-// R serves either mode.
+// R serves either mode.  Where every weight code is also an e2m1 value (unit
+// weights, Henikoff weights of a large alignment, dyadic sets: fp6_scale.hpp
+// fp6_codes_fit_fp4) and WLD_OPT_FP6_A4 is on, the A image is built as fp4
+// nibbles of the same values: two thirds of the bytes, the same sums, one
+// image per load that every fp6 kernel reads.
 // Built at load unless WLD_OPT_SCREEN_FP6 is 0, else on the first run that
 // may screen on fp6 after the option is set.
 int fp6_prepare(wld_ctx *c) {
@@ -345,14 +351,22 @@ int fp6_prepare(wld_ctx *c) {
         if (c->wst.plane_mask >> p & 1) top = p;
     const double r8 = (top > 0 ? (double)c->wst.resid[top - 1] : 0.0) + ref_extra_residual(c);
     c->i8_rel = r8 / std::max(std::ldexp((double)c->wst.dsum[top], 8 * (int)top), 1e-300);
+    c->f6.a4 = c->opt_fp6_a4 && fp6_codes_fit_fp4(codes.data(), c->N);
     WLD_TRY(ensure(c->w6, c->NP));
-    WLD_TRY(ensure(c->f6a, fp6_a_bytes(c->LP, c->NP)));
+    WLD_TRY(ensure(c->f6a, fp6_a_bytes(c->LP, c->NP, c->f6.a4)));
     WLD_TRY(ensure(c->f6b, fp6_b_bytes(c->LP, c->NP)));
     WLD_TRY(ensure(c->f6marg, 2 * c->LP * sizeof(float)));
     // (codes: zero past N, which the complement coding needs, pair_mfma.hip frag6_kernel)
     HIP_TRY(hipMemcpyAsync(c->w6.p, codes.data(), c->NP, hipMemcpyHostToDevice, c->stream));
-    launch_frag6(ptr<uint8_t>(c->codes), ptr<uint8_t>(c->w6), c->LP, c->NP, ptr<uint8_t>(c->f6a), ptr<uint8_t>(c->f6b),
-                 ptr<float>(c->f6marg), c->stream);
+    std::vector<uint8_t> codes4;  // (outlives the copy: the stream is synchronized below)
+    if (c->f6.a4) {
+        codes4.resize(c->NP);
+        for (size_t k = 0; k < c->NP; ++k) codes4[k] = (uint8_t)fp6_to_fp4_code(codes[k]);
+        WLD_TRY(ensure(c->w4, c->NP));
+        HIP_TRY(hipMemcpyAsync(c->w4.p, codes4.data(), c->NP, hipMemcpyHostToDevice, c->stream));
+    }
+    launch_frag6(ptr<uint8_t>(c->codes), ptr<uint8_t>(c->w6), ptr<uint8_t>(c->f6.a4 ? c->w4 : c->w6), c->f6.a4, c->LP,
+                 c->NP, ptr<uint8_t>(c->f6a), ptr<uint8_t>(c->f6b), ptr<float>(c->f6marg), c->stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->f6.a6 = ptr<uint8_t>(c->f6a);
@@ -980,8 +994,25 @@ int wld_set_option(wld_ctx *c, int option, int64_t value) {
             c->opt_fp6 = (int)value;
             c->learned.reset();  // another screen's break-even
             break;
+        case WLD_OPT_FP6_A4:
+            c->opt_fp6_a4 = value != 0;
+            // the A image's format may change: rebuilt by the next run that may screen on fp6
+            c->fp6_ok = c->fp6_better = c->fp6_tried = false;
+            break;
         default: return fail(WLD_E_ARG, "unknown option %d", option);
     }
+    return WLD_OK;
+}
+
+int wld_fp6_weight_codes(wld_ctx *c, uint8_t *codes, int *fits_fp4) {
+    if (!c || !codes || !fits_fp4) return fail(WLD_E_ARG, "null argument");
+    if (!c->members.empty()) return fail(WLD_E_ARG, "wld_fp6_weight_codes takes a single-device context");
+    if (c->pend.active) return fail(WLD_E_STATE, "wld_fp6_weight_codes during a run");
+    if (!c->loaded || !c->fp6_ok) return fail(WLD_E_STATE, "the loaded set has no fp6 operands");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipMemcpyAsync(codes, c->w6.p, c->N, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    *fits_fp4 = fp6_codes_fit_fp4(codes, c->N) ? 1 : 0;
     return WLD_OK;
 }
 
@@ -1079,6 +1110,7 @@ int wld_get_option(wld_ctx *c, int option, int64_t *value) {
         case WLD_OPT_FP6_PAIRS_MIN_TILES: *value = c->opt_fp6_pairs_min; break;
         case WLD_OPT_SCREEN_FP6: *value = c->opt_fp6; break;
         case WLD_OPT_I8_PAIRS: *value = c->opt_i8_pairs; break;
+        case WLD_OPT_FP6_A4: *value = c->opt_fp6_a4; break;
         default: return fail(WLD_E_ARG, "unknown option %d", option);
     }
     return WLD_OK;
@@ -1616,6 +1648,7 @@ int run_complete(wld_ctx *c, uint64_t *n_rows) {
     c->stats.screened = screen_policy::stat_screened(route);
     c->stats.screen_fp6 = screen_policy::stat_screen_fp6(route) ? 1 : abandoned ? 2 : 0;
     c->stats.fp6_sampled = c->fp6_sampled ? 1 : 0;
+    c->stats.fp6_a4 = c->stats.screen_fp6 == 1 && c->f6.a4 ? 1 : 0;
     c->stats.candidate_pairs = cand_pairs ? h[0] : 0;
     // auto: what this pass's counts teach the policy (screen_policy.hpp: the break-evens)
     screen_policy::learn(c->learned, screen_policy::Outcome{route, r.thr, false, h[2], c->n_tiles, h[0], r.pairs});

@@ -81,4 +81,26 @@ inline Fp6ScaleCost fp6_choose_scale(const float *w, size_t N, double wmax) {
     return *best;
 }
 
+// e2m3 codes whose value is also an e2m1 (fp4) value: mantissa bits 1-0 clear,
+// that is 0, 4, 8, 12, 16, 20, 24, 28 for 0, 0.5, 1, 1.5, 2, 3, 4, 6.  Both
+// formats have two exponent bits at bias 1, so the e2m1 code of the same
+// value is the e2m3 code without those two bits.  -1: no e2m1 value.
+inline int fp6_to_fp4_code(uint32_t c6) { return c6 < 32u && (c6 & 3u) == 0u ? (int)(c6 >> 2) : -1; }
+// The value of an e2m3 / e2m1 code (sign 0).
+inline double fp6_value(uint32_t c6) {
+    const uint32_t e = c6 >> 3 & 3u, m = c6 & 7u;
+    return e ? std::ldexp(1.0 + m / 8.0, (int)e - 1) : m / 8.0;
+}
+inline double fp4_value(uint32_t c4) {
+    const uint32_t e = c4 >> 1 & 3u, m = c4 & 1u;
+    return e ? std::ldexp(1.0 + m / 2.0, (int)e - 1) : m / 2.0;
+}
+// Whether a load's N weight codes all fit e2m1: its A image can then be fp4
+// nibbles (pair_mfma.hip, WLD_OPT_FP6_A4), every product and sum unchanged.
+inline bool fp6_codes_fit_fp4(const uint8_t *w6, size_t N) {
+    for (size_t k = 0; k < N; ++k)
+        if (fp6_to_fp4_code(w6[k]) < 0) return false;
+    return true;
+}
+
 }  // namespace wld

@@ -46,6 +46,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "fp6_pack.hpp"
 #include "pair_common.hpp"
 
 
@@ -837,7 +838,7 @@ __global__ __launch_bounds__(64 * GroupShape<NPL>::kWaves, GroupShape<NPL>::kWgP
     }
 }
 
-// ---- fp6 screen (block-scaled MFMA, twice the i8 rate) ----------------------
+// ---- fp6 screen (f8f6f4 MFMA without block scales, twice the i8 rate) -------
 //
 // The one-plane screen's sums from v_mfma_f32_16x16x128_f8f6f4 with fp6 (e2m3)
 // A operands and fp4 (e2m1) B operands, no block scales: 128 sequences per
@@ -892,6 +893,21 @@ __global__ __launch_bounds__(64 * GroupShape<NPL>::kWaves, GroupShape<NPL>::kWgP
 //      and one ds_read_b64 fill the operand registers in place)
 //   b6 [tile][kb][16-site block][1024 B]: the b codes' nibbles, sequences
 //      32 (l >> 4) + j at bits 4j of four dwords at 16 l (4 KB)
+// Where every w6 of a load is also an e2m1 value (0, 0.5, 1, 1.5, 2, 3, 4, 6:
+// unit weights, Henikoff weights of a large alignment, which fp6_scale.hpp
+// puts on 4.0; capi.hip fp6_prepare decides once per load, WLD_OPT_FP6_A4) the
+// A image holds fp4 nibbles of the same values, laid out as a B block per
+// channel, and the kernels' kA4 instantiations multiply fp4 x fp4 (cbsz 4) at
+// the same rate: every product is exact in either format, so accumulators,
+// verdicts and candidate sets are bit for bit the fp6 image's.
+//   a6 (fp4) [tile][kb][16-site block][channel missing, minor][1024 B] (8 KB):
+//      sequences 32 (l >> 4) + j at bits 4j of four dwords at 16 l (one
+//      ds_read_b128 per operand)
+// Per tile-pair stage that is 16 KB instead of 20 (four LDS-DMA pieces per
+// wave instead of five), 8 LDS read instructions per wave instead of 12, 16
+// A operand registers instead of 24 and 8 operand dwords per MFMA instead of
+// 10 (round 10: C4 screen launch -5.0%, bench step -6.5%, C5 -7.2%;
+// profiles/r10a/).
 // Single tiles (pair_fp6_screen_kernel): one 64x64 tile per 4-wave workgroup,
 // four per CU; per 128 sequences the waves LDS-DMA the row tile's A image and
 // the column tile's B image (16 1-KB pieces) into a double-buffered 16 KB
@@ -902,21 +918,34 @@ __global__ __launch_bounds__(64 * GroupShape<NPL>::kWaves, GroupShape<NPL>::kWgP
 // (Round 5 measured the alternatives to fp4 B and removed them: 6-bit codes
 // read twice as e2m3 / e3m2, slower per MFMA and 1.5x the B bytes; a minor-bit
 // plane copied into LDS beside B, a larger stage; DESIGN.md Appendix A.)
-constexpr int kF6ABytes = 3072;                         // per 16-site block: A, two channels
-constexpr int kF6BBytes = 1024;                         // ... and B (fp4 codes)
-constexpr int kF6AStage = 4 * kF6ABytes;                // a tile's A image per 128 sequences
-constexpr int kF6BStage = 4 * kF6BBytes;                // ... and B image
-constexpr int kF6Stage = kF6AStage + kF6BStage;
+constexpr int kF6BBytes = 1024;                         // per 16-site block: B (fp4 codes)
+constexpr int kF6BStage = 4 * kF6BBytes;                // a tile's B image per 128 sequences
+// The A image's format (kA4: fp4 nibbles, a load whose weight codes all fit
+// e2m1; else fp6) and the stage constants that follow from it.
+template <bool kA4>
+struct F6Fmt {
+    static constexpr int kChan = kA4 ? 1024 : 1536;     // per 16-site block: one A channel
+    static constexpr int kABytes = 2 * kChan;           // ... and both
+    static constexpr int kAStage = 4 * kABytes;         // a tile's A image per 128 sequences
+    static constexpr int kStage = kAStage + kF6BStage;  // a single tile's stage
+    static constexpr int kPStage = kAStage + 2 * kF6BStage;  // a tile pair's
+    static constexpr int kCbsz = kA4 ? 4 : 2;           // the MFMA's A format: fp4 (e2m1) / fp6 (e2m3)
+};
 typedef int v8i __attribute__((ext_vector_type(8)));
 typedef float v4f __attribute__((ext_vector_type(4)));
 
-size_t fp6_a_bytes(size_t LP, size_t NP) { return LP / 64 * ((NP + 127) / 128) * kF6AStage; }
+size_t fp6_a_bytes(size_t LP, size_t NP, bool a4) {
+    return LP / 64 * ((NP + 127) / 128) * (a4 ? F6Fmt<true>::kAStage : F6Fmt<false>::kAStage);
+}
 size_t fp6_b_bytes(size_t LP, size_t NP) { return LP / 64 * ((NP + 127) / 128) * kF6BStage; }
 
-// one thread per (64-site tile, 128-sequence block, 16-site block, lane)
-__global__ __launch_bounds__(256) void frag6_kernel(const uint8_t *__restrict__ codes, const uint8_t *__restrict__ w6,
+// one thread per (64-site tile, 128-sequence block, 16-site block, lane); wa:
+// the A image's weight codes (e2m3, or e2m1 for the fp4 image), 0 past N
+template <bool kA4>
+__global__ __launch_bounds__(256) void frag6_kernel(const uint8_t *__restrict__ codes, const uint8_t *__restrict__ wa,
                                                      uint32_t LP, uint32_t NP, uint8_t *__restrict__ a6,
                                                      uint8_t *__restrict__ b6) {
+    using F = F6Fmt<kA4>;
     const uint32_t NK = (NP + 127) / 128;
     const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (idx >= (size_t)LP / 16 * NK * 64) return;
@@ -925,38 +954,26 @@ __global__ __launch_bounds__(256) void frag6_kernel(const uint8_t *__restrict__ 
     const uint32_t kb = (uint32_t)(tk % NK);
     const uint8_t *row = codes + (tile * 64 + blk * 16 + (lane & 15)) * (size_t)NP;
     const uint32_t k0 = 128 * kb + 32 * (lane >> 4);
-    uint32_t ai[6] = {0, 0, 0, 0, 0, 0}, am[6] = {0, 0, 0, 0, 0, 0}, b[4] = {0, 0, 0, 0};
-    for (uint32_t j = 0; j < 32; ++j) {
-        const uint32_t k = k0 + j;
+    // channel 0: w [missing] (ai keeps the operand slot's name).  A padded
+    // sequence (N <= k < NP) has code 0 and so reads as missing in A and in
+    // B: it contributes nothing only because its weight code is 0 there
+    // (fp6_prepare zero-fills the codes past N; fp6_marginals_kernel relies
+    // on the same), and past NP the operand is 0 outright (fp6_pack.hpp).
 #ifdef WLD_EXP_ZERO_IMG  // diagnostic: all-zero operand images, the same instruction stream
-        const uint32_t c = 0u, v = 0u;
+    const uint32_t n = 0u;
 #else
-        const uint32_t c = k < NP ? row[k] : 0u, v = k < NP ? w6[k] : 0u;
+    const uint32_t n = k0 < NP ? min(32u, NP - k0) : 0u;
 #endif
-        // channel 0: w6 [missing] (ai keeps the operand slot's name).  A
-        // padded sequence (N <= k < NP) has code 0 and so reads as missing in
-        // A and in B: it contributes nothing only because w6[k] = 0 there
-        // (fp6_prepare zero-fills the codes past N; fp6_marginals_kernel
-        // relies on the same), and past NP the operand is 0 outright.
-        const uint32_t vi = (c & kCodeIn) ? 0u : v, vm = (c & (kCodeIn | kCodeMaj)) == kCodeIn ? v : 0u;
-        const uint32_t bit = 6 * j, d = bit >> 5, o = bit & 31;
-        ai[d] |= vi << o;
-        am[d] |= vm << o;
-        if (o > 26) {
-            ai[d + 1] |= vi >> (32 - o);
-            am[d + 1] |= vm >> (32 - o);
-        }
-        // fp4 nibble j: 4 (2.0: missing), 2 (1.0: minor), 0 (major)
-#ifndef WLD_EXP_ZERO_IMG
-        if (k < NP) b[j >> 3] |= ((c & kCodeIn) ? ((c & kCodeMaj) ? 0u : 2u) : 4u) << (4 * (j & 7));
-#endif
-    }
-    uint8_t *pa = a6 + tk * kF6AStage + blk * kF6ABytes, *pm = pa + 1536;
+    uint32_t ai[6], am[6], b[4];
+    f6_pack_lane<kA4>(row + k0, wa + k0, n, ai, am, b);
+    uint8_t *pa = a6 + tk * F::kAStage + blk * F::kABytes, *pm = pa + F::kChan;
     uint8_t *pb = b6 + tk * kF6BStage + blk * kF6BBytes;
     *reinterpret_cast<uint4 *>(pa + 16 * lane) = make_uint4(ai[0], ai[1], ai[2], ai[3]);
-    *reinterpret_cast<uint2 *>(pa + 1024 + 8 * lane) = make_uint2(ai[4], ai[5]);
     *reinterpret_cast<uint4 *>(pm + 16 * lane) = make_uint4(am[0], am[1], am[2], am[3]);
-    *reinterpret_cast<uint2 *>(pm + 1024 + 8 * lane) = make_uint2(am[4], am[5]);
+    if (!kA4) {
+        *reinterpret_cast<uint2 *>(pa + 1024 + 8 * lane) = make_uint2(ai[4], ai[5]);
+        *reinterpret_cast<uint2 *>(pm + 1024 + 8 * lane) = make_uint2(am[4], am[5]);
+    }
     *reinterpret_cast<uint4 *>(pb + 16 * lane) = make_uint4(b[0], b[1], b[2], b[3]);
 }
 
@@ -1008,6 +1025,15 @@ __device__ __forceinline__ v8i f6_ldb(const uint8_t *p, uint32_t lane) {
     const uint4 x = *reinterpret_cast<const uint4 *>(p + 16 * lane);
     return v8i{(int)x.x, (int)x.y, (int)x.z, (int)x.w, 0, 0, 0, 0};
 }
+// one A channel of a 16-site block in the image's format: the fp4 image's is
+// laid out as a B block (one ds_read_b128)
+template <bool kA4>
+__device__ __forceinline__ v8i f6_lda(const uint8_t *p, uint32_t lane) {
+    if constexpr (kA4)
+        return f6_ldb(p, lane);
+    else
+        return f6_ld24(p, lane);
+}
 // one B block's four MFMAs against the wave's A channels (missing: ai, minor: am):
 // acc[channel_a][0 / 1] = X / Y (B raw: 2 missing + minor, B's minor bit)
 // Zero scale operands: the compiler selects the unscaled
@@ -1016,17 +1042,20 @@ __device__ __forceinline__ v8i f6_ldb(const uint8_t *p, uint32_t lane) {
 // faster: 17.5 / 16.7 / 16.5 against 19.5 / 17.3 / 17.0 cycles per
 // instruction at 1 / 2 / 3 waves per SIMD (tools/probes/fp6_unscaled_probe.hip);
 // screen C4 -4.1%, 1/8 shard -4.8% (profiles/r06c/).
+// kCbsz: the A operand's format (F6Fmt: 2 fp6, six registers; 4 fp4, four, at
+// the same rate); B is fp4 (blgp 4).
+template <int kCbsz>
 __device__ __forceinline__ v4f f6_mfma(const v8i &a, const v8i &b, const v4f &c) {
-    return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, c, 2, 4, 0, 0, 0, 0);
+    return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, c, kCbsz, 4, 0, 0, 0, 0);
 }
+template <int kCbsz>
 __device__ __forceinline__ void f6_block_mfma(v4f (&acc)[2][2], const v8i &ai, const v8i &am, const v8i &b) {
-    constexpr int kOne = 0;
     constexpr int kMinor = 0x22222222;  // fp4 1.0 (minor) nibbles; 2.0 (missing) is 0x4
     const v8i bmin = {b[0] & kMinor, b[1] & kMinor, b[2] & kMinor, b[3] & kMinor, 0, 0, 0, 0};
-    acc[0][0] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(ai, b, acc[0][0], 2, 4, 0, kOne, 0, kOne);
-    acc[0][1] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(ai, bmin, acc[0][1], 2, 4, 0, kOne, 0, kOne);
-    acc[1][0] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(am, b, acc[1][0], 2, 4, 0, kOne, 0, kOne);
-    acc[1][1] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(am, bmin, acc[1][1], 2, 4, 0, kOne, 0, kOne);
+    acc[0][0] = f6_mfma<kCbsz>(ai, b, acc[0][0]);
+    acc[0][1] = f6_mfma<kCbsz>(ai, bmin, acc[0][1]);
+    acc[1][0] = f6_mfma<kCbsz>(am, b, acc[1][0]);
+    acc[1][1] = f6_mfma<kCbsz>(am, bmin, acc[1][1]);
 }
 // t1 of pair e of a B block's accumulators, mlo its smallest marginal
 __device__ __forceinline__ float f6_terms(const v4f (&acc)[2][2], int e, float R2, float thr_c, float E,
@@ -1115,7 +1144,9 @@ __device__ __forceinline__ void f6c_rebuild(v4f (&acc)[4][2][2], const float2 *s
 }  // namespace
 
 // one 64x64 tile per 4-wave workgroup, four per CU (tile lists past 2^15
-// tile columns, and WLD_OPT_FP6_PAIRS_MIN_TILES's smaller lists)
+// tile columns, and WLD_OPT_FP6_PAIRS_MIN_TILES's smaller lists); kA4: the
+// load's A image is fp4 (12-KB stages, three pieces per wave)
+template <bool kA4>
 __global__ __launch_bounds__(256, 4) void pair_fp6_screen_kernel(const uint8_t *__restrict__ a6,
                                                                   const uint8_t *__restrict__ b6,
                                                                   const float2 *__restrict__ marg, float W6,
@@ -1123,6 +1154,8 @@ __global__ __launch_bounds__(256, 4) void pair_fp6_screen_kernel(const uint8_t *
                                                                   const uint32_t *__restrict__ tiles, uint32_t n_tiles,
                                                                   uint32_t NK, uint32_t L, uint32_t n_chunk_rows,
                                                                   float thr, OrderArgs o, ScreenArgs sc) {
+    using F = F6Fmt<kA4>;
+    constexpr int kF6AStage = F::kAStage, kF6ABytes = F::kABytes, kF6Stage = F::kStage;
     __shared__ __attribute__((aligned(16))) uint8_t smem[2 * kF6Stage];
     __shared__ float2 sMarg[2 * kTile];  // {M, m} of the row tile's sites, then the column tile's
     __shared__ unsigned long long sMask;
@@ -1186,9 +1219,10 @@ __global__ __launch_bounds__(256, 4) void pair_fp6_screen_kernel(const uint8_t *
         }
         if (kb + 1 < NK) issue(kb + 1, buf ^ 1);
         const uint8_t *g = smem + buf * kF6Stage;
-        const v8i ai = f6_ld24(g + wave * kF6ABytes, lane), am = f6_ld24(g + wave * kF6ABytes + 1536, lane);
+        const v8i ai = f6_lda<kA4>(g + wave * kF6ABytes, lane), am = f6_lda<kA4>(g + wave * kF6ABytes + F::kChan, lane);
 #pragma unroll
-        for (int n = 0; n < 4; ++n) f6_block_mfma(acc[n], ai, am, f6_ldb(g + kF6AStage + n * kF6BBytes, lane));
+        for (int n = 0; n < 4; ++n)
+            f6_block_mfma<F::kCbsz>(acc[n], ai, am, f6_ldb(g + kF6AStage + n * kF6BBytes, lane));
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // reads of this buffer done before the next barrier
         buf ^= 1;
     }
@@ -1230,11 +1264,12 @@ constexpr uint32_t kF6Single = 0x8000u;  // (= tile_order::kSingleEntry)
 // (per MFMA 0.31 KB of LDS reads); 128 accumulator registers per lane.  Each
 // half decides its own tile; a single entry's second half computes on the
 // first B image and decides nothing (it keeps the workgroup's barriers).
+// kA4 (the load's A image is fp4): 8 KB of A, two 16-KB stage buffers, wave w
+// copies A pieces w and w + 4.
 // (Measured and removed: eight waves of 16 x 64, three stage buffers, a
 // producer/consumer split, register-staged operands (round 5); tile triples
 // on six waves, two workgroups per CU (+43%), and the full-tile bound on
 // packed f32 (+1%) (round 6); DESIGN.md Appendix A.)
-constexpr int kF6PStage = kF6AStage + 2 * kF6BStage;
 #ifdef WLD_EXP_CLOCK
 // diagnostic build: per workgroup (slot blockIdx.x % kF6ClockSlots) wave 0's
 // shader-clock and 100-MHz real-time counts around the stage loop
@@ -1244,11 +1279,14 @@ extern "C" int wld_debug_f6_clock(unsigned long long *out) {
     return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(gF6Clock), sizeof(gF6Clock));
 }
 #endif
+template <bool kA4>
 __global__ __launch_bounds__(256, 3) void pair_fp6_screen2w_kernel(
     const uint8_t *__restrict__ a6, const uint8_t *__restrict__ b6, const float2 *__restrict__ marg, float W6,
     const uint64_t *__restrict__ ok_bits,
     const uint32_t *__restrict__ pairs, uint32_t n_pairs, uint32_t NK, uint32_t L, uint32_t n_chunk_rows, float thr,
     OrderArgs o, ScreenArgs sc) {
+    using F = F6Fmt<kA4>;
+    constexpr int kF6AStage = F::kAStage, kF6ABytes = F::kABytes, kF6PStage = F::kPStage;
     __shared__ __attribute__((aligned(16))) uint8_t smem[2 * kF6PStage];
     __shared__ float2 sMarg[3 * kTile];  // {M, m} of the row tile's sites, then each half's column tile's
     __shared__ unsigned long long sMask[2];
@@ -1264,7 +1302,8 @@ __global__ __launch_bounds__(256, 3) void pair_fp6_screen2w_kernel(
     // + 1 16-19): wave w copies w, w + 4, w + 8 of A and piece w of each B
     // image (a single entry's second image is the first's, which its idle
     // half reads)
-    static_assert(kF6AStage == 3 * 4096 && kF6BStage == 4096, "five pieces per wave and stage");
+    // (the fp4 A image is eight pieces: w and w + 4, four pieces per wave)
+    static_assert(kF6AStage == (kA4 ? 2 : 3) * 4096 && kF6BStage == 4096, "five (fp4 A: four) pieces per wave and stage");
     struct Src {
         const uint8_t *pA, *pB0, *pB1;
     };
@@ -1282,7 +1321,7 @@ __global__ __launch_bounds__(256, 3) void pair_fp6_screen2w_kernel(
         const size_t bo = (size_t)kb * kF6BStage;
         glds16_s(a, lane16, gb);
         glds16_s(a + 4096, lane16, gb + 4096);
-        glds16_s(a + 8192, lane16, gb + 8192);
+        if (!kA4) glds16_s(a + 8192, lane16, gb + 8192);
         glds16_s(sr.pB0 + bo, lane16, gb + kF6AStage);
         glds16_s(sr.pB1 + bo, lane16, gb + kF6AStage + kF6BStage);
     };
@@ -1345,24 +1384,25 @@ __global__ __launch_bounds__(256, 3) void pair_fp6_screen2w_kernel(
             // left the read's latency exposed; profiles/r06k/.  Reading row
             // block 0's A and B block 0 first, or the next stage's copies
             // issued after the reads, measured no better: profiles/r06l/)
-            const v8i ai0 = f6_ld24(g + aoff, lane), am0 = f6_ld24(g + aoff + 1536, lane);
-            const v8i ai1 = f6_ld24(g + aoff + kF6ABytes, lane), am1 = f6_ld24(g + aoff + kF6ABytes + 1536, lane);
+            const v8i ai0 = f6_lda<kA4>(g + aoff, lane), am0 = f6_lda<kA4>(g + aoff + F::kChan, lane);
+            const v8i ai1 = f6_lda<kA4>(g + aoff + kF6ABytes, lane),
+                      am1 = f6_lda<kA4>(g + aoff + kF6ABytes + F::kChan, lane);
             const v4f kZero = {0.0f, 0.0f, 0.0f, 0.0f};
             v8i bs[2] = {f6_ldb(g + boff, lane), f6_ldb(g + boff + kF6BBytes, lane)};
 #pragma unroll
             for (int n = 0; n < 4; ++n) {
                 v8i &b = bs[n & 1];
                 constexpr int kMinor = 0x22222222;  // fp4 1.0 (minor) nibbles; 2.0 (missing) is 0x4
-                acc[0][n][0][0] = f6_mfma(ai0, b, kFirst ? kZero : acc[0][n][0][0]);
-                acc[0][n][1][0] = f6_mfma(am0, b, kFirst ? kZero : acc[0][n][1][0]);
-                acc[1][n][0][0] = f6_mfma(ai1, b, kFirst ? kZero : acc[1][n][0][0]);
-                acc[1][n][1][0] = f6_mfma(am1, b, kFirst ? kZero : acc[1][n][1][0]);
+                acc[0][n][0][0] = f6_mfma<F::kCbsz>(ai0, b, kFirst ? kZero : acc[0][n][0][0]);
+                acc[0][n][1][0] = f6_mfma<F::kCbsz>(am0, b, kFirst ? kZero : acc[0][n][1][0]);
+                acc[1][n][0][0] = f6_mfma<F::kCbsz>(ai1, b, kFirst ? kZero : acc[1][n][0][0]);
+                acc[1][n][1][0] = f6_mfma<F::kCbsz>(am1, b, kFirst ? kZero : acc[1][n][1][0]);
                 __builtin_amdgcn_sched_barrier(0);
                 b = v8i{b[0] & kMinor, b[1] & kMinor, b[2] & kMinor, b[3] & kMinor, 0, 0, 0, 0};
-                acc[0][n][0][1] = f6_mfma(ai0, b, kFirst ? kZero : acc[0][n][0][1]);
-                acc[0][n][1][1] = f6_mfma(am0, b, kFirst ? kZero : acc[0][n][1][1]);
-                acc[1][n][0][1] = f6_mfma(ai1, b, kFirst ? kZero : acc[1][n][0][1]);
-                acc[1][n][1][1] = f6_mfma(am1, b, kFirst ? kZero : acc[1][n][1][1]);
+                acc[0][n][0][1] = f6_mfma<F::kCbsz>(ai0, b, kFirst ? kZero : acc[0][n][0][1]);
+                acc[0][n][1][1] = f6_mfma<F::kCbsz>(am0, b, kFirst ? kZero : acc[0][n][1][1]);
+                acc[1][n][0][1] = f6_mfma<F::kCbsz>(ai1, b, kFirst ? kZero : acc[1][n][0][1]);
+                acc[1][n][1][1] = f6_mfma<F::kCbsz>(am1, b, kFirst ? kZero : acc[1][n][1][1]);
                 __builtin_amdgcn_sched_barrier(0);
                 if (n + 2 < 4) b = f6_ldb(g + boff + (n + 2) * kF6BBytes, lane);
                 __builtin_amdgcn_sched_barrier(0);
@@ -1589,11 +1629,14 @@ __global__ __launch_bounds__(256, 3) void pair_i8_screen2w_kernel(
     if (!idle) screen_verdict(mine ? (uint32_t)sMask[half] : 0u, ta, tb, ltid, n_chunk_rows, o, sc);
 }
 
-void launch_frag6(const uint8_t *codes, const uint8_t *w6, size_t LP, size_t NP, uint8_t *a6, uint8_t *b6,
-                  float *marg, hipStream_t s) {
+void launch_frag6(const uint8_t *codes, const uint8_t *w6, const uint8_t *wa, bool a4, size_t LP, size_t NP,
+                  uint8_t *a6, uint8_t *b6, float *marg, hipStream_t s) {
     const size_t n = LP / 16 * ((NP + 127) / 128) * 64;
-    hipLaunchKernelGGL(frag6_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, codes, w6, (uint32_t)LP,
-                       (uint32_t)NP, a6, b6);
+    const dim3 grid((unsigned)((n + 255) / 256));
+    if (a4)
+        hipLaunchKernelGGL(frag6_kernel<true>, grid, dim3(256), 0, s, codes, wa, (uint32_t)LP, (uint32_t)NP, a6, b6);
+    else
+        hipLaunchKernelGGL(frag6_kernel<false>, grid, dim3(256), 0, s, codes, wa, (uint32_t)LP, (uint32_t)NP, a6, b6);
     hipLaunchKernelGGL(fp6_marginals_kernel, dim3((unsigned)((LP + 3) / 4)), dim3(256), 0, s, codes, w6, (uint32_t)LP,
                        (uint32_t)NP, marg);
 }
@@ -1747,22 +1790,30 @@ void fp6_screen_args(const MfmaLaunch &m, ScreenArgs &sc) {
     screen_consts(m.fp6->Tg, 2.0f * sc.Rf, sc.E, sc.mloc);
 }
 // the fp6 screen over the pair list (or the tile list), every entry, or with
-// sc.probe every stride-th one
-void launch_fp6_screen(const MfmaLaunch &m, const uint64_t *ok_bits, const OrderArgs &o, const ScreenArgs &sc,
-                       uint32_t stride, hipStream_t s) {
+// sc.probe every stride-th one, on the kernels of the load's A format
+template <bool kA4>
+void launch_fp6_screen_fmt(const MfmaLaunch &m, const uint64_t *ok_bits, const OrderArgs &o, const ScreenArgs &sc,
+                           uint32_t stride, hipStream_t s) {
     if (m.f6_pairs) {
         // (a tile group per workgroup, the XCD-ordered group list)
-        hipLaunchKernelGGL(pair_fp6_screen2w_kernel, dim3((m.f6_n_pairs + stride - 1) / stride), dim3(256), 0, s,
+        hipLaunchKernelGGL(pair_fp6_screen2w_kernel<kA4>, dim3((m.f6_n_pairs + stride - 1) / stride), dim3(256), 0, s,
                            m.fp6->a6, m.fp6->b6, reinterpret_cast<const float2 *>(m.fp6->marg), m.fp6->W6, ok_bits,
                            m.f6_pairs, m.f6_n_pairs, m.fp6->NK, m.L, m.n_chunk_rows,
                            m.thr, o, sc);
     } else {
         // (one tile per workgroup, the XCD-ordered list)
-        hipLaunchKernelGGL(pair_fp6_screen_kernel, dim3((m.n_tiles + stride - 1) / stride), dim3(256), 0, s,
+        hipLaunchKernelGGL(pair_fp6_screen_kernel<kA4>, dim3((m.n_tiles + stride - 1) / stride), dim3(256), 0, s,
                            m.fp6->a6, m.fp6->b6, reinterpret_cast<const float2 *>(m.fp6->marg), m.fp6->W6, ok_bits,
                            m.tiles, m.n_tiles, m.fp6->NK, m.L, m.n_chunk_rows, m.thr,
                            o, sc);
     }
+}
+void launch_fp6_screen(const MfmaLaunch &m, const uint64_t *ok_bits, const OrderArgs &o, const ScreenArgs &sc,
+                       uint32_t stride, hipStream_t s) {
+    if (m.fp6->a4)
+        launch_fp6_screen_fmt<true>(m, ok_bits, o, sc, stride, s);
+    else
+        launch_fp6_screen_fmt<false>(m, ok_bits, o, sc, stride, s);
 }
 }  // namespace
 
