@@ -248,6 +248,12 @@ int wld_set_kernel(wld_ctx *ctx, int kernel);
  *                      exact either way: same sums, candidates and rows.
  *                      Setting it discards the built images (the next run that
  *                      may screen on fp6 rebuilds them).
+ *   WLD_OPT_TARGET_BATCH_SLOTS  wld_run_targets: the pair slots (16 x target
+ *                      blocks x padded site count, three floats each) of the
+ *                      dense staging one batch may use (default 2^26: 768 MiB;
+ *                      a batch always holds at least one block of 16 targets).
+ *                      Changes no result; it exists so tests can force several
+ *                      batches.
  *   WLD_OPT_TEST_GUARD 0 (default); 1 (tests only): before each candidate
  *                      launch the last candidate bucket's count is set one
  *                      past its capacity, so the launch meets an entry outside
@@ -271,6 +277,7 @@ int wld_set_kernel(wld_ctx *ctx, int kernel);
 #define WLD_OPT_FP6_PAIRS_MIN_TILES 15
 #define WLD_OPT_I8_PAIRS 16
 #define WLD_OPT_FP6_A4 17
+#define WLD_OPT_TARGET_BATCH_SLOTS 18
 int wld_set_option(wld_ctx *ctx, int option, int64_t value);
 int wld_get_option(wld_ctx *ctx, int option, int64_t *value);
 
@@ -648,6 +655,59 @@ void wld_prune_free(wld_prune *p);
  * edge): the CSR build, the rounds (with the host's reads of the undecided
  * count between them), the tags.  Any pointer may be NULL. */
 int wld_prune_times(wld_ctx *ctx, double *csr_ms, double *rounds_ms, double *tags_ms);
+
+/* ---- Target sites: the rows of chosen sites against every in-window partner
+ * (not in the reference; PLINK's --ld-snp / --ld-snps / --ld-snp-list, a proxy
+ * search, the r2 track of a regional plot) ----
+ *
+ * targets: n_targets LOADED indices of the loaded set, in any order, without
+ * repeats.  For target t and every loaded site s != t, with a = min(s, t) and
+ * b = max(s, t), there is a row iff the pair (a, b) is in the context's
+ * current window (wld_set_window; symmetric about a target),
+ * single_weighted_ld_pair gives Some, and r2 > r2_threshold strictly (NaN
+ * never passes).  d, d_prime and r2 are, bit for bit, what the default row
+ * path (WLD_OPT_REF_SUMS 1) puts in the row of pair (a, b), whichever side of
+ * the target the partner lies on: the result always comes from lib.rs's
+ * summation order; the kernel choice, WLD_OPT_REF_SUMS and the screen options
+ * do not apply.  The work is n_targets x n_sites pairs (one pass over the
+ * resident codes per 16 targets), not the triangle.
+ *
+ * Rows are ordered by position in the caller's list, then by the partner's
+ * loaded index ascending; target k's rows are [offset[k], offset[k + 1]).  A
+ * pair of two targets appears once under each.  site_target / site_partner
+ * are PARENT indices, target[] the list position k.
+ *   items     work items launched: the (block of 16 targets in loaded order,
+ *             64-site partner tile) pairs whose tile holds an in-window
+ *             partner of a target of the block;
+ *   batches   the staging's batches (WLD_OPT_TARGET_BATCH_SLOTS);
+ *   kernel_ms HIP-event time of the pair launches, summed over the batches.
+ * Everything but kernel_ms is a function of the load, the window, the list and
+ * the threshold: identical from run to run and across batch sizes.  The call
+ * changes nothing a later row run depends on; the last run's rows and
+ * wld_last_stats stay as they were.
+ *
+ * n_targets == 0: WLD_OK, no rows (offset[0] = 0).  WLD_E_ARG, naming the
+ * first offending list position: a target >= the loaded site count; a repeated
+ * target.  WLD_E_ARG also: targets == NULL with n_targets > 0; non-finite
+ * weights (a load that takes the row path's select loop); n_targets x
+ * (n_sites - 1) > 2^32 - 1 (split the list).  WLD_E_STATE: before a load,
+ * while a run is in flight, on a device group.  WLD_E_OOM leaves the context
+ * usable.  No progress callback.  Release with wld_target_rows_free. */
+typedef struct {
+    uint64_t n;             /* rows */
+    uint32_t n_targets;
+    uint64_t *offset;       /* n_targets + 1: target k's rows are [offset[k], offset[k+1]) */
+    uint32_t *target;       /* n: index k into the caller's list */
+    uint32_t *site_target;  /* n: PARENT index of the target  */
+    uint32_t *site_partner; /* n: PARENT index of the partner */
+    float *d, *d_prime, *r2;
+    uint64_t items;         /* work items launched */
+    uint32_t batches;
+    double kernel_ms;       /* HIP-event time of the pair launches, summed over batches */
+} wld_target_rows;
+int  wld_run_targets(wld_ctx *ctx, const uint32_t *targets, uint32_t n_targets,
+                     float r2_threshold, wld_target_rows *out);
+void wld_target_rows_free(wld_target_rows *r);
 
 #ifdef __cplusplus
 }

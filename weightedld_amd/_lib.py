@@ -26,7 +26,8 @@ KERNEL_AUTO, KERNEL_VALU, KERNEL_MFMA = 0, 1, 2
 # wld_set_option ids (include/weightedld.h)
 OPTIONS = {"prefilter": 1, "screen": 2, "tile_order": 3, "all_planes": 4, "mfma_layout": 5, "valu_plain": 6,
            "staging_rows": 7, "host_batch_pairs": 8, "ref_sums": 11, "fused_scan": 12, "screen_fp6": 13,
-           "test_guard": 14, "fp6_pairs_min_tiles": 15, "i8_pairs": 16, "fp6_a4": 17}
+           "test_guard": 14, "fp6_pairs_min_tiles": 15, "i8_pairs": 16, "fp6_a4": 17,
+           "target_batch_slots": 18}
 
 
 class WldError(RuntimeError):
@@ -100,6 +101,23 @@ class Prune(ctypes.Structure):
         ("tag", ctypes.POINTER(ctypes.c_uint32)),
         ("pair_ms", ctypes.c_double),
         ("prune_ms", ctypes.c_double),
+    ]
+
+
+class TargetRowsC(ctypes.Structure):
+    _fields_ = [
+        ("n", ctypes.c_uint64),
+        ("n_targets", ctypes.c_uint32),
+        ("offset", ctypes.POINTER(ctypes.c_uint64)),
+        ("target", ctypes.POINTER(ctypes.c_uint32)),
+        ("site_target", ctypes.POINTER(ctypes.c_uint32)),
+        ("site_partner", ctypes.POINTER(ctypes.c_uint32)),
+        ("d", ctypes.POINTER(ctypes.c_float)),
+        ("d_prime", ctypes.POINTER(ctypes.c_float)),
+        ("r2", ctypes.POINTER(ctypes.c_float)),
+        ("items", ctypes.c_uint64),
+        ("batches", ctypes.c_uint32),
+        ("kernel_ms", ctypes.c_double),
     ]
 
 
@@ -184,6 +202,8 @@ SIGNATURES = {
     "wld_loaded_sites": (_sz, [_vp]),
     "wld_prune_times": (_int, [_vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                                ctypes.POINTER(ctypes.c_double)]),
+    "wld_run_targets": (_int, [_vp, _u32p, ctypes.c_uint32, ctypes.c_float, ctypes.POINTER(TargetRowsC)]),
+    "wld_target_rows_free": (None, [ctypes.POINTER(TargetRowsC)]),
 }
 
 _lib = None

@@ -13,13 +13,13 @@ from collections import namedtuple
 
 import numpy as np
 
-from ._lib import (KERNEL_AUTO, KERNEL_MFMA, KERNEL_VALU, OPTIONS, PROGRESS_FN, Pairs, Prune, RunStats, Summary, WldError,
-                   check, lib)
+from ._lib import (KERNEL_AUTO, KERNEL_MFMA, KERNEL_VALU, OPTIONS, PROGRESS_FN, Pairs, Prune, RunStats, Summary, TargetRowsC,
+                   WldError, check, lib)
 
 __all__ = [
     "Symbol", "SymbolHistogram", "SiteSet", "LdStats", "PairStore", "read_fasta", "read_vcf",
     "is_site_of_interest", "henikoff_weights", "single_weighted_ld_pair", "all_weighted_ld_pairs",
-    "ld_summary", "LdSummary", "ld_prune", "LdPrune", "maf_priority", "Context", "default_context", "KERNEL_AUTO", "KERNEL_VALU", "KERNEL_MFMA", "OPTIONS", "WldError",
+    "ld_summary", "LdSummary", "ld_prune", "LdPrune", "maf_priority", "ld_targets", "TargetRows", "Context", "default_context", "KERNEL_AUTO", "KERNEL_VALU", "KERNEL_MFMA", "OPTIONS", "WldError",
 ]
 
 
@@ -228,6 +228,21 @@ class LdPrune:
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
+
+
+class TargetRows:
+    """wld_target_rows as numpy arrays and numbers (Context.run_targets,
+    ld_targets): offset (uint64, one more than the targets: target k's rows are
+    [offset[k], offset[k + 1])), target (the list position k), site_target and
+    site_partner (PARENT indices), d, d_prime, r2 (float32), in list order then
+    by partner; items, batches and kernel_ms.  From ld_targets also targets:
+    the loaded indices the rows' `target` column indexes."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def __len__(self):
+        return int(self.r2.size)
 
 
 def maf_priority(site_set):
@@ -507,6 +522,31 @@ class Context:
         lib().wld_prune_free(ctypes.byref(out))
         return res
 
+    def run_targets(self, targets, r2_threshold):
+        """wld_run_targets: the rows (r2 > r2_threshold) of the listed LOADED
+        site indices against every in-window partner, as a TargetRows: by list
+        position, then partner ascending; values bit-identical to the default
+        row path's row of the pair."""
+        t = np.ascontiguousarray(targets, dtype=np.int64).reshape(-1)
+        if t.size and (t.min() < 0 or t.max() > 0xFFFFFFFF):
+            raise ValueError("targets must be loaded site indices (32-bit, nonnegative)")
+        t = t.astype(np.uint32)
+        out = TargetRowsC()
+        check(lib().wld_run_targets(self._h, _p(t, ctypes.c_uint32) if t.size else None, int(t.size), r2_threshold,
+                                    ctypes.byref(out)), "wld_run_targets")
+        n, q = int(out.n), int(out.n_targets)
+
+        def grab(p, m, dt):
+            return np.ctypeslib.as_array(p, shape=(m,)).astype(dt, copy=True) if m else np.zeros(0, dtype=dt)
+
+        res = TargetRows(offset=grab(out.offset, q + 1, np.uint64), target=grab(out.target, n, np.uint32),
+                         site_target=grab(out.site_target, n, np.uint32),
+                         site_partner=grab(out.site_partner, n, np.uint32), d=grab(out.d, n, np.float32),
+                         d_prime=grab(out.d_prime, n, np.float32), r2=grab(out.r2, n, np.float32),
+                         items=int(out.items), batches=int(out.batches), kernel_ms=float(out.kernel_ms))
+        lib().wld_target_rows_free(ctypes.byref(out))
+        return res
+
     def prune_times(self):
         """wld_prune_times: the last run_prune's prune_ms by phase, (csr_ms, rounds_ms, tags_ms)."""
         t = [ctypes.c_double() for _ in range(3)]
@@ -700,6 +740,45 @@ def ld_prune(site_set, weights, r2_threshold, priority=None, max_distance=None, 
         ctx.set_window(*before)
     kept = np.flatnonzero(res.keep).astype(np.uint64)
     res.kept_sites = kept if sm is None else sm[kept]
+    return res
+
+
+def ld_targets(site_set, weights, r2_threshold, targets=None, parents=None, max_distance=None, max_sites=None,
+               ctx=None):
+    """Target-site LD (not in the reference; PLINK --ld-snp / --ld-snps): loads
+    site_set and runs Context.run_targets at r2_threshold under the window
+    max_distance / max_sites (the context's own window is restored
+    afterwards).  Exactly one of targets (the set's own site indices) and
+    parents (parent coordinates: each maps to every site of the set carrying
+    it, in site order — multi-allelic VCF lines share a POS; one that no site
+    carries raises ValueError) must be given.  Returns a TargetRows whose
+    `targets` are the site indices the `target` column refers to."""
+    if (targets is None) == (parents is None):
+        raise ValueError("give exactly one of targets and parents")
+    ctx = ctx or default_context()
+    w = np.ascontiguousarray(weights, dtype=np.float32)
+    if w.size != site_set.n_seqs():
+        raise ValueError("weights must have n_seqs entries")
+    sm = site_set.site_map
+    if parents is not None:
+        pos = np.arange(site_set.n_sites(), dtype=np.uint64) if sm is None else np.asarray(sm, dtype=np.uint64)
+        chosen = []
+        for c in np.asarray(parents).reshape(-1).tolist():
+            hit = np.flatnonzero(pos == np.uint64(c)) if c >= 0 else np.zeros(0, dtype=np.int64)
+            if hit.size == 0:
+                raise ValueError("no site of the set has parent coordinate %d" % c)
+            chosen.extend(hit.tolist())
+        targets = chosen
+    targets = np.ascontiguousarray(targets, dtype=np.int64).reshape(-1)
+    before = ctx.window()
+    if max_distance is not None or max_sites is not None:
+        ctx.set_window(max_distance, max_sites)
+    try:
+        ctx.load(site_set.buffer, w, sm)
+        res = ctx.run_targets(targets, r2_threshold)
+    finally:
+        ctx.set_window(*before)
+    res.targets = targets.astype(np.uint32)
     return res
 
 

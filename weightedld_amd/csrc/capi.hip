@@ -26,6 +26,7 @@
 #include "window_plan.hpp"
 #include "summary_plan.hpp"
 #include "prune_plan.hpp"
+#include "targets_plan.hpp"
 #include "kernels.hpp"
 #include "fp6_scale.hpp"
 
@@ -134,6 +135,7 @@ struct wld_ctx {
     bool opt_fp6_a4 = true;      // WLD_OPT_FP6_A4: the fp6 screen's A image as fp4 where the weight codes fit e2m1
     bool opt_ref_sums = true;  // WLD_OPT_REF_SUMS: lib.rs's own f32 summation order (default)
     uint64_t opt_staging_rows = 1ull << 25, opt_host_batch_pairs = 1ull << 31;
+    uint64_t opt_target_slots = targets_plan::kDefaultBatchSlots;  // WLD_OPT_TARGET_BATCH_SLOTS
 
     // loaded SiteSet
     bool loaded = false;
@@ -232,6 +234,19 @@ struct wld_ctx {
     hipEvent_t ev_pr[4] = {};
     double pr_ms[3] = {0.0, 0.0, 0.0};
 
+    // wld_run_targets: a batch's lists, dense staging, masks, counts and rows
+    // (kept between calls while small: run_targets), and the two events around
+    // its pair launch (created at the first call)
+    struct TargetBufs {
+        DevBuf slot_site, slot_pos, items, d, dp, r2, mask, tile_pref, slot_cnt, slot_base, guard;
+        DevBuf o_t, o_st, o_sp, o_d, o_dp, o_r2;
+        std::vector<DevBuf *> all() {
+            return {&slot_site, &slot_pos, &items, &d, &dp, &r2, &mask, &tile_pref, &slot_cnt, &slot_base, &guard,
+                    &o_t, &o_st, &o_sp, &o_d, &o_dp, &o_r2};
+        }
+    } tg;
+    hipEvent_t ev_tg[2] = {};
+
     ~wld_ctx() {
         for (wld_ctx *m : members) delete m;
         if (!members.empty()) return;
@@ -243,6 +258,9 @@ struct wld_ctx {
                          &seg_cnt, &seg_off, &chunk_total, &chunk_base, &counters, &chunk_left, &prog_n, &win_hi, &win_pairs, &sum_buf, &st_a, &st_b, &st_d,
                          &st_dp, &st_r2, &out_a, &out_b, &out_d, &out_dp, &out_r2};
         for (DevBuf *b : all) release(*b);
+        for (DevBuf *b : tg.all()) release(*b);
+        for (auto &e : ev_tg)
+            if (e) (void)hipEventDestroy(e);
         for (auto &e : ev)
             if (e) (void)hipEventDestroy(e);
         for (auto &e : ev_sum)
@@ -981,6 +999,10 @@ int wld_set_option(wld_ctx *c, int option, int64_t value) {
             if (value < 1) return fail(WLD_E_ARG, "WLD_OPT_HOST_BATCH_PAIRS must be >= 1");
             c->opt_host_batch_pairs = (uint64_t)value;
             break;
+        case WLD_OPT_TARGET_BATCH_SLOTS:
+            if (value < 1) return fail(WLD_E_ARG, "WLD_OPT_TARGET_BATCH_SLOTS must be >= 1");
+            c->opt_target_slots = (uint64_t)value;
+            break;
         case WLD_OPT_FUSED_SCAN: c->opt_fused_scan = value != 0; break;
         case WLD_OPT_I8_PAIRS: c->opt_i8_pairs = value != 0; break;
         case WLD_OPT_TEST_GUARD: c->opt_test_guard = value != 0; break;
@@ -1105,6 +1127,7 @@ int wld_get_option(wld_ctx *c, int option, int64_t *value) {
         case WLD_OPT_REF_SUMS: *value = c->opt_ref_sums; break;
         case WLD_OPT_STAGING_ROWS: *value = (int64_t)c->opt_staging_rows; break;
         case WLD_OPT_HOST_BATCH_PAIRS: *value = (int64_t)c->opt_host_batch_pairs; break;
+        case WLD_OPT_TARGET_BATCH_SLOTS: *value = (int64_t)c->opt_target_slots; break;
         case WLD_OPT_FUSED_SCAN: *value = c->opt_fused_scan; break;
         case WLD_OPT_TEST_GUARD: *value = c->opt_test_guard; break;
         case WLD_OPT_FP6_PAIRS_MIN_TILES: *value = c->opt_fp6_pairs_min; break;
@@ -2389,6 +2412,226 @@ int wld_prune_times(wld_ctx *c, double *csr_ms, double *rounds_ms, double *tags_
     if (rounds_ms) *rounds_ms = c->pr_ms[1];
     if (tags_ms) *tags_ms = c->pr_ms[2];
     return WLD_OK;
+}
+
+namespace {
+// the rows of one batch on the host, in (slot, partner) order
+struct TargetCols {
+    std::vector<uint32_t> t, st, sp;
+    std::vector<float> d, dp, r2;
+};
+
+// wld_run_targets past its argument checks.  Per batch of the plan: the lists
+// up, masks zeroed, the pair launch (pair_targets.hip) between the call's two
+// events, the counts and their scans, one read of the slots' bases (the
+// batch's exact row total, before its row buffers are sized), the row launch,
+// the rows down.  Every slot's rows are one run of its batch's arrays; the
+// list order is put together on the host once every batch has been counted.
+// Uses the context's stream, the lane-class layout and the window's limits;
+// touches no tile list, staging, counter, row or event of the row path.
+int run_targets(wld_ctx *c, const uint32_t *targets, uint32_t n, float thr, wld_target_rows *out) {
+    const uint32_t L = (uint32_t)c->L, LP = (uint32_t)c->LP, T = LP / kTile;
+    const std::vector<uint32_t> no_window;
+    const bool windowed = window_on(c) && c->win_hi_host.size() == L;
+    const targets_plan::Plan p =
+        targets_plan::make(targets, n, L, LP, windowed ? c->win_hi_host : no_window, c->opt_target_slots);
+    out->items = p.items();
+    out->batches = p.batches();
+    if (!p.items()) return WLD_OK;  // (a single site, or a window that leaves no partner)
+    WLD_TRY(ensure_ref_layout(c));
+    for (auto &e : c->ev_tg)
+        if (!e) HIP_TRY(hipEventCreate(&e));
+    wld_ctx::TargetBufs &tb = c->tg;
+    const size_t n_slots_all = p.slot_site.size();
+    std::vector<TargetCols> cols(p.batches());
+    std::vector<uint64_t> slot_begin(n_slots_all, 0), slot_rows(n_slots_all, 0);  // within the slot's batch
+    std::vector<uint32_t> base;
+    double ms = 0.0;
+    for (uint32_t k = 0; k < p.batches(); ++k) {
+        const uint32_t b0 = p.batch_begin[k], nb = p.batch_begin[k + 1] - b0;
+        const size_t ns = (size_t)nb * targets_plan::kBlock;
+        const std::vector<uint32_t> items = targets_plan::batch_items(p, b0, b0 + nb);
+        const uint32_t n_items = (uint32_t)(items.size() / 2);
+        if (!n_items) continue;
+        WLD_TRY(ensure(tb.slot_site, ns * 4));
+        WLD_TRY(ensure(tb.slot_pos, ns * 4));
+        WLD_TRY(ensure(tb.items, items.size() * 4));
+        WLD_TRY(ensure(tb.d, ns * LP * 4));
+        WLD_TRY(ensure(tb.dp, ns * LP * 4));
+        WLD_TRY(ensure(tb.r2, ns * LP * 4));
+        WLD_TRY(ensure(tb.mask, ns * T * 8));
+        WLD_TRY(ensure(tb.tile_pref, ns * T * 4));
+        WLD_TRY(ensure(tb.slot_cnt, ns * 4));
+        WLD_TRY(ensure(tb.slot_base, (ns + 1) * 4));
+        WLD_TRY(ensure(tb.guard, 16));
+        TargetsLaunch t{};
+        t.rcodes = ptr<uint8_t>(c->rcodes);
+        t.rw = ptr<float>(c->rw);
+        t.site_ok = ptr<uint8_t>(c->site_ok);
+        t.win_hi = windowed ? ptr<uint32_t>(c->win_hi) : nullptr;
+        t.site_map = c->has_map ? ptr<uint32_t>(c->site_map) : nullptr;
+        t.L = L;
+        t.LP = LP;
+        t.NPr = (uint32_t)c->NPr;
+        t.ref_cs = c->ref_cls / 64;
+        t.ref_tail_n = (uint32_t)(c->N % 8);
+        t.thr = thr;
+        t.n_blocks = nb;
+        t.slot_site = ptr<uint32_t>(tb.slot_site);
+        t.slot_pos = ptr<uint32_t>(tb.slot_pos);
+        t.items = ptr<uint32_t>(tb.items);
+        t.n_items = n_items;
+        t.d = ptr<float>(tb.d);
+        t.dp = ptr<float>(tb.dp);
+        t.r2 = ptr<float>(tb.r2);
+        t.mask = ptr<unsigned long long>(tb.mask);
+        t.tile_pref = ptr<uint32_t>(tb.tile_pref);
+        t.slot_cnt = ptr<uint32_t>(tb.slot_cnt);
+        t.slot_base = ptr<uint32_t>(tb.slot_base);
+        t.guard = ptr<unsigned>(tb.guard);
+        const size_t s0 = (size_t)b0 * targets_plan::kBlock;
+        HIP_TRY(hipMemcpyAsync(tb.slot_site.p, p.slot_site.data() + s0, ns * 4, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(tb.slot_pos.p, p.slot_pos.data() + s0, ns * 4, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(tb.items.p, items.data(), items.size() * 4, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemsetAsync(tb.mask.p, 0, ns * T * 8, c->stream));
+        HIP_TRY(hipMemsetAsync(tb.guard.p, 0, 16, c->stream));
+        HIP_TRY(hipEventRecord(c->ev_tg[0], c->stream));
+        launch_targets_pairs(t, c->stream);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(c->ev_tg[1], c->stream));
+        launch_targets_count(t, c->stream);
+        HIP_TRY(hipGetLastError());
+        base.assign(ns + 1, 0);
+        unsigned guard = 0;
+        HIP_TRY(hipMemcpyAsync(base.data(), tb.slot_base.p, (ns + 1) * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(&guard, tb.guard.p, sizeof guard, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));  // (items, too, has been read)
+        ms += std::max(0.0f, event_ms(c->ev_tg[0], c->ev_tg[1]));
+        const uint64_t rows = base[ns];
+        for (size_t s = 0; s < ns; ++s) {
+            slot_begin[s0 + s] = base[s];
+            slot_rows[s0 + s] = base[s + 1] - base[s];
+        }
+        if (!guard && rows) {
+            for (DevBuf *b : {&tb.o_t, &tb.o_st, &tb.o_sp, &tb.o_d, &tb.o_dp, &tb.o_r2}) WLD_TRY(ensure(*b, rows * 4));
+            t.out_target = ptr<uint32_t>(tb.o_t);
+            t.out_site_target = ptr<uint32_t>(tb.o_st);
+            t.out_site_partner = ptr<uint32_t>(tb.o_sp);
+            t.out_d = ptr<float>(tb.o_d);
+            t.out_dp = ptr<float>(tb.o_dp);
+            t.out_r2 = ptr<float>(tb.o_r2);
+            t.out_cap = rows;
+            launch_targets_rows(t, c->stream);
+            HIP_TRY(hipGetLastError());
+            TargetCols &h = cols[k];
+            h.t.resize(rows), h.st.resize(rows), h.sp.resize(rows), h.d.resize(rows), h.dp.resize(rows), h.r2.resize(rows);
+            HIP_TRY(hipMemcpyAsync(h.t.data(), tb.o_t.p, rows * 4, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipMemcpyAsync(h.st.data(), tb.o_st.p, rows * 4, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipMemcpyAsync(h.sp.data(), tb.o_sp.p, rows * 4, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipMemcpyAsync(h.d.data(), tb.o_d.p, rows * 4, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipMemcpyAsync(h.dp.data(), tb.o_dp.p, rows * 4, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipMemcpyAsync(h.r2.data(), tb.o_r2.p, rows * 4, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipMemcpyAsync(&guard, tb.guard.p, sizeof guard, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+        }
+        if (guard)
+            return fail(WLD_E_STATE, "internal: the target kernels refused an out-of-range index (guard 0x%x: %s%s%s)",
+                        guard, guard & kTargetsGuardItem ? "work item " : "", guard & kTargetsGuardSite ? "target site " : "",
+                        guard & kTargetsGuardRow ? "row position" : "");
+    }
+    out->kernel_ms = ms;
+    // the list order: target k's rows are its slot's run of its batch's arrays
+    std::vector<uint32_t> slot_batch(n_slots_all, 0);
+    for (uint32_t k = 0; k < p.batches(); ++k)
+        for (size_t s = (size_t)p.batch_begin[k] * targets_plan::kBlock; s < (size_t)p.batch_begin[k + 1] * targets_plan::kBlock; ++s)
+            slot_batch[s] = k;
+    std::vector<size_t> slot_of(n);
+    for (size_t s = 0; s < n_slots_all; ++s)
+        if (p.slot_pos[s] != targets_plan::kNoTarget) slot_of[p.slot_pos[s]] = s;
+    for (uint32_t k = 0; k < n; ++k) out->offset[k + 1] = out->offset[k] + slot_rows[slot_of[k]];
+    const uint64_t total = out->offset[n];
+    const size_t bytes = std::max<uint64_t>(total, 1) * 4;
+    out->target = (uint32_t *)malloc(bytes);
+    out->site_target = (uint32_t *)malloc(bytes);
+    out->site_partner = (uint32_t *)malloc(bytes);
+    out->d = (float *)malloc(bytes);
+    out->d_prime = (float *)malloc(bytes);
+    out->r2 = (float *)malloc(bytes);
+    if (!out->target || !out->site_target || !out->site_partner || !out->d || !out->d_prime || !out->r2)
+        return fail(WLD_E_OOM, "host allocation of %llu target rows failed", (unsigned long long)total);
+    for (uint32_t k = 0; k < n; ++k) {
+        const size_t s = slot_of[k];
+        const uint64_t m = slot_rows[s], from = slot_begin[s], to = out->offset[k];
+        if (!m) continue;
+        const TargetCols &h = cols[slot_batch[s]];
+        memcpy(out->target + to, h.t.data() + from, m * 4);
+        memcpy(out->site_target + to, h.st.data() + from, m * 4);
+        memcpy(out->site_partner + to, h.sp.data() + from, m * 4);
+        memcpy(out->d + to, h.d.data() + from, m * 4);
+        memcpy(out->d_prime + to, h.dp.data() + from, m * 4);
+        memcpy(out->r2 + to, h.r2.data() + from, m * 4);
+    }
+    out->n = total;
+    return WLD_OK;
+}
+}  // namespace
+
+int wld_run_targets(wld_ctx *c, const uint32_t *targets, uint32_t n_targets, float r2_threshold,
+                    wld_target_rows *out) {
+    if (!out) return fail(WLD_E_ARG, "null out");
+    memset(out, 0, sizeof(*out));
+    WLD_TRY(set_dev(c));  // (a device group: WLD_E_STATE)
+    if (!c->loaded) return fail(WLD_E_STATE, "wld_run_targets before wld_load");
+    if (c->pend.active) return fail(WLD_E_STATE, "wld_run_targets during a run");
+    if (n_targets && !targets) return fail(WLD_E_ARG, "wld_run_targets: null targets with n_targets %u", n_targets);
+    if (c->safe)
+        return fail(WLD_E_ARG, "wld_run_targets needs finite weights (this load takes the select loop)");
+    const size_t L = c->L;
+    int st = WLD_OK;
+    try {
+        const targets_plan::Bad bad = targets_plan::validate(targets, n_targets, (uint32_t)L);
+        if (bad.kind == targets_plan::kOutOfRange)
+            return fail(WLD_E_ARG, "wld_run_targets: targets[%u] = %u is not a loaded site (%zu loaded)", bad.pos,
+                        targets[bad.pos], L);
+        if (bad.kind == targets_plan::kRepeated)
+            return fail(WLD_E_ARG, "wld_run_targets: targets[%u] = %u repeats targets[%u]", bad.pos, targets[bad.pos],
+                        bad.first);
+        if (n_targets && (uint64_t)n_targets * (L - 1) > targets_plan::kMaxRows)
+            return fail(WLD_E_ARG, "wld_run_targets: %u targets x %zu partners exceed 2^32 - 1 rows: split the list",
+                        n_targets, L - 1);
+        out->n_targets = n_targets;
+        out->offset = (uint64_t *)calloc((size_t)n_targets + 1, sizeof(uint64_t));
+        if (!out->offset) return fail(WLD_E_OOM, "host allocation of %u offsets failed", n_targets);
+        if (n_targets) st = run_targets(c, targets, n_targets, r2_threshold, out);
+    } catch (const std::bad_alloc &) {
+        st = fail(WLD_E_OOM, "wld_run_targets: host allocation failed");
+    }
+    // the staging goes back unless it is small (a later row run finds the
+    // memory it would have found without this call)
+    size_t held = 0;
+    for (DevBuf *b : c->tg.all()) held += b->bytes;
+    if (st != WLD_OK || held > (64u << 20)) {
+        (void)hipStreamSynchronize(c->stream);  // nothing of the call is in flight when its buffers go
+        for (DevBuf *b : c->tg.all()) release(*b);
+    }
+    if (st != WLD_OK) {
+        const std::string msg = wld_last_error();  // (wld_target_rows_free does not fail, but keep the message)
+        wld_target_rows_free(out);
+        return fail(st, "%s", msg.c_str());
+    }
+    return WLD_OK;
+}
+
+void wld_target_rows_free(wld_target_rows *r) {
+    if (!r) return;
+    free(r->offset);
+    free(r->target);
+    free(r->site_target);
+    free(r->site_partner);
+    free(r->d);
+    free(r->d_prime);
+    free(r->r2);
+    memset(r, 0, sizeof(*r));
 }
 
 int wld_all_weighted_ld_pairs(wld_ctx *c, const uint8_t *sites, size_t n_sites, size_t n_seqs,

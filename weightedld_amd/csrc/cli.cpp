@@ -27,6 +27,14 @@
 //                      minor-allele fraction first, ties to the lower index);
 //                      tag: the kept site standing for a removed one
 //                      (wld_run_prune; parent indices as in the pair TSV)
+//   --ld-sites P[,P...]      target-site LD TSV (target, site, d, d', r2): the
+//   --ld-sites-file FILE     rows of the sites at the given parent coordinates
+//   --ld-sites-output FILE   (the list, then the file's, one per line; every
+//   --ld-sites-r2 T          site of interest carrying a coordinate is a target)
+//                      against every in-window partner with r2 > T (default:
+//                      --r2-threshold's value), by target, then partner
+//                      (wld_run_targets: targets x sites pairs, not the
+//                      triangle); with it --pair-output may be left out
 #include <chrono>
 #include <cinttypes>
 #include <cmath>
@@ -211,6 +219,11 @@ struct Opt {
     std::string prune_output;  // --prune-output / --prune-r2 / --prune-priority: wld_run_prune
     bool have_prune_r2 = false, prune_maf = false;
     float prune_r2 = 0.0f;
+    // --ld-sites / --ld-sites-file / --ld-sites-output / --ld-sites-r2: wld_run_targets
+    std::vector<uint64_t> ld_sites;
+    std::string ld_sites_file, ld_sites_output;
+    bool have_ld_sites = false, have_ld_sites_r2 = false;
+    float ld_sites_r2 = 0.0f;
 };
 
 void usage(FILE *f) {
@@ -261,7 +274,15 @@ void usage(FILE *f) {
             "                                             needs --prune-r2; obeys --max-distance and --max-sites\n"
             "        --prune-r2 <prune-r2>                (addition) no two kept sites have r2 above this\n"
             "        --prune-priority <prune-priority>    (addition) index | maf: the order in which sites are kept\n"
-            "                                             [default: index]\n");
+            "                                             [default: index]\n"
+            "        --ld-sites <ld-sites>                (addition) target sites: parent coordinates \"P[,P...]\";\n"
+            "                                             every site of interest at one is a target\n"
+            "        --ld-sites-file <ld-sites-file>      (addition) more target coordinates, one per line\n"
+            "        --ld-sites-output <ld-sites-output>  (addition) Filename to write the targets' rows to (target,\n"
+            "                                             site, d, d', r2: every in-window partner above the\n"
+            "                                             threshold); --pair-output may then be left out\n"
+            "        --ld-sites-r2 <ld-sites-r2>          (addition) Minimum value of R2 of a target row [default:\n"
+            "                                             --r2-threshold's value]\n");
 }
 
 [[noreturn]] void arg_error(const char *msg, const char *arg) {
@@ -371,6 +392,25 @@ Opt parse(int argc, char **argv) {
             const std::string k = need("--prune-priority");
             if (k != "index" && k != "maf") arg_error("Invalid value for '--prune-priority':", k.c_str());
             o.prune_maf = k == "maf";
+        } else if (a == "--ld-sites") {
+            const std::string v = need("--ld-sites");
+            o.have_ld_sites = true;
+            size_t at = 0;
+            while (at <= v.size()) {
+                const size_t e = std::min(v.find(',', at), v.size());
+                const std::string t = v.substr(at, e - at);
+                if (t.empty() || t.find_first_not_of("0123456789") != std::string::npos || t.size() > 19)
+                    arg_error("Invalid value for '--ld-sites':", v.c_str());
+                o.ld_sites.push_back(strtoull(t.c_str(), nullptr, 10));
+                at = e + 1;
+            }
+        } else if (a == "--ld-sites-file") {
+            o.ld_sites_file = need("--ld-sites-file");
+        } else if (a == "--ld-sites-output") {
+            o.ld_sites_output = need("--ld-sites-output");
+        } else if (a == "--ld-sites-r2") {
+            o.ld_sites_r2 = parse_f32(need("--ld-sites-r2").c_str(), "ld-sites-r2");
+            o.have_ld_sites_r2 = true;
         } else if (a == "--kernel") {
             std::string k = need("--kernel");
             o.kernel = k == "valu" ? WLD_KERNEL_VALU : k == "mfma" ? WLD_KERNEL_MFMA : WLD_KERNEL_AUTO;
@@ -381,7 +421,17 @@ Opt parse(int argc, char **argv) {
     }
     if (o.fasta_input.empty() && o.vcf_input.empty())
         arg_error("The following required arguments were not provided:", "--fasta-input <fasta-input>");
-    if (!have_pair) arg_error("The following required arguments were not provided:", "--pair-output <pair-output>");
+    const bool ld_sel = o.have_ld_sites || !o.ld_sites_file.empty();
+    if (ld_sel && o.ld_sites_output.empty())
+        arg_error("The following required arguments were not provided:", "--ld-sites-output <ld-sites-output>");
+    if (!ld_sel && !o.ld_sites_output.empty())
+        arg_error("The argument '--ld-sites-output' needs", "--ld-sites <ld-sites> or --ld-sites-file <ld-sites-file>");
+    if (!ld_sel && o.have_ld_sites_r2) arg_error("The argument '--ld-sites-r2' needs", "--ld-sites-output <ld-sites-output>");
+    if (ld_sel && o.devices.size() > 1)
+        arg_error("The argument '--ld-sites-output' cannot be used with", "--devices (target sites run on one device)");
+    if (!have_pair && !ld_sel)
+        arg_error("The following required arguments were not provided:", "--pair-output <pair-output>");
+    if (!o.have_ld_sites_r2) o.ld_sites_r2 = o.r2_threshold;
     if (!o.decay_output.empty() && !o.decay_bin_width)
         arg_error("The following required arguments were not provided:", "--decay-bin-width <decay-bin-width>");
     if (o.decay_output.empty() && o.decay_bin_width)
@@ -623,6 +673,82 @@ void write_prune(const Opt &opt, wld_ctx *ctx, const std::vector<uint64_t> &pare
     wld_prune_free(&p);
 }
 
+// --ld-sites / --ld-sites-file: the target coordinates (the list's, then the
+// file's lines) as loaded indices — every loaded site carrying a coordinate,
+// in loaded order.  parent[i] as in write_summaries.  A coordinate no loaded
+// site carries ends the run, before any pair is computed.
+std::vector<uint32_t> resolve_targets(const Opt &opt, const std::vector<uint64_t> &parent) {
+    std::vector<uint32_t> t;
+    if (opt.ld_sites_output.empty()) return t;
+    std::vector<uint64_t> want = opt.ld_sites;
+    if (!opt.ld_sites_file.empty()) {
+        FILE *f = fopen(opt.ld_sites_file.c_str(), "rb");
+        if (!f) {
+            fprintf(stderr, "Error: cannot read %s\n", opt.ld_sites_file.c_str());
+            quit(1);
+        }
+        char line[256];
+        while (fgets(line, sizeof line, f)) {
+            std::string v(line);
+            while (!v.empty() && (v.back() == '\n' || v.back() == '\r' || v.back() == ' ' || v.back() == '\t')) v.pop_back();
+            if (v.empty()) continue;
+            if (v.find_first_not_of("0123456789") != std::string::npos || v.size() > 19) {
+                fprintf(stderr, "error: --ld-sites-file %s: '%s' is not a coordinate\n", opt.ld_sites_file.c_str(), v.c_str());
+                quit(1);
+            }
+            want.push_back(strtoull(v.c_str(), nullptr, 10));
+        }
+        fclose(f);
+    }
+    for (const uint64_t p : want) {
+        const size_t before = t.size();
+        for (size_t i = 0; i < parent.size(); ++i)
+            if (parent[i] == p) t.push_back((uint32_t)i);
+        if (t.size() == before) {
+            fprintf(stderr, "error: --ld-sites: no site of interest has coordinate %" PRIu64 "\n", p);
+            quit(1);
+        }
+    }
+    return t;
+}
+
+// --ld-sites-output: the targets' rows at --ld-sites-r2 under the window
+// (wld_run_targets), by target then partner; parent indices and the three
+// numbers formatted as the pair TSV's.
+void write_targets(const Opt &opt, wld_ctx *ctx, const std::vector<uint32_t> &targets) {
+    if (opt.ld_sites_output.empty()) return;
+    using clk = std::chrono::steady_clock;
+    const auto sw = clk::now();
+    wld_target_rows r;
+    const int st = wld_run_targets(ctx, targets.data(), (uint32_t)targets.size(), opt.ld_sites_r2, &r);
+    if (st != WLD_OK) die(st, "run_targets");
+    INFO("Computed %zu target sites: %s rows above r2 %g in %s", targets.size(), human((double)r.n).c_str(),
+         (double)opt.ld_sites_r2, fmt_duration(clk::now() - sw).c_str());
+    INFO("Writing output to %s", debug_path(opt.ld_sites_output).c_str());
+    std::string out = "target\tsite\td\td'\tr2\n";
+    char line[160];
+    for (uint64_t i = 0; i < r.n; ++i) {
+        int m = fmt_u64(line, r.site_target[i]);
+        line[m++] = '\t';
+        m += fmt_u64(line + m, r.site_partner[i]);
+        line[m++] = '\t';
+        m += fmt3(line + m, r.d[i]);
+        line[m++] = '\t';
+        m += fmt3(line + m, r.d_prime[i]);
+        line[m++] = '\t';
+        m += fmt3(line + m, r.r2[i]);
+        line[m++] = '\n';
+        out.append(line, m);
+    }
+    FILE *f = fopen(opt.ld_sites_output.c_str(), "wb");
+    const bool ok = f && fwrite(out.data(), 1, out.size(), f) == out.size();
+    if ((f && fclose(f) != 0) || !ok) {
+        fprintf(stderr, "Error: cannot write %s\n", opt.ld_sites_output.c_str());
+        quit(1);
+    }
+    wld_target_rows_free(&r);
+}
+
 // (debug level only, so info-level output is the reference's: the LD pass's
 // progress_report calls — progress(0), then one per 256x256 chunk)
 void log_progress(const ProgressBar &pb) {
@@ -634,6 +760,10 @@ void log_progress(const ProgressBar &pb) {
 int finish(const Opt &opt, wld_ctx *ctx, wld_pairs &pairs, std::chrono::steady_clock::duration dur,
            uint64_t total_pairs) {
     using clk = std::chrono::steady_clock;
+    if (opt.pair_output.empty()) {  // (--ld-sites-output alone: no pair pass ran)
+        wld_destroy(ctx);
+        return 0;
+    }
     INFO("Finished computing pairwise weighted LD stats in %s", fmt_duration(dur).c_str());
     const double secs = std::chrono::duration<double>(dur).count();
     INFO("    %s pairs computed at ~%s, %s passed threshold", human((double)total_pairs).c_str(),
@@ -677,11 +807,14 @@ int run_gpu_prepass(const Opt &opt, wld_siteset *siteset, wld_ctx *ctx) {
             quit(1);  // the context thread may still be running
         }
     }
-    INFO("Beginning pairwise weighted LD computation");
+    std::vector<uint64_t> parent(L);
+    if (L && (st = wld_site_map_copy(ctx, parent.data())) != WLD_OK) die(st, "site_map_copy");
+    const std::vector<uint32_t> targets = resolve_targets(opt, parent);
+    if (!opt.pair_output.empty()) INFO("Beginning pairwise weighted LD computation");
     sw = clk::now();
     const uint64_t total_pairs = ((uint64_t)L - 1) * ((uint64_t)L - 2) / 2;  // main.rs:168 (sic, wraps)
-    wld_pairs pairs;  // any L: batches of <= 2^31 pairs, rows appended in reference order
-    {
+    wld_pairs pairs{};  // any L: batches of <= 2^31 pairs, rows appended in reference order
+    if (!opt.pair_output.empty()) {
         ProgressBar pb(total_pairs);  // main.rs:170-178
         on_progress(0, &pb);  // all_weighted_ld_pairs' initial report (lib.rs:584); wld_run_host reports chunks only
         if ((st = wld_run_host(ctx, opt.r2_threshold, on_progress, &pb, &pairs)) != WLD_OK)
@@ -689,9 +822,8 @@ int run_gpu_prepass(const Opt &opt, wld_siteset *siteset, wld_ctx *ctx) {
         log_progress(pb);
     }
     const auto dur = clk::now() - sw;
-    std::vector<uint64_t> parent(L);
-    if (L && (st = wld_site_map_copy(ctx, parent.data())) != WLD_OK) die(st, "site_map_copy");
     write_summaries(opt, ctx, parent);
+    write_targets(opt, ctx, targets);
     // (a FASTA set has no site_map: a kept site's parent index is its index in the unfiltered set)
     write_prune(opt, ctx, parent, siteset, std::vector<size_t>(parent.begin(), parent.end()));
     return finish(opt, ctx, pairs, dur, total_pairs);
@@ -787,12 +919,18 @@ int main(int argc, char **argv) {
         }
     }
 
-    INFO("Beginning pairwise weighted LD computation");
+    std::vector<uint64_t> parent(L);
+    for (size_t i = 0; i < L; ++i) parent[i] = wld_siteset_parent_site_index(filtered, i);
+    const std::vector<uint32_t> targets = resolve_targets(opt, parent);
+    if (!opt.pair_output.empty()) INFO("Beginning pairwise weighted LD computation");
     sw = clk::now();
     const uint64_t total_pairs = ((uint64_t)L - 1) * ((uint64_t)L - 2) / 2;  // main.rs:168 (sic, wraps)
     get_ctx();
-    wld_pairs pairs;
-    {
+    wld_pairs pairs{};
+    if (opt.pair_output.empty()) {  // (--ld-sites-output alone: the load, no pair pass)
+        st = wld_load(ctx, wld_siteset_buffer(filtered), L, N, wld_siteset_site_map(filtered), weights.data());
+        if (st != WLD_OK) die(st, "load");
+    } else {
         ProgressBar pb(total_pairs);  // main.rs:170-178, fed by the closure of main.rs:184-188
         st = wld_all_weighted_ld_pairs(ctx, wld_siteset_buffer(filtered), L, N, wld_siteset_site_map(filtered),
                                        weights.data(), opt.r2_threshold, on_progress, &pb, &pairs);
@@ -800,9 +938,8 @@ int main(int argc, char **argv) {
         log_progress(pb);
     }
     const auto dur = clk::now() - sw;
-    std::vector<uint64_t> parent(L);
-    for (size_t i = 0; i < L; ++i) parent[i] = wld_siteset_parent_site_index(filtered, i);
     write_summaries(opt, ctx, parent);
+    write_targets(opt, ctx, targets);
     std::vector<size_t> self(L);
     for (size_t i = 0; i < L; ++i) self[i] = i;
     write_prune(opt, ctx, parent, filtered, self);

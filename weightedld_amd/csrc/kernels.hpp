@@ -212,6 +212,42 @@ void launch_ref_layout(const uint8_t *codes, const float *w_pad, size_t LP, size
 // nothing of the row path's run state is read or written.
 void launch_pair_summary(const ValuLaunch &v, const OrderArgs &o, const SummaryArgs &s, hipStream_t st);
 
+// pair_targets.hip (wld_run_targets): one batch of target blocks against their
+// partner tiles.  Slot 16 b + j is the j-th target of the batch's block b.
+// The pair launch writes d, d', r2 of every passing (slot, site) into the dense
+// staging and a 64-bit pass mask per (slot, partner tile) (zero before the
+// launch); the count launches give every slot's rows, their prefix over the
+// slot's tiles and over the slots; the row launch then writes the rows in
+// (slot, partner) order.
+struct TargetsLaunch {
+    const uint8_t *rcodes;  // the lane-class layout (NPr bytes per site)
+    const float *rw;
+    const uint8_t *site_ok;
+    const uint32_t *win_hi;    // the window's limits ([LP]); null: no window
+    const uint32_t *site_map;  // parent indices (L entries); null: identity
+    uint32_t L, LP, NPr, ref_cs, ref_tail_n;
+    float thr;
+    uint32_t n_blocks;           // of the batch
+    const uint32_t *slot_site;   // [16 n_blocks] loaded index of the slot's target (targets_plan::kNoTarget: empty)
+    const uint32_t *slot_pos;    // [16 n_blocks] its position in the caller's list
+    const uint32_t *items;       // n_items x {block, partner tile}
+    uint32_t n_items;
+    float *d, *dp, *r2;          // [16 n_blocks][LP]
+    unsigned long long *mask;    // [16 n_blocks][LP / 64]
+    uint32_t *tile_pref;         // [16 n_blocks][LP / 64]: the slot's rows in the tiles before
+    uint32_t *slot_cnt;          // [16 n_blocks]
+    uint32_t *slot_base;         // [16 n_blocks + 1]: the rows of the slots before; the last: the batch's rows
+    unsigned *guard;             // zero before the launches; kGuard* bits of refused indices
+    // the batch's rows (out_cap entries each)
+    uint32_t *out_target, *out_site_target, *out_site_partner;
+    float *out_d, *out_dp, *out_r2;
+    uint64_t out_cap;
+};
+constexpr unsigned kTargetsGuardItem = 1, kTargetsGuardSite = 2, kTargetsGuardRow = 4;
+void launch_targets_pairs(const TargetsLaunch &t, hipStream_t s);
+void launch_targets_count(const TargetsLaunch &t, hipStream_t s);
+void launch_targets_rows(const TargetsLaunch &t, hipStream_t s);
+
 // pair_mfma.hip
 bool mfma_supported();
 // weight digits (two layouts) + per-64-site filter bits
