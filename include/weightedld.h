@@ -248,6 +248,17 @@ int wld_set_kernel(wld_ctx *ctx, int kernel);
  *                      exact either way: same sums, candidates and rows.
  *                      Setting it discards the built images (the next run that
  *                      may screen on fp6 rebuilds them).
+ *   WLD_OPT_FP6_SHARED 1 (default, auto): where every rounded weight of a load
+ *                      is the same nonzero value (unit weights, an unweighted
+ *                      VCF, Henikoff weights of a large alignment) the fp6
+ *                      screen builds no A operand image: its kernels read the
+ *                      row tile from the B code image as well, mask it into
+ *                      the two A channels and scale the sums by the one weight
+ *                      value afterwards (a third of the operand bytes per load,
+ *                      three quarters of the bytes per stage); 0: the A image
+ *                      WLD_OPT_FP6_A4 chooses.  Every scaled sum is exact: same
+ *                      sums, candidates and rows.  Setting it discards the
+ *                      built images, as WLD_OPT_FP6_A4.
  *   WLD_OPT_TARGET_BATCH_SLOTS  wld_run_targets: the pair slots (16 x target
  *                      blocks x padded site count, three floats each) of the
  *                      dense staging one batch may use (default 2^26: 768 MiB;
@@ -278,6 +289,7 @@ int wld_set_kernel(wld_ctx *ctx, int kernel);
 #define WLD_OPT_I8_PAIRS 16
 #define WLD_OPT_FP6_A4 17
 #define WLD_OPT_TARGET_BATCH_SLOTS 18
+#define WLD_OPT_FP6_SHARED 19
 int wld_set_option(wld_ctx *ctx, int option, int64_t value);
 int wld_get_option(wld_ctx *ctx, int option, int64_t *value);
 
@@ -511,7 +523,10 @@ typedef struct {
                                  host made up from the chunk pair counts because the pass's log lacked
                                  their entries once it had completed; 0 unless the kernels' chunk
                                  accounting lost a count (the tests assert 0) */
-    int fp6_a4;              /* 1: the pass screened on fp6 (screen_fp6 == 1) with the fp4 A image (WLD_OPT_FP6_A4) */
+    int fp6_a4;              /* 1: the pass screened on fp6 (screen_fp6 == 1) with the fp4 A image (WLD_OPT_FP6_A4),
+                                or, where fp6_shared is 1, on a load whose codes would have taken it */
+    int fp6_shared;          /* 1: the pass screened on fp6 (screen_fp6 == 1) with one code image for both
+                                operands and no A image (WLD_OPT_FP6_SHARED) */
 } wld_run_stats;
 int wld_last_stats(wld_ctx *ctx, wld_run_stats *out);
 /* The fp6 screen's weight codes of the loaded set (tests, diagnostics): the

@@ -27,7 +27,7 @@ KERNEL_AUTO, KERNEL_VALU, KERNEL_MFMA = 0, 1, 2
 OPTIONS = {"prefilter": 1, "screen": 2, "tile_order": 3, "all_planes": 4, "mfma_layout": 5, "valu_plain": 6,
            "staging_rows": 7, "host_batch_pairs": 8, "ref_sums": 11, "fused_scan": 12, "screen_fp6": 13,
            "test_guard": 14, "fp6_pairs_min_tiles": 15, "i8_pairs": 16, "fp6_a4": 17,
-           "target_batch_slots": 18}
+           "target_batch_slots": 18, "fp6_shared": 19}
 
 
 class WldError(RuntimeError):
@@ -70,6 +70,7 @@ class RunStats(ctypes.Structure):
         ("fp6_sampled", ctypes.c_int),
         ("progress_filled", ctypes.c_uint64),
         ("fp6_a4", ctypes.c_int),
+        ("fp6_shared", ctypes.c_int),
     ]
 
 

@@ -133,6 +133,7 @@ struct wld_ctx {
     bool opt_i8_pairs = true;    // WLD_OPT_I8_PAIRS: the i8 screen on tile pairs (pre-multiplied images)
     int opt_fp6 = 1;             // WLD_OPT_SCREEN_FP6: 0 off, 1 auto, 2 whenever it applies, 3 auto without the sample run
     bool opt_fp6_a4 = true;      // WLD_OPT_FP6_A4: the fp6 screen's A image as fp4 where the weight codes fit e2m1
+    bool opt_fp6_shared = true;  // WLD_OPT_FP6_SHARED: no A image where the weight codes are all one code (the B image serves both operands)
     bool opt_ref_sums = true;  // WLD_OPT_REF_SUMS: lib.rs's own f32 summation order (default)
     uint64_t opt_staging_rows = 1ull << 25, opt_host_batch_pairs = 1ull << 31;
     uint64_t opt_target_slots = targets_plan::kDefaultBatchSlots;  // WLD_OPT_TARGET_BATCH_SLOTS
@@ -334,7 +335,11 @@ double ref_extra_residual(const wld_ctx *c);
 // weights, Henikoff weights of a large alignment, dyadic sets: fp6_scale.hpp
 // fp6_codes_fit_fp4) and WLD_OPT_FP6_A4 is on, the A image is built as fp4
 // nibbles of the same values: two thirds of the bytes, the same sums, one
-// image per load that every fp6 kernel reads.
+// image per load that every fp6 kernel reads.  Where every weight code is the
+// same nonzero code (unit weights, Henikoff weights of a large alignment:
+// fp6_shared_code) and WLD_OPT_FP6_SHARED is on, no A image is built at all:
+// the kernels form the A operands from the row tile's B image, whose padded
+// sequences are then coded 0, and scale the restored sums by the code's value.
 // Built at load unless WLD_OPT_SCREEN_FP6 is 0, else on the first run that
 // may screen on fp6 after the option is set.
 int fp6_prepare(wld_ctx *c) {
@@ -370,25 +375,32 @@ int fp6_prepare(wld_ctx *c) {
     const double r8 = (top > 0 ? (double)c->wst.resid[top - 1] : 0.0) + ref_extra_residual(c);
     c->i8_rel = r8 / std::max(std::ldexp((double)c->wst.dsum[top], 8 * (int)top), 1e-300);
     c->f6.a4 = c->opt_fp6_a4 && fp6_codes_fit_fp4(codes.data(), c->N);
+    const uint32_t one = c->opt_fp6_shared ? fp6_shared_code(codes.data(), c->N) : 0u;
+    c->f6.shared = one != 0u;
+    c->f6.wv = (float)fp6_value(one);
     WLD_TRY(ensure(c->w6, c->NP));
-    WLD_TRY(ensure(c->f6a, fp6_a_bytes(c->LP, c->NP, c->f6.a4)));
+    if (c->f6.shared)
+        release(c->f6a);  // (an earlier load's, or the same load's before the option was set)
+    else
+        WLD_TRY(ensure(c->f6a, fp6_a_bytes(c->LP, c->NP, c->f6.a4)));
     WLD_TRY(ensure(c->f6b, fp6_b_bytes(c->LP, c->NP)));
     WLD_TRY(ensure(c->f6marg, 2 * c->LP * sizeof(float)));
     // (codes: zero past N, which the complement coding needs, pair_mfma.hip frag6_kernel)
     HIP_TRY(hipMemcpyAsync(c->w6.p, codes.data(), c->NP, hipMemcpyHostToDevice, c->stream));
     std::vector<uint8_t> codes4;  // (outlives the copy: the stream is synchronized below)
-    if (c->f6.a4) {
+    if (c->f6.a4 && !c->f6.shared) {
         codes4.resize(c->NP);
         for (size_t k = 0; k < c->NP; ++k) codes4[k] = (uint8_t)fp6_to_fp4_code(codes[k]);
         WLD_TRY(ensure(c->w4, c->NP));
         HIP_TRY(hipMemcpyAsync(c->w4.p, codes4.data(), c->NP, hipMemcpyHostToDevice, c->stream));
     }
-    launch_frag6(ptr<uint8_t>(c->codes), ptr<uint8_t>(c->w6), ptr<uint8_t>(c->f6.a4 ? c->w4 : c->w6), c->f6.a4, c->LP,
-                 c->NP, ptr<uint8_t>(c->f6a), ptr<uint8_t>(c->f6b), ptr<float>(c->f6marg), c->stream);
+    launch_frag6(ptr<uint8_t>(c->codes), ptr<uint8_t>(c->w6), ptr<uint8_t>(c->f6.a4 ? c->w4 : c->w6), c->f6.a4,
+                 c->f6.shared, c->LP, c->NP, c->N, ptr<uint8_t>(c->f6a), ptr<uint8_t>(c->f6b), ptr<float>(c->f6marg),
+                 c->stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(c->stream));
-    c->f6.a6 = ptr<uint8_t>(c->f6a);
     c->f6.b6 = ptr<uint8_t>(c->f6b);
+    c->f6.a6 = c->f6.shared ? c->f6.b6 : ptr<uint8_t>(c->f6a);  // (shared: the row tiles are read from b6)
     c->f6.marg = ptr<float>(c->f6marg);
     c->fp6_ok = true;
     c->fp6_better = c->fp6_rel <= std::max(2.0 * c->i8_rel, 0.02);
@@ -1021,6 +1033,11 @@ int wld_set_option(wld_ctx *c, int option, int64_t value) {
             // the A image's format may change: rebuilt by the next run that may screen on fp6
             c->fp6_ok = c->fp6_better = c->fp6_tried = false;
             break;
+        case WLD_OPT_FP6_SHARED:
+            c->opt_fp6_shared = value != 0;
+            // the operand images may change: rebuilt by the next run that may screen on fp6
+            c->fp6_ok = c->fp6_better = c->fp6_tried = false;
+            break;
         default: return fail(WLD_E_ARG, "unknown option %d", option);
     }
     return WLD_OK;
@@ -1134,6 +1151,7 @@ int wld_get_option(wld_ctx *c, int option, int64_t *value) {
         case WLD_OPT_SCREEN_FP6: *value = c->opt_fp6; break;
         case WLD_OPT_I8_PAIRS: *value = c->opt_i8_pairs; break;
         case WLD_OPT_FP6_A4: *value = c->opt_fp6_a4; break;
+        case WLD_OPT_FP6_SHARED: *value = c->opt_fp6_shared; break;
         default: return fail(WLD_E_ARG, "unknown option %d", option);
     }
     return WLD_OK;
@@ -1672,6 +1690,7 @@ int run_complete(wld_ctx *c, uint64_t *n_rows) {
     c->stats.screen_fp6 = screen_policy::stat_screen_fp6(route) ? 1 : abandoned ? 2 : 0;
     c->stats.fp6_sampled = c->fp6_sampled ? 1 : 0;
     c->stats.fp6_a4 = c->stats.screen_fp6 == 1 && c->f6.a4 ? 1 : 0;
+    c->stats.fp6_shared = c->stats.screen_fp6 == 1 && c->f6.shared ? 1 : 0;
     c->stats.candidate_pairs = cand_pairs ? h[0] : 0;
     // auto: what this pass's counts teach the policy (screen_policy.hpp: the break-evens)
     screen_policy::learn(c->learned, screen_policy::Outcome{route, r.thr, false, h[2], c->n_tiles, h[0], r.pairs});

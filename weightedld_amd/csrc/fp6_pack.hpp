@@ -1,5 +1,6 @@
-// The fp6 screen's operand packing for one lane (pair_mfma.hip frag6_kernel;
-// tests/cpp/f6_a4_check.cpp runs the same code on the host): a lane of the
+// The fp6 screen's operand packing for one lane (pair_mfma.hip frag6_kernel,
+// frag6_shared_kernel; tests/cpp/f6_a4_check.cpp and f6_shared_check.cpp run
+// the same code on the host): a lane of the
 // MFMA's 16 x 128 operand holds one site's 32 consecutive sequences, sequence j
 // at bits 6 j of six dwords (e2m3, the fp6 A image) or at bits 4 j of four
 // (e2m1: the B image, and the fp4 A image of a load whose weight codes all fit
@@ -47,6 +48,22 @@ WLD_HD inline void f6_pack_lane(const uint8_t *sym, const uint8_t *wa, uint32_t 
             }
         }
         if (j < n) b[j >> 3] |= ((c & kF6SymIn) ? ((c & kF6SymMaj) ? 0u : 2u) : 4u) << (4 * (j & 7));
+    }
+}
+
+// The shared image's lane (a load whose weight codes are all one code,
+// fp6_scale.hpp fp6_shared_code): the B nibbles alone, which the kernels read
+// for both operands.  n counts the lane's real sequences (below N, not NP): a
+// padded sequence is coded 0 here, not missing, because no A image's zero
+// weight nulls it; with 0 it adds to none of the four products from either
+// side.  The row tile's A channels are two masks of these dwords: missing at
+// 2.0 (0x4 nibbles), minor at 1.0 (0x2 nibbles, the mask the B side applies).
+constexpr uint32_t kF6MaskMissing = 0x44444444u, kF6MaskMinor = 0x22222222u;
+WLD_HD inline void f6_pack_lane_shared(const uint8_t *sym, uint32_t n, uint32_t (&b)[4]) {
+    for (int d = 0; d < 4; ++d) b[d] = 0u;
+    for (uint32_t j = 0; j < n && j < 32; ++j) {
+        const uint32_t c = sym[j];
+        b[j >> 3] |= ((c & kF6SymIn) ? ((c & kF6SymMaj) ? 0u : 2u) : 4u) << (4 * (j & 7));
     }
 }
 

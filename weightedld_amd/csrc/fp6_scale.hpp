@@ -102,5 +102,19 @@ inline bool fp6_codes_fit_fp4(const uint8_t *w6, size_t N) {
         if (fp6_to_fp4_code(w6[k]) < 0) return false;
     return true;
 }
+// The one nonzero e2m3 code that all N weight codes of a load share (unit
+// weights, Henikoff weights of a large alignment: the scale rule puts either
+// on 4.0), or 0 where they differ, one of them is 0, or N is 0.  With one
+// weight value v the A image is a function of the B image: its channels are v
+// [missing] and v [minor], B's nibbles 2.0 [missing] + 1.0 [minor], so two
+// masks of the row tile's B image give them at the weights 2.0 and 1.0, and v
+// enters the restored sums as a scale (pair_mfma.hip, WLD_OPT_FP6_SHARED;
+// pair_common.hpp f6s_direct).  Any code serves, e2m1 value or not.
+inline uint32_t fp6_shared_code(const uint8_t *w6, size_t N) {
+    if (N == 0 || w6[0] == 0u || w6[0] >= 32u) return 0u;
+    for (size_t k = 1; k < N; ++k)
+        if (w6[k] != w6[0]) return 0u;
+    return w6[0];
+}
 
 }  // namespace wld

@@ -299,14 +299,21 @@ struct Fp6Screen {
     // fp6_scale.hpp fp6_codes_fit_fp4, and WLD_OPT_FP6_A4 on): 8 KB per tile
     // and 128 sequences instead of 12, the same products and sums
     bool a4;
+    // no A image: every weight code of the load is the one code of value wv
+    // (fp6_scale.hpp fp6_shared_code, and WLD_OPT_FP6_SHARED on), a6 is b6,
+    // the kernels mask the row tile's B image into the A operands and scale
+    // the restored sums by wv; the padded sequences are coded 0 in b6
+    bool shared;
+    float wv;
 };
 size_t fp6_a_bytes(size_t LP, size_t NP, bool a4);
 size_t fp6_b_bytes(size_t LP, size_t NP);
 // w6: NP fp6 (e2m3) codes of the rounded weights (0 for padding: a padded
 // sequence reads as missing and must weigh nothing); wa: the codes the A
-// image holds, w6 itself or (a4) their e2m1 codes; marg: 2 LP floats
-void launch_frag6(const uint8_t *codes, const uint8_t *w6, const uint8_t *wa, bool a4, size_t LP, size_t NP,
-                  uint8_t *a6, uint8_t *b6, float *marg, hipStream_t s);
+// image holds, w6 itself or (a4) their e2m1 codes; marg: 2 LP floats.
+// shared: b6 alone is built (a6, wa unused), the N real sequences' symbols
+void launch_frag6(const uint8_t *codes, const uint8_t *w6, const uint8_t *wa, bool a4, bool shared, size_t LP,
+                  size_t NP, size_t N, uint8_t *a6, uint8_t *b6, float *marg, hipStream_t s);
 
 // The i8 one-plane screen's pre-multiplied operand images (pair_mfma.hip
 // pair_i8_screen2w_kernel; capi.hip i8img_prepare): A = the top weight digit

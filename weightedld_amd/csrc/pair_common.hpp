@@ -268,6 +268,23 @@ __host__ __device__ __forceinline__ void f6c_direct(float &x0, float &y0, float 
     y0 = mb - y0;
     x1 = ma2 - x1;
 }
+// The same from the shared image's accumulators (pair_mfma.hip, a load whose
+// weight codes are all the one value v): the A operands are masks of the row
+// tile's B image, missing at 2.0 and minor at 1.0, so the four accumulators
+// hold counts, 2 (2 C00 + C01), 2 C01, 2 C10 + C11 and C11 with C = sum_k
+// (miss | minor of a)_k (miss | minor of b)_k, and aX = (v/2) acc, aY = (v/2)
+// acc, bX = v acc, bY = v acc.  Every count is an integer of at most 2^16 (4 x
+// 16384) and v, v/2 have at most 4 significant bits, so each product is exact
+// and each fmaf below rounds an exactly representable value (f6c_direct's
+// argument): X0, Y0, X1, Y1 are f6c_direct's bit for bit
+// (tests/cpp/f6_shared_check.cpp).  hv = v / 2.
+__host__ __device__ __forceinline__ void f6s_direct(float &x0, float &y0, float &x1, float &y1, float row, float col,
+                                                    float ma2, float mb, float v, float hv) {
+    x0 = fmaf(hv, x0, row + col);
+    y0 = fmaf(-hv, y0, mb);
+    x1 = fmaf(-v, x1, ma2);
+    y1 = v * y1;
+}
 __host__ __device__ __forceinline__ float r2_screen_violation(float T, float A, float B, float AB, float R,
                                                               float thr_c) {
     float E, mloc, t2;

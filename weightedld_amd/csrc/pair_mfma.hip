@@ -908,6 +908,22 @@ __global__ __launch_bounds__(64 * GroupShape<NPL>::kWaves, GroupShape<NPL>::kWgP
 // A operand registers instead of 24 and 8 operand dwords per MFMA instead of
 // 10 (round 10: C4 screen launch -5.0%, bench step -6.5%, C5 -7.2%;
 // profiles/r10a/).
+// Where every w6 of a load is the same nonzero code of value v (the same two
+// kinds of load: fp6_scale.hpp fp6_shared_code, WLD_OPT_FP6_SHARED) the A
+// image is a function of the B image, A = v [missing], v [minor] against B =
+// 2.0 [missing] + 1.0 [minor], and is not built: the kernels' kF6Shared
+// instantiations copy the row tile's B image in its place (a6 = b6), read each
+// row block raw and mask it, & 0x44444444 the missing channel at 2.0, &
+// 0x22222222 the minor channel at 1.0 (f6_ld_rows), so the accumulators hold
+// 2 (2 C00 + C01), 2 C01, 2 C10 + C11, C11 in counts, and f6c_rebuild
+// multiplies them by v / 2, v / 2, v, v inside its adds (pair_common.hpp
+// f6s_direct: exact, the same X0, Y0, X1, Y1 bit for bit).  The padded
+// sequences are coded 0 in this image (frag6_shared_kernel): no zero weight
+// on an A side nulls them.  Per tile-pair stage 12 KB instead of 16 (three
+// LDS-DMA pieces per wave), 6 LDS reads per wave instead of 8, 16 more v_and,
+// A nibbles with one set bit instead of two, and one 20.5-MB image per C4
+// load instead of 61 MB (round 12: C4 screen launch -2.0%, bench step -2.9%,
+// L2 fetch -45%, LDS cycles -22%; profiles/r12a/).
 // Single tiles (pair_fp6_screen_kernel): one 64x64 tile per 4-wave workgroup,
 // four per CU; per 128 sequences the waves LDS-DMA the row tile's A image and
 // the column tile's B image (16 1-KB pieces) into a double-buffered 16 KB
@@ -920,16 +936,20 @@ __global__ __launch_bounds__(64 * GroupShape<NPL>::kWaves, GroupShape<NPL>::kWgP
 // plane copied into LDS beside B, a larger stage; DESIGN.md Appendix A.)
 constexpr int kF6BBytes = 1024;                         // per 16-site block: B (fp4 codes)
 constexpr int kF6BStage = 4 * kF6BBytes;                // a tile's B image per 128 sequences
-// The A image's format (kA4: fp4 nibbles, a load whose weight codes all fit
-// e2m1; else fp6) and the stage constants that follow from it.
-template <bool kA4>
+// The A operand's source (kF6A6: the fp6 A image; kF6A4: fp4 nibbles, a load
+// whose weight codes all fit e2m1; kF6Shared: no A image, the row tile's B
+// image masked, a load whose weight codes are all one code) and the stage
+// constants that follow from it.
+enum : int { kF6A6 = 0, kF6A4 = 1, kF6Shared = 2 };
+template <int kFmt>
 struct F6Fmt {
+    static constexpr bool kA4 = kFmt == kF6A4, kShared = kFmt == kF6Shared;
     static constexpr int kChan = kA4 ? 1024 : 1536;     // per 16-site block: one A channel
-    static constexpr int kABytes = 2 * kChan;           // ... and both
+    static constexpr int kABytes = kShared ? kF6BBytes : 2 * kChan;  // ... and both (shared: the block's B image)
     static constexpr int kAStage = 4 * kABytes;         // a tile's A image per 128 sequences
     static constexpr int kStage = kAStage + kF6BStage;  // a single tile's stage
     static constexpr int kPStage = kAStage + 2 * kF6BStage;  // a tile pair's
-    static constexpr int kCbsz = kA4 ? 4 : 2;           // the MFMA's A format: fp4 (e2m1) / fp6 (e2m3)
+    static constexpr int kCbsz = kFmt == kF6A6 ? 2 : 4;  // the MFMA's A format: fp6 (e2m3) / fp4 (e2m1)
 };
 typedef int v8i __attribute__((ext_vector_type(8)));
 typedef float v4f __attribute__((ext_vector_type(4)));
@@ -945,7 +965,7 @@ template <bool kA4>
 __global__ __launch_bounds__(256) void frag6_kernel(const uint8_t *__restrict__ codes, const uint8_t *__restrict__ wa,
                                                      uint32_t LP, uint32_t NP, uint8_t *__restrict__ a6,
                                                      uint8_t *__restrict__ b6) {
-    using F = F6Fmt<kA4>;
+    using F = F6Fmt<kA4 ? kF6A4 : kF6A6>;
     const uint32_t NK = (NP + 127) / 128;
     const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (idx >= (size_t)LP / 16 * NK * 64) return;
@@ -975,6 +995,31 @@ __global__ __launch_bounds__(256) void frag6_kernel(const uint8_t *__restrict__ 
         *reinterpret_cast<uint2 *>(pm + 1024 + 8 * lane) = make_uint2(am[4], am[5]);
     }
     *reinterpret_cast<uint4 *>(pb + 16 * lane) = make_uint4(b[0], b[1], b[2], b[3]);
+}
+// The shared image (a load whose weight codes are all one code): the B image
+// alone, in frag6_kernel's layout and thread map, with the padded sequences
+// (N <= k < NP) coded 0 instead of missing: the kernels read this image for
+// both operands, so no zero weight code on an A side nulls them
+// (fp6_pack.hpp f6_pack_lane_shared).
+__global__ __launch_bounds__(256) void frag6_shared_kernel(const uint8_t *__restrict__ codes, uint32_t LP, uint32_t NP,
+                                                            uint32_t N, uint8_t *__restrict__ b6) {
+    const uint32_t NK = (NP + 127) / 128;
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (size_t)LP / 16 * NK * 64) return;
+    const uint32_t lane = idx & 63, blk = (idx >> 6) & 3;
+    const size_t tk = idx >> 8, tile = tk / NK;  // tk = tile * NK + kb
+    const uint32_t kb = (uint32_t)(tk % NK);
+    const uint32_t k0 = 128 * kb + 32 * (lane >> 4);
+#ifdef WLD_EXP_ZERO_IMG  // diagnostic: all-zero operand images, the same instruction stream
+    const uint32_t n = 0u;
+#else
+    const uint32_t n = k0 < N ? min(32u, N - k0) : 0u;
+#endif
+    // (n = 0: nothing is read, the row pointer is not formed past the array)
+    const uint8_t *row = codes + (tile * 64 + blk * 16 + (lane & 15)) * (size_t)NP + (n ? k0 : 0u);
+    uint32_t b[4];
+    f6_pack_lane_shared(row, n, b);
+    *reinterpret_cast<uint4 *>(b6 + tk * kF6BStage + blk * kF6BBytes + 16 * lane) = make_uint4(b[0], b[1], b[2], b[3]);
 }
 
 // The complement coding's per-site marginals (pair_common.hpp f6c_direct):
@@ -1027,12 +1072,30 @@ __device__ __forceinline__ v8i f6_ldb(const uint8_t *p, uint32_t lane) {
 }
 // one A channel of a 16-site block in the image's format: the fp4 image's is
 // laid out as a B block (one ds_read_b128)
-template <bool kA4>
+template <int kFmt>
 __device__ __forceinline__ v8i f6_lda(const uint8_t *p, uint32_t lane) {
-    if constexpr (kA4)
+    if constexpr (kFmt == kF6A4)
         return f6_ldb(p, lane);
     else
         return f6_ld24(p, lane);
+}
+// A 16-site row block's two A channels in the image's format.  The shared
+// image has none of its own: the block's B dwords are read raw (one
+// ds_read_b128) and masked, missing (0x4 nibbles: 2.0) into ai, minor (0x2:
+// 1.0) in place into am; what the operands' weights 2.0 and 1.0 leave out of
+// the weight v is restored with the sums (f6c_rebuild).
+template <int kFmt>
+__device__ __forceinline__ void f6_ld_rows(const uint8_t *p, uint32_t lane, v8i &ai, v8i &am) {
+    if constexpr (kFmt == kF6Shared) {
+        am = f6_ldb(p, lane);
+        ai = v8i{am[0] & (int)kF6MaskMissing, am[1] & (int)kF6MaskMissing, am[2] & (int)kF6MaskMissing,
+                 am[3] & (int)kF6MaskMissing, 0, 0, 0, 0};
+        am = v8i{am[0] & (int)kF6MaskMinor, am[1] & (int)kF6MaskMinor, am[2] & (int)kF6MaskMinor,
+                 am[3] & (int)kF6MaskMinor, 0, 0, 0, 0};
+    } else {
+        ai = f6_lda<kFmt>(p, lane);
+        am = f6_lda<kFmt>(p + F6Fmt<kFmt>::kChan, lane);
+    }
 }
 // one B block's four MFMAs against the wave's A channels (missing: ai, minor: am):
 // acc[channel_a][0 / 1] = X / Y (B raw: 2 missing + minor, B's minor bit)
@@ -1118,8 +1181,11 @@ struct F6Epi {
 // summed (pair_common.hpp f6c_direct).  sA / sB: the row tile's and the
 // column tile's 64 x {M, m} in LDS (staged with the entry's first stage, read
 // only here: 12 sites per lane, no register held across the stage loop).
+// kShared: the accumulators are the shared image's counts, scaled by the
+// load's one weight value wv on the way (f6s_direct: the same four values).
+template <bool kShared>
 __device__ __forceinline__ void f6c_rebuild(v4f (&acc)[4][2][2], const float2 *sA, const float2 *sB, uint32_t wq,
-                                            uint32_t lane, float W6) {
+                                            uint32_t lane, float W6, float wv) {
     float col[4], mb[4];
 #pragma unroll
     for (int n = 0; n < 4; ++n) {
@@ -1134,7 +1200,13 @@ __device__ __forceinline__ void f6c_rebuild(v4f (&acc)[4][2][2], const float2 *s
 #pragma unroll
         for (int n = 0; n < 4; ++n) {
             float x0 = acc[n][0][0][e], y0 = acc[n][0][1][e], x1 = acc[n][1][0][e];
-            f6c_direct(x0, y0, x1, row, col[n], ma2, mb[n]);
+            if constexpr (kShared) {
+                float y1 = acc[n][1][1][e];
+                f6s_direct(x0, y0, x1, y1, row, col[n], ma2, mb[n], wv, 0.5f * wv);
+                acc[n][1][1][e] = y1;
+            } else {
+                f6c_direct(x0, y0, x1, row, col[n], ma2, mb[n]);
+            }
             acc[n][0][0][e] = x0;
             acc[n][0][1][e] = y0;
             acc[n][1][0][e] = x1;
@@ -1144,17 +1216,19 @@ __device__ __forceinline__ void f6c_rebuild(v4f (&acc)[4][2][2], const float2 *s
 }  // namespace
 
 // one 64x64 tile per 4-wave workgroup, four per CU (tile lists past 2^15
-// tile columns, and WLD_OPT_FP6_PAIRS_MIN_TILES's smaller lists); kA4: the
-// load's A image is fp4 (12-KB stages, three pieces per wave)
-template <bool kA4>
+// tile columns, and WLD_OPT_FP6_PAIRS_MIN_TILES's smaller lists); kF6A4: the
+// load's A image is fp4 (12-KB stages, three pieces per wave); kF6Shared: a6
+// is b6, the row tile's B image stands for the A image (8-KB stages, two
+// pieces per wave) and wv is the load's one weight value
+template <int kFmt>
 __global__ __launch_bounds__(256, 4) void pair_fp6_screen_kernel(const uint8_t *__restrict__ a6,
                                                                   const uint8_t *__restrict__ b6,
                                                                   const float2 *__restrict__ marg, float W6,
                                                                   const uint64_t *__restrict__ ok_bits,
                                                                   const uint32_t *__restrict__ tiles, uint32_t n_tiles,
                                                                   uint32_t NK, uint32_t L, uint32_t n_chunk_rows,
-                                                                  float thr, OrderArgs o, ScreenArgs sc) {
-    using F = F6Fmt<kA4>;
+                                                                  float thr, OrderArgs o, ScreenArgs sc, float wv) {
+    using F = F6Fmt<kFmt>;
     constexpr int kF6AStage = F::kAStage, kF6ABytes = F::kABytes, kF6Stage = F::kStage;
     __shared__ __attribute__((aligned(16))) uint8_t smem[2 * kF6Stage];
     __shared__ float2 sMarg[2 * kTile];  // {M, m} of the row tile's sites, then the column tile's
@@ -1219,14 +1293,15 @@ __global__ __launch_bounds__(256, 4) void pair_fp6_screen_kernel(const uint8_t *
         }
         if (kb + 1 < NK) issue(kb + 1, buf ^ 1);
         const uint8_t *g = smem + buf * kF6Stage;
-        const v8i ai = f6_lda<kA4>(g + wave * kF6ABytes, lane), am = f6_lda<kA4>(g + wave * kF6ABytes + F::kChan, lane);
+        v8i ai, am;
+        f6_ld_rows<kFmt>(g + wave * kF6ABytes, lane, ai, am);
 #pragma unroll
         for (int n = 0; n < 4; ++n)
             f6_block_mfma<F::kCbsz>(acc[n], ai, am, f6_ldb(g + kF6AStage + n * kF6BBytes, lane));
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // reads of this buffer done before the next barrier
         buf ^= 1;
     }
-    f6c_rebuild(acc, sMarg, sMarg + kTile, wave, lane, W6);
+    f6c_rebuild<F::kShared>(acc, sMarg, sMarg + kTile, wave, lane, W6, wv);
     const F6Epi ep{ta, tb, wave, lane, okA, okB, 2.0f * sc.Rf, thr * (1.0f - 0x1p-7f), sc.E, sc.mloc};
     const bool cand = ep.any(acc);
     if (sc.probe) {  // the sample run: count, decide nothing
@@ -1264,8 +1339,14 @@ constexpr uint32_t kF6Single = 0x8000u;  // (= tile_order::kSingleEntry)
 // (per MFMA 0.31 KB of LDS reads); 128 accumulator registers per lane.  Each
 // half decides its own tile; a single entry's second half computes on the
 // first B image and decides nothing (it keeps the workgroup's barriers).
-// kA4 (the load's A image is fp4): 8 KB of A, two 16-KB stage buffers, wave w
-// copies A pieces w and w + 4.
+// kF6A4 (the load's A image is fp4): 8 KB of A, two 16-KB stage buffers, wave
+// w copies A pieces w and w + 4.
+// kF6Shared (the load's weight codes are all one code, value wv; a6 is b6):
+// the row tile's 4-KB B image stands for the A image, two 12-KB stage
+// buffers, three pieces per wave; each wave reads its two row blocks raw (two
+// ds_read_b128) and masks them into the four A operands (f6_ld_rows), so the
+// stage has 6 LDS reads per wave instead of 8 and 16 more v_and; the
+// accumulators hold counts, which f6c_rebuild scales by wv.
 // (Measured and removed: eight waves of 16 x 64, three stage buffers, a
 // producer/consumer split, register-staged operands (round 5); tile triples
 // on six waves, two workgroups per CU (+43%), and the full-tile bound on
@@ -1279,13 +1360,13 @@ extern "C" int wld_debug_f6_clock(unsigned long long *out) {
     return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(gF6Clock), sizeof(gF6Clock));
 }
 #endif
-template <bool kA4>
+template <int kFmt>
 __global__ __launch_bounds__(256, 3) void pair_fp6_screen2w_kernel(
     const uint8_t *__restrict__ a6, const uint8_t *__restrict__ b6, const float2 *__restrict__ marg, float W6,
     const uint64_t *__restrict__ ok_bits,
     const uint32_t *__restrict__ pairs, uint32_t n_pairs, uint32_t NK, uint32_t L, uint32_t n_chunk_rows, float thr,
-    OrderArgs o, ScreenArgs sc) {
-    using F = F6Fmt<kA4>;
+    OrderArgs o, ScreenArgs sc, float wv) {
+    using F = F6Fmt<kFmt>;
     constexpr int kF6AStage = F::kAStage, kF6ABytes = F::kABytes, kF6PStage = F::kPStage;
     __shared__ __attribute__((aligned(16))) uint8_t smem[2 * kF6PStage];
     __shared__ float2 sMarg[3 * kTile];  // {M, m} of the row tile's sites, then each half's column tile's
@@ -1302,8 +1383,10 @@ __global__ __launch_bounds__(256, 3) void pair_fp6_screen2w_kernel(
     // + 1 16-19): wave w copies w, w + 4, w + 8 of A and piece w of each B
     // image (a single entry's second image is the first's, which its idle
     // half reads)
-    // (the fp4 A image is eight pieces: w and w + 4, four pieces per wave)
-    static_assert(kF6AStage == (kA4 ? 2 : 3) * 4096 && kF6BStage == 4096, "five (fp4 A: four) pieces per wave and stage");
+    // (the fp4 A image is eight pieces: w and w + 4, four pieces per wave;
+    // the shared image's row tile four: w alone, three per wave)
+    constexpr int kAPieces = kFmt == kF6A6 ? 3 : kFmt == kF6A4 ? 2 : 1;  // per wave
+    static_assert(kF6AStage == kAPieces * 4096 && kF6BStage == 4096, "five (fp4 A: four, shared: three) pieces per wave and stage");
     struct Src {
         const uint8_t *pA, *pB0, *pB1;
     };
@@ -1320,8 +1403,8 @@ __global__ __launch_bounds__(256, 3) void pair_fp6_screen2w_kernel(
         const uint8_t *a = sr.pA + (size_t)kb * kF6AStage;
         const size_t bo = (size_t)kb * kF6BStage;
         glds16_s(a, lane16, gb);
-        glds16_s(a + 4096, lane16, gb + 4096);
-        if (!kA4) glds16_s(a + 8192, lane16, gb + 8192);
+        if (kAPieces > 1) glds16_s(a + 4096, lane16, gb + 4096);
+        if (kAPieces > 2) glds16_s(a + 8192, lane16, gb + 8192);
         glds16_s(sr.pB0 + bo, lane16, gb + kF6AStage);
         glds16_s(sr.pB1 + bo, lane16, gb + kF6AStage + kF6BStage);
     };
@@ -1384,9 +1467,9 @@ __global__ __launch_bounds__(256, 3) void pair_fp6_screen2w_kernel(
             // left the read's latency exposed; profiles/r06k/.  Reading row
             // block 0's A and B block 0 first, or the next stage's copies
             // issued after the reads, measured no better: profiles/r06l/)
-            const v8i ai0 = f6_lda<kA4>(g + aoff, lane), am0 = f6_lda<kA4>(g + aoff + F::kChan, lane);
-            const v8i ai1 = f6_lda<kA4>(g + aoff + kF6ABytes, lane),
-                      am1 = f6_lda<kA4>(g + aoff + kF6ABytes + F::kChan, lane);
+            v8i ai0, am0, ai1, am1;
+            f6_ld_rows<kFmt>(g + aoff, lane, ai0, am0);
+            f6_ld_rows<kFmt>(g + aoff + kF6ABytes, lane, ai1, am1);
             const v4f kZero = {0.0f, 0.0f, 0.0f, 0.0f};
             v8i bs[2] = {f6_ldb(g + boff, lane), f6_ldb(g + boff + kF6BBytes, lane)};
 #pragma unroll
@@ -1425,8 +1508,8 @@ __global__ __launch_bounds__(256, 3) void pair_fp6_screen2w_kernel(
         const F6Epi ep0{ta, tb, 2 * rp, lane, okA, okB, 2.0f * sc.Rf, thr * (1.0f - 0x1p-7f), sc.E, sc.mloc};
         const F6Epi ep1{ta, tb, 2 * rp + 1, lane, okA, okB, 2.0f * sc.Rf, thr * (1.0f - 0x1p-7f), sc.E, sc.mloc};
         if (!idle) {
-            f6c_rebuild(acc[0], sMarg, sMarg + kTile * (1 + half), 2 * rp, lane, W6);
-            f6c_rebuild(acc[1], sMarg, sMarg + kTile * (1 + half), 2 * rp + 1, lane, W6);
+            f6c_rebuild<F::kShared>(acc[0], sMarg, sMarg + kTile * (1 + half), 2 * rp, lane, W6, wv);
+            f6c_rebuild<F::kShared>(acc[1], sMarg, sMarg + kTile * (1 + half), 2 * rp + 1, lane, W6, wv);
         }
         const bool cand = !idle && (ep0.any(acc[0]) || ep1.any(acc[1]));
         if (cand) sCand[half] = 1u;  // (benign race: every writer stores 1)
@@ -1629,11 +1712,13 @@ __global__ __launch_bounds__(256, 3) void pair_i8_screen2w_kernel(
     if (!idle) screen_verdict(mine ? (uint32_t)sMask[half] : 0u, ta, tb, ltid, n_chunk_rows, o, sc);
 }
 
-void launch_frag6(const uint8_t *codes, const uint8_t *w6, const uint8_t *wa, bool a4, size_t LP, size_t NP,
-                  uint8_t *a6, uint8_t *b6, float *marg, hipStream_t s) {
+void launch_frag6(const uint8_t *codes, const uint8_t *w6, const uint8_t *wa, bool a4, bool shared, size_t LP,
+                  size_t NP, size_t N, uint8_t *a6, uint8_t *b6, float *marg, hipStream_t s) {
     const size_t n = LP / 16 * ((NP + 127) / 128) * 64;
     const dim3 grid((unsigned)((n + 255) / 256));
-    if (a4)
+    if (shared)
+        hipLaunchKernelGGL(frag6_shared_kernel, grid, dim3(256), 0, s, codes, (uint32_t)LP, (uint32_t)NP, (uint32_t)N, b6);
+    else if (a4)
         hipLaunchKernelGGL(frag6_kernel<true>, grid, dim3(256), 0, s, codes, wa, (uint32_t)LP, (uint32_t)NP, a6, b6);
     else
         hipLaunchKernelGGL(frag6_kernel<false>, grid, dim3(256), 0, s, codes, wa, (uint32_t)LP, (uint32_t)NP, a6, b6);
@@ -1791,29 +1876,31 @@ void fp6_screen_args(const MfmaLaunch &m, ScreenArgs &sc) {
 }
 // the fp6 screen over the pair list (or the tile list), every entry, or with
 // sc.probe every stride-th one, on the kernels of the load's A format
-template <bool kA4>
+template <int kFmt>
 void launch_fp6_screen_fmt(const MfmaLaunch &m, const uint64_t *ok_bits, const OrderArgs &o, const ScreenArgs &sc,
                            uint32_t stride, hipStream_t s) {
     if (m.f6_pairs) {
         // (a tile group per workgroup, the XCD-ordered group list)
-        hipLaunchKernelGGL(pair_fp6_screen2w_kernel<kA4>, dim3((m.f6_n_pairs + stride - 1) / stride), dim3(256), 0, s,
+        hipLaunchKernelGGL(pair_fp6_screen2w_kernel<kFmt>, dim3((m.f6_n_pairs + stride - 1) / stride), dim3(256), 0, s,
                            m.fp6->a6, m.fp6->b6, reinterpret_cast<const float2 *>(m.fp6->marg), m.fp6->W6, ok_bits,
                            m.f6_pairs, m.f6_n_pairs, m.fp6->NK, m.L, m.n_chunk_rows,
-                           m.thr, o, sc);
+                           m.thr, o, sc, m.fp6->wv);
     } else {
         // (one tile per workgroup, the XCD-ordered list)
-        hipLaunchKernelGGL(pair_fp6_screen_kernel<kA4>, dim3((m.n_tiles + stride - 1) / stride), dim3(256), 0, s,
+        hipLaunchKernelGGL(pair_fp6_screen_kernel<kFmt>, dim3((m.n_tiles + stride - 1) / stride), dim3(256), 0, s,
                            m.fp6->a6, m.fp6->b6, reinterpret_cast<const float2 *>(m.fp6->marg), m.fp6->W6, ok_bits,
                            m.tiles, m.n_tiles, m.fp6->NK, m.L, m.n_chunk_rows, m.thr,
-                           o, sc);
+                           o, sc, m.fp6->wv);
     }
 }
 void launch_fp6_screen(const MfmaLaunch &m, const uint64_t *ok_bits, const OrderArgs &o, const ScreenArgs &sc,
                        uint32_t stride, hipStream_t s) {
-    if (m.fp6->a4)
-        launch_fp6_screen_fmt<true>(m, ok_bits, o, sc, stride, s);
+    if (m.fp6->shared)  // (a6 is b6 there: the row tile is read from the shared image)
+        launch_fp6_screen_fmt<kF6Shared>(m, ok_bits, o, sc, stride, s);
+    else if (m.fp6->a4)
+        launch_fp6_screen_fmt<kF6A4>(m, ok_bits, o, sc, stride, s);
     else
-        launch_fp6_screen_fmt<false>(m, ok_bits, o, sc, stride, s);
+        launch_fp6_screen_fmt<kF6A6>(m, ok_bits, o, sc, stride, s);
 }
 }  // namespace
 
