@@ -606,6 +606,87 @@ int wld_run_summary(wld_ctx *ctx, uint32_t chunk_begin, uint32_t chunk_end, uint
                     wld_summary *out);
 void wld_summary_free(wld_summary *s);
 
+/* ---- LD heat map: r2 or |D'| reduced on the device over a grid of site
+ * cells (not in the reference; the LD heat map of a genome, of one region, or
+ * gene x gene) ----
+ *
+ * wld_run_heatmap reduces every considered pair over a caller-defined grid of
+ * n_cells x n_cells cells: per cell the pair count, the sum of the value and
+ * its max.  No row is produced, staged or copied; O(n_cells^2) numbers come
+ * back, and 64x64 tiles that touch no cell are not computed.
+ *
+ * site_cell has one entry per LOADED site (wld_loaded_sites): -1 (the site is
+ * on no cell) or a cell id < n_cells; the ids must be non-decreasing over the
+ * sites that have one.  Gaps of -1 are allowed anywhere, and so are cells
+ * without a site.  Equal runs of sites, equal bins of a coordinate, gene
+ * boundaries and a zoom on one region are all maps of this kind.
+ *
+ * A pair a < b of the linear chunk range [chunk_begin,chunk_end) (end 0 =
+ * all, as wld_run_summary) is considered iff it is in the context's current
+ * window (wld_set_window) and both sites have a cell.  Every considered pair
+ * falls into exactly one class:
+ *   none       single_weighted_ld_pair gives None;
+ *   nonfinite  Some, but the chosen value is NaN or +-inf;
+ *   counted    Some and the value finite.
+ * A counted pair adds to cell (site_cell[a], site_cell[b]) — always row <=
+ * column; the lower triangle stays at count 0, sum 0, max NaN.  The value is
+ * the f32 the default row path (WLD_OPT_REF_SUMS 1) puts in the pair's row,
+ * bit for bit: r2 (WLD_HEAT_R2) or fabsf of its d_prime (WLD_HEAT_ABS_DPRIME);
+ * the heat map always sums in lib.rs's order.  WLD_OPT_REF_SUMS, the kernel
+ * choice and the screen options do not apply, and no threshold applies.
+ *
+ * Outputs (library-allocated; release with wld_heatmap_free), n_cells x
+ * n_cells each, row-major [i * n_cells + j]:
+ *   pairs, none_pairs, nonfinite_pairs, counted_pairs
+ *              pairs = none_pairs + nonfinite_pairs + counted_pairs;
+ *   count      the counted pairs of the cell; their sum is counted_pairs;
+ *   sum        the sum of (double) value over them;
+ *   max        their largest value, ordered as floats over ALL finite values
+ *              (an f32 r2 can come out slightly negative); NaN where count
+ *              is 0;
+ *   tiles      the 64x64 tiles launched: those of the range and window whose
+ *              row block and column block both hold a site with a cell;
+ *   kernel_ms  HIP-event time of the launch (device group: the slowest
+ *              member's).
+ * The result depends only on the set of considered pairs, not on the order in
+ * which tiles finish: count and max are exact and identical from run to run,
+ * across splits of the chunk range and across device groups.  The f64 sums are
+ * NOT bitwise reproducible from run to run: tiles add to a cell with f64
+ * atomics in whatever order they finish.  Every term is exact ((double) of an
+ * f32), so each sum is within the rounding of an any-order f64 sum of its
+ * terms: relative error at most about n 2^-53 for n nonnegative terms.  Heat
+ * maps over disjoint chunk ranges combine to the whole run's: counts add, max
+ * is the max of the parts, sums agree to that rounding.
+ *
+ * On a device group (wld_create_multi) the range is sharded exactly as
+ * wld_run_summary shards it, the members run concurrently and their maps are
+ * merged on the host in member order.
+ *
+ * WLD_E_ARG: n_cells == 0 or > WLD_HEAT_MAX_CELLS; an unknown stat; site_cell
+ * NULL; an id >= n_cells, an id < -1 or a descending id (the message names
+ * the first offending index); non-finite weights (a load that takes the row
+ * path's select loop); chunk_begin > chunk_end.  WLD_E_STATE: before a load,
+ * or while a run is in flight.  WLD_E_OOM leaves the context usable.  A heat
+ * map changes nothing a later row run depends on — it keeps its tile list in
+ * a buffer of its own — and wld_last_stats and the last run's rows stay as
+ * they were.  No progress callback. */
+#define WLD_HEAT_R2 0         /* value = r2 */
+#define WLD_HEAT_ABS_DPRIME 1 /* value = fabsf(d_prime) */
+#define WLD_HEAT_MAX_CELLS 4096
+typedef struct {
+    uint32_t n_cells;
+    int stat;
+    uint64_t pairs, none_pairs, nonfinite_pairs, counted_pairs;
+    uint64_t *count; /* n_cells*n_cells, row-major [i*n_cells + j] */
+    double *sum;     /* same shape */
+    float *max;      /* same shape; NaN where count == 0 */
+    uint64_t tiles;  /* 64x64 tiles launched */
+    double kernel_ms; /* HIP-event time of the launch (device group: slowest member) */
+} wld_heatmap;
+int wld_run_heatmap(wld_ctx *ctx, const int32_t *site_cell, uint32_t n_cells, int stat, uint32_t chunk_begin,
+                    uint32_t chunk_end, wld_heatmap *out);
+void wld_heatmap_free(wld_heatmap *h);
+
 /* ---- LD pruning: a greedy r2-independent site set with tags (not in the
  * reference; PLINK's --indep-pairwise, bcftools +prune) ----
  *

@@ -1,0 +1,22 @@
+"""The LD heat map's host-side pieces (weightedld_amd/csrc/heatmap_plan.hpp: the
+check of a site -> cell map, the order-preserving key of an f32, the tile
+filter, the considered-pair count, the merge of two heat maps) against brute
+force (tests/cpp/heatmap_plan_check.cpp, host only), plain and under
+AddressSanitizer + UndefinedBehaviorSanitizer (a stand-alone host program)."""
+import os
+import subprocess
+
+import pytest
+
+from conftest import REPO
+
+
+@pytest.mark.parametrize("san", [[], ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-g"]],
+                         ids=["plain", "asan_ubsan"])
+def test_heatmap_plan_against_brute_force(tmp_path, san):
+    exe = str(tmp_path / "heatmap_plan_check")
+    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", *san,
+                    "-I", os.path.join(REPO, "weightedld_amd", "csrc"),
+                    os.path.join(REPO, "tests", "cpp", "heatmap_plan_check.cpp"), "-o", exe], check=True)
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0 and out.stdout.strip().endswith("OK"), out.stdout + out.stderr

@@ -92,6 +92,25 @@ class Summary(ctypes.Structure):
     ]
 
 
+HEAT_R2, HEAT_ABS_DPRIME, HEAT_MAX_CELLS = 0, 1, 4096
+
+
+class Heatmap(ctypes.Structure):
+    _fields_ = [
+        ("n_cells", ctypes.c_uint32),
+        ("stat", ctypes.c_int),
+        ("pairs", ctypes.c_uint64),
+        ("none_pairs", ctypes.c_uint64),
+        ("nonfinite_pairs", ctypes.c_uint64),
+        ("counted_pairs", ctypes.c_uint64),
+        ("count", ctypes.POINTER(ctypes.c_uint64)),
+        ("sum", ctypes.POINTER(ctypes.c_double)),
+        ("max", ctypes.POINTER(ctypes.c_float)),
+        ("tiles", ctypes.c_uint64),
+        ("kernel_ms", ctypes.c_double),
+    ]
+
+
 class Prune(ctypes.Structure):
     _fields_ = [
         ("n_sites", ctypes.c_uint64),
@@ -198,6 +217,9 @@ SIGNATURES = {
     "wld_run_summary": (_int, [_vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint32,
                                ctypes.POINTER(Summary)]),
     "wld_summary_free": (None, [ctypes.POINTER(Summary)]),
+    "wld_run_heatmap": (_int, [_vp, ctypes.POINTER(ctypes.c_int32), ctypes.c_uint32, _int, ctypes.c_uint32,
+                               ctypes.c_uint32, ctypes.POINTER(Heatmap)]),
+    "wld_heatmap_free": (None, [ctypes.POINTER(Heatmap)]),
     "wld_run_prune": (_int, [_vp, ctypes.c_float, _f32p, ctypes.POINTER(Prune)]),
     "wld_prune_free": (None, [ctypes.POINTER(Prune)]),
     "wld_loaded_sites": (_sz, [_vp]),

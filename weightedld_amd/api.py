@@ -13,13 +13,13 @@ from collections import namedtuple
 
 import numpy as np
 
-from ._lib import (KERNEL_AUTO, KERNEL_MFMA, KERNEL_VALU, OPTIONS, PROGRESS_FN, Pairs, Prune, RunStats, Summary, TargetRowsC,
-                   WldError, check, lib)
+from ._lib import (HEAT_ABS_DPRIME, HEAT_MAX_CELLS, HEAT_R2, KERNEL_AUTO, KERNEL_MFMA, KERNEL_VALU, OPTIONS, PROGRESS_FN,
+                   Heatmap, Pairs, Prune, RunStats, Summary, TargetRowsC, WldError, check, lib)
 
 __all__ = [
     "Symbol", "SymbolHistogram", "SiteSet", "LdStats", "PairStore", "read_fasta", "read_vcf",
     "is_site_of_interest", "henikoff_weights", "single_weighted_ld_pair", "all_weighted_ld_pairs",
-    "ld_summary", "LdSummary", "ld_prune", "LdPrune", "maf_priority", "ld_targets", "TargetRows", "Context", "default_context", "KERNEL_AUTO", "KERNEL_VALU", "KERNEL_MFMA", "OPTIONS", "WldError",
+    "ld_summary", "LdSummary", "ld_heatmap", "LdHeatmap", "heatmap_cells", "ld_prune", "LdPrune", "maf_priority", "ld_targets", "TargetRows", "Context", "default_context", "KERNEL_AUTO", "KERNEL_VALU", "KERNEL_MFMA", "OPTIONS", "WldError",
 ]
 
 
@@ -217,6 +217,112 @@ class LdSummary:
             return None
         with np.errstate(invalid="ignore", divide="ignore"):
             return np.where(self.bin_pairs > 0, self.bin_r2_sum / self.bin_pairs, np.nan)
+
+
+class LdHeatmap:
+    """wld_heatmap as numpy arrays and ints (Context.run_heatmap, ld_heatmap):
+    count (uint64), sum (float64) and max (float32, NaN where count is 0) as
+    (n_cells, n_cells) arrays — cell (i, j), i <= j, holds the counted pairs
+    a < b with site a on cell i and site b on cell j; the lower triangle is
+    empty — the class counts (pairs = none_pairs + nonfinite_pairs +
+    counted_pairs), stat ("r2" or "dprime"), tiles and kernel_ms.  From
+    ld_heatmap also cell_start, the parent coordinate each cell begins at."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def mean(self):
+        """Per-cell mean of the value (NaN where count is 0)."""
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(self.count > 0, self.sum / self.count, np.nan)
+
+    def symmetric(self, field="mean"):
+        """`field` ("count", "sum", "max" or "mean") with the upper triangle
+        mirrored into the lower one: the square image of a heat-map plot."""
+        if field not in ("count", "sum", "max", "mean"):
+            raise ValueError("field must be \"count\", \"sum\", \"max\" or \"mean\"")
+        a = (self.mean() if field == "mean" else getattr(self, field)).copy()
+        lo = np.tril_indices(a.shape[0], -1)
+        a[lo] = a.T[lo]
+        return a
+
+
+HEAT_STATS = {"r2": HEAT_R2, "dprime": HEAT_ABS_DPRIME}
+
+
+def heatmap_cells(site_map_or_siteset, n_sites=None, *, sites_per_cell=None, cell_width=None, edges=None,
+                  region=None):
+    """The site -> cell map of a heat map (Context.run_heatmap): returns
+    (site_cell, n_cells, cell_start) — site_cell int32 per site (-1: on no
+    cell), cell_start uint64 per cell, the parent coordinate the cell begins at.
+
+    The first argument is a SiteSet, a site_map (parent coordinate per site)
+    or None with n_sites (coordinate = site index).  Exactly one layout:
+      sites_per_cell=S  equal runs of S sites (the last may be shorter);
+                        cell_start is the coordinate of the run's first site;
+      cell_width=W      equal bins of the coordinate: cell (pos - origin) // W,
+                        origin = the region's start, or without a region the
+                        multiple of W at or below the first site;
+      edges=[e0..ek]    k cells [e_c, e_c+1) (gene boundaries; strictly
+                        ascending); sites outside [e0, ek) are on no cell.
+    region=(start, stop), parent coordinates, start <= pos < stop: every site
+    outside is on no cell.  Pure numpy.  ValueError: more than 4,096 cells, no
+    site on any cell, or (coordinate layouts) a site_map that descends."""
+    if isinstance(site_map_or_siteset, SiteSet):
+        n_sites = site_map_or_siteset.n_sites()
+        site_map_or_siteset = site_map_or_siteset.site_map
+    if site_map_or_siteset is None:
+        if n_sites is None:
+            raise ValueError("give a SiteSet, a site_map or n_sites")
+        pos = np.arange(int(n_sites), dtype=np.int64)
+    else:
+        pos = np.asarray(site_map_or_siteset).astype(np.int64).reshape(-1)
+        if n_sites is not None and int(n_sites) != pos.size:
+            raise ValueError("site_map has %d entries for %d sites" % (pos.size, int(n_sites)))
+    if sum(x is not None for x in (sites_per_cell, cell_width, edges)) != 1:
+        raise ValueError("give exactly one of sites_per_cell, cell_width and edges")
+    inside = np.ones(pos.size, dtype=bool)
+    if region is not None:
+        start, stop = int(region[0]), int(region[1])
+        if start < 0 or stop < start:
+            raise ValueError("region must be (start, stop) with 0 <= start <= stop")
+        inside = (pos >= start) & (pos < stop)
+    cell = np.full(pos.size, -1, dtype=np.int64)
+    if sites_per_cell is not None:
+        S = int(sites_per_cell)
+        if S < 1:
+            raise ValueError("sites_per_cell must be at least 1")
+        idx = np.flatnonzero(inside)
+        cell[idx] = np.arange(idx.size) // S
+        n_cells = (idx.size + S - 1) // S
+        cell_start = pos[idx[::S]].astype(np.uint64)
+    elif cell_width is not None:
+        W = int(cell_width)
+        if W < 1:
+            raise ValueError("cell_width must be at least 1")
+        if not inside.any():
+            n_cells, cell_start = 0, np.zeros(0, dtype=np.uint64)
+        else:
+            origin = int(region[0]) if region is not None else int(pos[inside].min()) // W * W
+            cell[inside] = (pos[inside] - origin) // W
+            n_cells = int(cell.max()) + 1
+            cell_start = (origin + W * np.arange(min(n_cells, HEAT_MAX_CELLS + 1), dtype=np.int64)).astype(np.uint64)
+    else:
+        e = np.asarray(edges).astype(np.int64).reshape(-1)
+        if e.size < 2 or np.any(np.diff(e) <= 0) or e[0] < 0:
+            raise ValueError("edges must be at least two strictly ascending coordinates")
+        inside &= (pos >= e[0]) & (pos < e[-1])
+        cell[inside] = np.searchsorted(e, pos[inside], side="right") - 1
+        n_cells = e.size - 1
+        cell_start = e[:-1].astype(np.uint64)
+    if n_cells > HEAT_MAX_CELLS:
+        raise ValueError("%d cells; a heat map has at most %d per side" % (n_cells, HEAT_MAX_CELLS))
+    if n_cells == 0 or not (cell >= 0).any():
+        raise ValueError("no site is on a cell")
+    on = cell[cell >= 0]
+    if np.any(np.diff(on) < 0):
+        raise ValueError("the cells descend along the sites: a coordinate layout needs a non-decreasing site_map")
+    return cell.astype(np.int32), int(n_cells), cell_start
 
 
 class LdPrune:
@@ -495,6 +601,41 @@ class Context:
         lib().wld_summary_free(ctypes.byref(out))
         return res
 
+    def run_heatmap(self, site_cell, n_cells, stat="r2", chunk_begin=0, chunk_end=0):
+        """wld_run_heatmap: every in-window pair of the linear chunk range
+        (end 0 = all) whose two sites have a cell, reduced on the device over
+        the n_cells x n_cells grid to an LdHeatmap — no rows.  site_cell: one
+        int32 per LOADED site, -1 or a cell id, non-decreasing over the sites
+        that have one (heatmap_cells builds the usual layouts).  stat: "r2"
+        or "dprime" (|D'|)."""
+        if isinstance(stat, str):
+            if stat not in HEAT_STATS:
+                raise ValueError("stat must be \"r2\" or \"dprime\"")
+            stat = HEAT_STATS[stat]
+        sc = None
+        if site_cell is not None:
+            sc = np.ascontiguousarray(site_cell, dtype=np.int32)
+            if sc.ndim != 1:
+                raise ValueError("site_cell must be one cell id per loaded site")
+            n = int(lib().wld_loaded_sites(self._h))
+            if n and sc.size != n:  # (not loaded: the library refuses the call)
+                raise ValueError("site_cell has %d entries for %d loaded sites" % (sc.size, n))
+        out = Heatmap()
+        check(lib().wld_run_heatmap(self._h, None if sc is None else _p(sc, ctypes.c_int32), int(n_cells), int(stat),
+                                    chunk_begin, chunk_end, ctypes.byref(out)), "wld_run_heatmap")
+        nc = int(out.n_cells)
+
+        def grab(p, dt):
+            return np.ctypeslib.as_array(p, shape=(nc, nc)).astype(dt, copy=True)
+
+        res = LdHeatmap(n_cells=nc, stat="dprime" if int(out.stat) == HEAT_ABS_DPRIME else "r2",
+                        pairs=int(out.pairs), none_pairs=int(out.none_pairs),
+                        nonfinite_pairs=int(out.nonfinite_pairs), counted_pairs=int(out.counted_pairs),
+                        count=grab(out.count, np.uint64), sum=grab(out.sum, np.float64),
+                        max=grab(out.max, np.float32), tiles=int(out.tiles), kernel_ms=float(out.kernel_ms))
+        lib().wld_heatmap_free(ctypes.byref(out))
+        return res
+
     def run_prune(self, r2_threshold, priority=None):
         """wld_run_prune: the greedy r2-independent set of the loaded sites at
         this threshold under the context's window, as an LdPrune (keep, tag in
@@ -711,6 +852,33 @@ def ld_summary(site_set, weights, bin_width=None, n_bins=None, max_distance=None
         return ctx.run_summary(bin_width or 0, n_bins or 0)
     finally:
         ctx.set_window(*before)
+
+
+def ld_heatmap(site_set, weights, stat="r2", sites_per_cell=None, cell_width=None, edges=None, region=None,
+               max_distance=None, max_sites=None, ctx=None):
+    """The LD heat map of site_set (not in the reference): builds the cells
+    with heatmap_cells (exactly one of sites_per_cell, cell_width and edges;
+    region optional), loads the set and runs Context.run_heatmap under the
+    window max_distance / max_sites (the context's own window is restored
+    afterwards).  Returns an LdHeatmap with cell_start, the parent coordinate
+    each cell begins at, and site_cell."""
+    ctx = ctx or default_context()
+    w = np.ascontiguousarray(weights, dtype=np.float32)
+    if w.size != site_set.n_seqs():
+        raise ValueError("weights must have n_seqs entries")
+    site_cell, n_cells, cell_start = heatmap_cells(site_set, sites_per_cell=sites_per_cell, cell_width=cell_width,
+                                                   edges=edges, region=region)
+    before = ctx.window()
+    if max_distance is not None or max_sites is not None:
+        ctx.set_window(max_distance, max_sites)
+    try:
+        ctx.load(site_set.buffer, w, site_set.site_map)
+        res = ctx.run_heatmap(site_cell, n_cells, stat)
+    finally:
+        ctx.set_window(*before)
+    res.cell_start = cell_start
+    res.site_cell = site_cell
+    return res
 
 
 def ld_prune(site_set, weights, r2_threshold, priority=None, max_distance=None, max_sites=None, ctx=None):

@@ -25,6 +25,7 @@
 #include "tile_order.hpp"
 #include "window_plan.hpp"
 #include "summary_plan.hpp"
+#include "heatmap_plan.hpp"
 #include "prune_plan.hpp"
 #include "targets_plan.hpp"
 #include "kernels.hpp"
@@ -227,6 +228,13 @@ struct wld_ctx {
     DevBuf sum_buf;
     hipEvent_t ev_sum[2] = {};
 
+    // wld_run_heatmap: its accumulators (zeroed per call), its own tile list
+    // (the range's list cut to the tiles that touch a cell: the row path's
+    // cached list and its range stay as they are), the site -> cell map with
+    // the per-block cell limits, and the two events around its launch
+    DevBuf heat_buf, heat_tiles, heat_map;
+    hipEvent_t ev_heat[2] = {};
+
     // wld_run_prune: while it runs, the gathers leave loaded indices in
     // out_a/out_b (no site_map); its four events (created at the first prune:
     // before the CSR build, after it, after the rounds, after the tags) and
@@ -256,7 +264,7 @@ struct wld_ctx {
         // buffers: it completes before they are freed
         if (stream && stream != own_stream) (void)hipStreamSynchronize(stream);
         DevBuf *all[] = {&keep, &htab, &htab_kept, &site_index, &raw, &wraw, &codes, &w_pad, &wstats, &site_ok, &site_map, &planes, &frag, &rcodes, &rw, &w6, &w4, &f6a, &f6b, &f6marg, &i8a, &i8b, &tiles, &cand, &f6_pairs, &fp6_probe_buf,
-                         &seg_cnt, &seg_off, &chunk_total, &chunk_base, &counters, &chunk_left, &prog_n, &win_hi, &win_pairs, &sum_buf, &st_a, &st_b, &st_d,
+                         &seg_cnt, &seg_off, &chunk_total, &chunk_base, &counters, &chunk_left, &prog_n, &win_hi, &win_pairs, &sum_buf, &heat_buf, &heat_tiles, &heat_map, &st_a, &st_b, &st_d,
                          &st_dp, &st_r2, &out_a, &out_b, &out_d, &out_dp, &out_r2};
         for (DevBuf *b : all) release(*b);
         for (DevBuf *b : tg.all()) release(*b);
@@ -265,6 +273,8 @@ struct wld_ctx {
         for (auto &e : ev)
             if (e) (void)hipEventDestroy(e);
         for (auto &e : ev_sum)
+            if (e) (void)hipEventDestroy(e);
+        for (auto &e : ev_heat)
             if (e) (void)hipEventDestroy(e);
         for (auto &e : ev_pr)
             if (e) (void)hipEventDestroy(e);
@@ -278,7 +288,7 @@ namespace {
 
 // Every single-device entry point starts here; a device group (wld_create_multi)
 // supports only wld_load, wld_run_host, wld_all_weighted_ld_pairs,
-// wld_run_summary and the option/kernel/stats calls, which dispatch to its
+// wld_run_summary, wld_run_heatmap and the option/kernel/stats calls, which dispatch to its
 // members.
 int set_dev(wld_ctx *c) {
     if (!c) return fail(WLD_E_ARG, "null context");
@@ -2223,6 +2233,207 @@ void wld_summary_free(wld_summary *s) {
     free(s->bin_pairs);
     free(s->bin_r2_sum);
     memset(s, 0, sizeof(*s));
+}
+
+namespace {
+// What wld_run_heatmap refuses, checked on a loaded single-device context
+// (every member of a group holds the same load).
+int heatmap_check(wld_ctx *c, const int32_t *site_cell, uint32_t n_cells, int stat) {
+    if (n_cells == 0) return fail(WLD_E_ARG, "wld_run_heatmap: n_cells 0");
+    if (n_cells > WLD_HEAT_MAX_CELLS)
+        return fail(WLD_E_ARG, "wld_run_heatmap: n_cells %u exceeds %u", n_cells, (unsigned)WLD_HEAT_MAX_CELLS);
+    if (stat != WLD_HEAT_R2 && stat != WLD_HEAT_ABS_DPRIME)
+        return fail(WLD_E_ARG, "wld_run_heatmap: unknown stat %d", stat);
+    if (!site_cell) return fail(WLD_E_ARG, "wld_run_heatmap: null site_cell");
+    if (c->safe)
+        return fail(WLD_E_ARG, "wld_run_heatmap needs finite weights (this load takes the select loop)");
+    const heatmap_plan::MapCheck m = heatmap_plan::validate(site_cell, (uint32_t)c->L, n_cells);
+    if (m.what == heatmap_plan::kMapTooLarge)
+        return fail(WLD_E_ARG, "wld_run_heatmap: site_cell[%u] = %d is not below n_cells %u", m.index,
+                    site_cell[m.index], n_cells);
+    if (m.what == heatmap_plan::kMapNegative)
+        return fail(WLD_E_ARG, "wld_run_heatmap: site_cell[%u] = %d (-1 means no cell)", m.index, site_cell[m.index]);
+    if (m.what == heatmap_plan::kMapDescends)
+        return fail(WLD_E_ARG, "wld_run_heatmap needs non-decreasing cell ids: site_cell[%u] = %d < site_cell[%u] = %d",
+                    m.index, site_cell[m.index], m.prev, site_cell[m.prev]);
+    return WLD_OK;
+}
+
+// The heat map of the linear chunks [lb, le) on one device (site_cell
+// checked): the range's tile list under the window, cut to the tiles that
+// touch a cell, in a buffer of its own — the row path's cached list, its
+// range and seg_clear are not touched — zeroed accumulators, one launch, one
+// copy back.  Touches no staging, segment count, chunk total, run counter or
+// row-path event.
+int heatmap_range(wld_ctx *c, const int32_t *site_cell, uint32_t n_cells, int stat, uint32_t lb, uint32_t le,
+                  heatmap_plan::Heatmap *out) {
+    WLD_TRY(set_dev(c));
+    if (!c->loaded) return fail(WLD_E_STATE, "wld_run_heatmap before wld_load");
+    if (c->pend.active) return fail(WLD_E_STATE, "wld_run_heatmap during a run");
+    const size_t L = c->L, LP = c->LP, nc2 = (size_t)n_cells * n_cells, TB = LP / kTile;
+    *out = heatmap_plan::Heatmap{};
+    out->n_cells = n_cells;
+    try {
+        out->count.assign(nc2, 0);
+        out->sum.assign(nc2, 0.0);
+        out->max_key.assign(nc2, heatmap_plan::kNoKey);
+    } catch (const std::bad_alloc &) {
+        return fail(WLD_E_OOM, "host allocation of the heat map (%u x %u cells) failed", n_cells, n_cells);
+    }
+    if (lb >= le) return WLD_OK;
+    const bool windowed = window_on(c);
+    if (windowed && c->win_hi_host.size() != L) return fail(WLD_E_STATE, "internal: the window has no plan");
+    // the plan: block limits, the filtered list, the pairs the launch must see
+    const heatmap_plan::Blocks blk = heatmap_plan::blocks(site_cell, (uint32_t)L, (uint32_t)TB);
+    const uint32_t T_used = (uint32_t)((L + kTile - 1) / kTile), n = chunk_rows_of(L);
+    std::vector<uint32_t> t = heatmap_plan::filter_tiles(
+        windowed ? window_plan::range_tiles(n, T_used, lb, le, c->win_hi_host) : tile_order::range_tiles(n, T_used, lb, le),
+        blk);
+    out->tiles = t.size();
+    const uint64_t expect =
+        heatmap_plan::considered_pairs(site_cell, windowed ? c->win_hi_host.data() : nullptr, (uint32_t)L, lb, le);
+    if (t.empty()) {
+        if (expect) return fail(WLD_E_HIP, "internal: the heat map's tile list is empty; the range holds %llu pairs",
+                                (unsigned long long)expect);
+        return WLD_OK;
+    }
+    if (!c->opt_tile_rows && t.size() >= 4096 && T_used < 65535)
+        t = xcd_order(t, tile_order::super_block_side((uint32_t)c->NP));
+    WLD_TRY(ensure_ref_layout(c));
+    for (auto &e : c->ev_heat)
+        if (!e) HIP_TRY(hipEventCreate(&e));
+    // {sum[nc2]} f64 | {classes[4], count[nc2]} u64 | max_key[nc2] u32: one memset
+    const size_t bytes = 8 * nc2 + 8 * (4 + nc2) + 4 * nc2;
+    WLD_TRY(ensure(c->heat_buf, bytes));
+    WLD_TRY(ensure(c->heat_tiles, t.size() * sizeof(uint32_t)));
+    WLD_TRY(ensure(c->heat_map, (LP + 2 * TB) * sizeof(int32_t)));
+    std::vector<int32_t> map(LP + 2 * TB, -1);  // site_cell[LP] (-1 past L), blk_lo[TB], blk_hi[TB]
+    std::copy(site_cell, site_cell + L, map.begin());
+    std::copy(blk.lo.begin(), blk.lo.end(), map.begin() + LP);
+    std::copy(blk.hi.begin(), blk.hi.end(), map.begin() + LP + TB);
+    HIP_TRY(hipMemcpyAsync(c->heat_map.p, map.data(), map.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->heat_tiles.p, t.data(), t.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(c->heat_buf.p, 0, bytes, c->stream));
+    double *d_sum = ptr<double>(c->heat_buf);
+    unsigned long long *d_cls = reinterpret_cast<unsigned long long *>(d_sum + nc2);
+    unsigned long long *d_cnt = d_cls + 4;
+    uint32_t *d_key = reinterpret_cast<uint32_t *>(d_cnt + nc2);
+    const int32_t *d_map = ptr<int32_t>(c->heat_map);
+    const HeatmapArgs ha{d_cls, d_cnt, d_sum, d_key, d_map, d_map + LP, d_map + LP + TB, n_cells, stat};
+    ValuLaunch v = ref_valu_launch(c, 0.0f);  // (finite weights: heatmap_check)
+    v.tiles = ptr<uint32_t>(c->heat_tiles);
+    v.n_tiles = (uint32_t)t.size();
+    OrderArgs o{};  // the window only
+    o.L = (uint32_t)L;
+    o.T = (uint32_t)TB;
+    o.win_hi = windowed ? ptr<uint32_t>(c->win_hi) : nullptr;
+    HIP_TRY(hipEventRecord(c->ev_heat[0], c->stream));
+    launch_pair_heatmap(v, o, ha, c->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c->ev_heat[1], c->stream));
+    uint64_t cls[4] = {0, 0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(out->sum.data(), d_sum, 8 * nc2, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(cls, d_cls, sizeof(cls), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(out->count.data(), d_cnt, 8 * nc2, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(out->max_key.data(), d_key, 4 * nc2, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));  // (map and t are read by the copies)
+    out->kernel_ms = event_ms(c->ev_heat[0], c->ev_heat[1]);
+    out->pairs = cls[0];
+    out->none_pairs = cls[1];
+    out->nonfinite_pairs = cls[2];
+    uint64_t in_cells = 0;
+    for (uint64_t x : out->count) in_cells += x;
+    out->counted_pairs = in_cells;
+    // the kernel's own accounting against the host's plan
+    if (out->pairs != expect || out->pairs != out->none_pairs + out->nonfinite_pairs + out->counted_pairs)
+        return fail(WLD_E_HIP, "internal: heat map counted %llu pairs (%llu none, %llu nonfinite, %llu in cells); "
+                               "the range holds %llu",
+                    (unsigned long long)out->pairs, (unsigned long long)out->none_pairs,
+                    (unsigned long long)out->nonfinite_pairs, (unsigned long long)out->counted_pairs,
+                    (unsigned long long)expect);
+    return WLD_OK;
+}
+
+// ... on a device group: member k takes its shard of the chunk sequence (as
+// summary_group deals them) cut to [lb, le), on its own host thread; the
+// members' maps are merged in member order.
+int heatmap_group(wld_ctx *g, const int32_t *site_cell, uint32_t n_cells, int stat, uint32_t lb, uint32_t le,
+                  heatmap_plan::Heatmap *out) {
+    const int G = (int)g->members.size();
+    wld_ctx *c0 = g->members[0];
+    std::vector<uint32_t> sb(G), se(G);
+    for (int k = 0; k < G; ++k) {  // every range before any thread starts
+        if (window_on(c0)) WLD_TRY(wld_shard_chunks_window(c0, G, k, &sb[k], &se[k]));
+        else WLD_TRY(wld_shard_chunks(c0->L, G, k, &sb[k], &se[k]));
+        sb[k] = std::max(sb[k], lb);
+        se[k] = std::max(sb[k], std::min(se[k], le));
+    }
+    std::vector<heatmap_plan::Heatmap> part(G);
+    std::vector<int> status(G, WLD_OK);
+    std::vector<std::string> msg(G);
+    std::vector<std::thread> th;
+    for (int k = 0; k < G; ++k)
+        th.emplace_back([&, k] {
+            status[k] = heatmap_range(g->members[k], site_cell, n_cells, stat, sb[k], se[k], &part[k]);
+            if (status[k] != WLD_OK) msg[k] = wld_last_error();
+        });
+    for (auto &t : th) t.join();
+    for (int k = 0; k < G; ++k)
+        if (status[k] != WLD_OK)
+            return fail(status[k], "device %d (shard %d): %s", g->members[k]->device, k, msg[k].c_str());
+    *out = heatmap_plan::Heatmap{};
+    for (int k = 0; k < G; ++k) heatmap_plan::merge(*out, part[k]);
+    return WLD_OK;
+}
+}  // namespace
+
+int wld_run_heatmap(wld_ctx *c, const int32_t *site_cell, uint32_t n_cells, int stat, uint32_t chunk_begin,
+                    uint32_t chunk_end, wld_heatmap *out) {
+    if (!out) return fail(WLD_E_ARG, "null out");
+    memset(out, 0, sizeof(*out));
+    if (!c) return fail(WLD_E_ARG, "null context");
+    wld_ctx *c0 = c->members.empty() ? c : c->members[0];
+    for (wld_ctx *m : c->members.empty() ? std::vector<wld_ctx *>{c} : c->members) {
+        if (!m->loaded) return fail(WLD_E_STATE, "wld_run_heatmap before wld_load");
+        if (m->pend.active) return fail(WLD_E_STATE, "wld_run_heatmap during a run");
+    }
+    WLD_TRY(heatmap_check(c0, site_cell, n_cells, stat));
+    const uint32_t m = chunks_of(c0->L);
+    if (chunk_end == 0 || chunk_end > m) chunk_end = m;
+    if (chunk_begin > chunk_end) return fail(WLD_E_ARG, "chunk range [%u,%u) invalid", chunk_begin, chunk_end);
+    heatmap_plan::Heatmap h;
+    if (c->members.empty()) WLD_TRY(heatmap_range(c, site_cell, n_cells, stat, chunk_begin, chunk_end, &h));
+    else WLD_TRY(heatmap_group(c, site_cell, n_cells, stat, chunk_begin, chunk_end, &h));
+    const size_t nc2 = (size_t)n_cells * n_cells;
+    out->count = (uint64_t *)malloc(nc2 * sizeof(uint64_t));
+    out->sum = (double *)malloc(nc2 * sizeof(double));
+    out->max = (float *)malloc(nc2 * sizeof(float));
+    if (!out->count || !out->sum || !out->max) {
+        wld_heatmap_free(out);
+        return fail(WLD_E_OOM, "host allocation of the heat map (%u x %u cells) failed", n_cells, n_cells);
+    }
+    for (size_t i = 0; i < nc2; ++i) {
+        out->count[i] = h.count[i];
+        out->sum[i] = h.sum[i];
+        out->max[i] = h.count[i] ? heatmap_plan::key_float(h.max_key[i]) : std::nanf("");
+    }
+    out->n_cells = n_cells;
+    out->stat = stat;
+    out->pairs = h.pairs;
+    out->none_pairs = h.none_pairs;
+    out->nonfinite_pairs = h.nonfinite_pairs;
+    out->counted_pairs = h.counted_pairs;
+    out->tiles = h.tiles;
+    out->kernel_ms = h.kernel_ms;
+    return WLD_OK;
+}
+
+void wld_heatmap_free(wld_heatmap *h) {
+    if (!h) return;
+    free(h->count);
+    free(h->sum);
+    free(h->max);
+    memset(h, 0, sizeof(*h));
 }
 
 namespace {

@@ -21,6 +21,14 @@
 //   --decay-bins B           64; the last also takes every longer distance); one
 //                      device summary pass over every in-window pair serves
 //                      both files (wld_run_summary; no threshold applies)
+//   --heatmap-output FILE    LD heat map TSV (cell_a_start, cell_b_start, pairs,
+//   --heatmap-cell-width W   sum, mean, max): every in-window pair reduced on the
+//   --heatmap-cell-sites S   device over a grid of cells — equal bins of W parent
+//   --heatmap-region A:B     coordinates, or equal runs of S sites of interest
+//   --heatmap-stat STAT      (exactly one of the two; at most 4,096 cells), of
+//                      the whole set or of the sites with A <= coordinate < B;
+//                      STAT r2 (default) or dprime (|D'|); cells without a pair
+//                      are not written (wld_run_heatmap; no threshold applies)
 //   --prune-output FILE      LD pruning TSV (site, kept, tag): the greedy set of
 //   --prune-r2 T             sites no two of which have r2 > T (in the window),
 //   --prune-priority P       visited by P = index (default) or maf (the larger
@@ -216,6 +224,11 @@ struct Opt {
     uint64_t max_distance = 0, max_sites = 0;  // --max-distance / --max-sites: wld_set_window (0: no limit)
     std::string ld_score_output, decay_output;  // --ld-score-output / --decay-output: wld_run_summary
     uint64_t decay_bin_width = 0, decay_bins = 64;
+    // --heatmap-output / --heatmap-cell-width / --heatmap-cell-sites / --heatmap-region / --heatmap-stat: wld_run_heatmap
+    std::string heatmap_output;
+    uint64_t heatmap_cell_width = 0, heatmap_cell_sites = 0, heatmap_lo = 0, heatmap_hi = 0;
+    bool have_heatmap_width = false, have_heatmap_sites = false, have_heatmap_region = false, have_heatmap_stat = false;
+    int heatmap_stat = WLD_HEAT_R2;
     std::string prune_output;  // --prune-output / --prune-r2 / --prune-priority: wld_run_prune
     bool have_prune_r2 = false, prune_maf = false;
     float prune_r2 = 0.0f;
@@ -269,6 +282,17 @@ void usage(FILE *f) {
             "        --decay-bin-width <decay-bin-width>  (addition) width of a distance bin, in parent coordinates\n"
             "        --decay-bins <decay-bins>            (addition) number of bins, at most 1024; the last one also\n"
             "                                             takes every longer distance [default: 64]\n"
+            "        --heatmap-output <heatmap-output>    (addition) Filename to write the LD heat map to (cell_a_start,\n"
+            "                                             cell_b_start, pairs, sum, mean, max per cell with a pair);\n"
+            "                                             needs one of --heatmap-cell-width, --heatmap-cell-sites;\n"
+            "                                             obeys --max-distance, --max-sites and --devices\n"
+            "        --heatmap-cell-width <heatmap-cell-width>  (addition) cells are equal bins of this many parent\n"
+            "                                             coordinates (at most 4096 cells)\n"
+            "        --heatmap-cell-sites <heatmap-cell-sites>  (addition) cells are equal runs of this many sites of\n"
+            "                                             interest (at most 4096 cells)\n"
+            "        --heatmap-region <heatmap-region>    (addition) \"START:END\": only the sites with START <=\n"
+            "                                             coordinate < END [default: every site]\n"
+            "        --heatmap-stat <heatmap-stat>        (addition) r2 | dprime (|D'|) [default: r2]\n"
             "        --prune-output <prune-output>        (addition) Filename to write the LD-pruned site set to (site,\n"
             "                                             kept, tag: the kept site that stands for a removed one);\n"
             "                                             needs --prune-r2; obeys --max-distance and --max-sites\n"
@@ -383,6 +407,32 @@ Opt parse(int argc, char **argv) {
             if (v.empty() || v.find_first_not_of("0123456789") != std::string::npos || v.size() > 19)
                 arg_error(("Invalid value for '" + name + "':").c_str(), v.c_str());
             (name == "--decay-bin-width" ? o.decay_bin_width : o.decay_bins) = strtoull(v.c_str(), nullptr, 10);
+        } else if (a == "--heatmap-output") {
+            o.heatmap_output = need("--heatmap-output");
+        } else if (a == "--heatmap-cell-width" || a == "--heatmap-cell-sites") {
+            const std::string name = a, v = need(name.c_str());
+            if (v.empty() || v.find_first_not_of("0123456789") != std::string::npos || v.size() > 19 ||
+                strtoull(v.c_str(), nullptr, 10) == 0)
+                arg_error(("Invalid value for '" + name + "':").c_str(), v.c_str());
+            (name == "--heatmap-cell-width" ? o.heatmap_cell_width : o.heatmap_cell_sites) = strtoull(v.c_str(), nullptr, 10);
+            (name == "--heatmap-cell-width" ? o.have_heatmap_width : o.have_heatmap_sites) = true;
+        } else if (a == "--heatmap-region") {
+            const std::string v = need("--heatmap-region");
+            const size_t c = v.find(':');
+            const std::string lo = v.substr(0, std::min(c, v.size())), hi = c == std::string::npos ? "" : v.substr(c + 1);
+            auto bad = [](const std::string &t) {
+                return t.empty() || t.find_first_not_of("0123456789") != std::string::npos || t.size() > 19;
+            };
+            if (bad(lo) || bad(hi) || strtoull(lo.c_str(), nullptr, 10) > strtoull(hi.c_str(), nullptr, 10))
+                arg_error("Invalid value for '--heatmap-region' (START:END):", v.c_str());
+            o.heatmap_lo = strtoull(lo.c_str(), nullptr, 10);
+            o.heatmap_hi = strtoull(hi.c_str(), nullptr, 10);
+            o.have_heatmap_region = true;
+        } else if (a == "--heatmap-stat") {
+            const std::string k = need("--heatmap-stat");
+            if (k != "r2" && k != "dprime") arg_error("Invalid value for '--heatmap-stat':", k.c_str());
+            o.heatmap_stat = k == "dprime" ? WLD_HEAT_ABS_DPRIME : WLD_HEAT_R2;
+            o.have_heatmap_stat = true;
         } else if (a == "--prune-output") {
             o.prune_output = need("--prune-output");
         } else if (a == "--prune-r2") {
@@ -438,6 +488,17 @@ Opt parse(int argc, char **argv) {
         arg_error("The argument '--decay-bin-width' needs", "--decay-output <decay-output>");
     if (!o.decay_output.empty() && (o.decay_bins < 1 || o.decay_bins > 1024))
         arg_error("Invalid value for '--decay-bins' (1 to 1024):", std::to_string(o.decay_bins).c_str());
+    if (!o.heatmap_output.empty() && !o.have_heatmap_width && !o.have_heatmap_sites)
+        arg_error("The following required arguments were not provided:",
+                  "--heatmap-cell-width <heatmap-cell-width> or --heatmap-cell-sites <heatmap-cell-sites>");
+    if (o.have_heatmap_width && o.have_heatmap_sites)
+        arg_error("The argument '--heatmap-cell-width' cannot be used with", "--heatmap-cell-sites");
+    if (o.heatmap_output.empty() && (o.have_heatmap_width || o.have_heatmap_sites))
+        arg_error(o.have_heatmap_width ? "The argument '--heatmap-cell-width' needs" : "The argument '--heatmap-cell-sites' needs",
+                  "--heatmap-output <heatmap-output>");
+    if (o.heatmap_output.empty() && (o.have_heatmap_region || o.have_heatmap_stat))
+        arg_error(o.have_heatmap_region ? "The argument '--heatmap-region' needs" : "The argument '--heatmap-stat' needs",
+                  "--heatmap-output <heatmap-output>");
     if (!o.prune_output.empty() && !o.have_prune_r2)
         arg_error("The following required arguments were not provided:", "--prune-r2 <prune-r2>");
     if (o.prune_output.empty() && o.have_prune_r2)
@@ -627,6 +688,93 @@ void write_summaries(const Opt &opt, wld_ctx *ctx, const std::vector<uint64_t> &
     wld_summary_free(&s);
 }
 
+// --heatmap-output: the site -> cell map of the loaded set (parent[i] as in
+// write_summaries) — equal bins of --heatmap-cell-width coordinates from the
+// region's start (without a region: from the multiple of the width at or below
+// the first site), or equal runs of --heatmap-cell-sites sites — and the
+// coordinate every cell begins at.  Sites outside --heatmap-region are on no
+// cell.  More than 4,096 cells, or no site on a cell, ends the run before any
+// pair is computed.
+struct HeatCells {
+    std::vector<int32_t> site_cell;
+    std::vector<uint64_t> cell_start;
+};
+HeatCells resolve_heat_cells(const Opt &opt, const std::vector<uint64_t> &parent) {
+    HeatCells h;
+    if (opt.heatmap_output.empty()) return h;
+    h.site_cell.assign(parent.size(), -1);
+    auto inside = [&](uint64_t p) { return !opt.have_heatmap_region || (p >= opt.heatmap_lo && p < opt.heatmap_hi); };
+    uint64_t n_cells = 0;
+    if (opt.have_heatmap_sites) {
+        uint64_t k = 0;
+        for (size_t i = 0; i < parent.size(); ++i) {
+            if (!inside(parent[i])) continue;
+            if (k % opt.heatmap_cell_sites == 0 && k / opt.heatmap_cell_sites < WLD_HEAT_MAX_CELLS) h.cell_start.push_back(parent[i]);
+            h.site_cell[i] = (int32_t)std::min<uint64_t>(k / opt.heatmap_cell_sites, WLD_HEAT_MAX_CELLS);
+            ++k;
+        }
+        n_cells = (k + opt.heatmap_cell_sites - 1) / opt.heatmap_cell_sites;
+    } else {
+        bool any = false;
+        uint64_t first = 0;
+        for (const uint64_t p : parent)
+            if (inside(p) && (!any || p < first)) first = p, any = true;
+        const uint64_t W = opt.heatmap_cell_width, origin = opt.have_heatmap_region ? opt.heatmap_lo : first / W * W;
+        for (size_t i = 0; i < parent.size() && any; ++i) {
+            if (!inside(parent[i])) continue;
+            const uint64_t c = (parent[i] - origin) / W;
+            n_cells = std::max(n_cells, c + 1);
+            h.site_cell[i] = (int32_t)std::min<uint64_t>(c, WLD_HEAT_MAX_CELLS);
+        }
+        for (uint64_t c = 0; c < std::min<uint64_t>(n_cells, WLD_HEAT_MAX_CELLS); ++c) h.cell_start.push_back(origin + c * W);
+    }
+    if (n_cells > WLD_HEAT_MAX_CELLS) {
+        fprintf(stderr, "error: --heatmap-output: %" PRIu64 " cells; a heat map has at most %d per side (use larger cells "
+                        "or a --heatmap-region)\n", n_cells, WLD_HEAT_MAX_CELLS);
+        quit(1);
+    }
+    if (n_cells == 0) {
+        fprintf(stderr, "error: --heatmap-output: no site of interest is on a cell\n");
+        quit(1);
+    }
+    return h;
+}
+
+// --heatmap-output: one heat-map pass over every in-window pair of the cells'
+// sites (wld_run_heatmap: the values of the pair TSV's rows, no threshold),
+// then the TSV: the cells with a pair in (i, j) order, i <= j.  Numbers print
+// as %.9g (the f32 max round-trips).
+void write_heatmap(const Opt &opt, wld_ctx *ctx, const HeatCells &cells) {
+    if (opt.heatmap_output.empty()) return;
+    using clk = std::chrono::steady_clock;
+    const auto sw = clk::now();
+    const uint32_t n = (uint32_t)cells.cell_start.size();
+    wld_heatmap h;
+    const int st = wld_run_heatmap(ctx, cells.site_cell.data(), n, opt.heatmap_stat, 0, 0, &h);
+    if (st != WLD_OK) die(st, "run_heatmap");
+    INFO("Reduced %s pairs (%s without a statistic) over %u x %u cells, %" PRIu64 " tiles, in %s",
+         human((double)h.pairs).c_str(), human((double)(h.none_pairs + h.nonfinite_pairs)).c_str(), n, n, h.tiles,
+         fmt_duration(clk::now() - sw).c_str());
+    INFO("Writing output to %s", debug_path(opt.heatmap_output).c_str());
+    std::string out = "cell_a_start\tcell_b_start\tpairs\tsum\tmean\tmax\n";
+    char line[200];
+    for (uint32_t i = 0; i < n; ++i)
+        for (uint32_t j = i; j < n; ++j) {
+            const size_t k = (size_t)i * n + j;
+            if (!h.count[k]) continue;
+            snprintf(line, sizeof line, "%" PRIu64 "\t%" PRIu64 "\t%" PRIu64 "\t%.9g\t%.9g\t%.9g\n", cells.cell_start[i],
+                     cells.cell_start[j], h.count[k], h.sum[k], h.sum[k] / (double)h.count[k], (double)h.max[k]);
+            out += line;
+        }
+    FILE *f = fopen(opt.heatmap_output.c_str(), "wb");
+    const bool ok = f && fwrite(out.data(), 1, out.size(), f) == out.size();
+    if ((f && fclose(f) != 0) || !ok) {
+        fprintf(stderr, "Error: cannot write %s\n", opt.heatmap_output.c_str());
+        quit(1);
+    }
+    wld_heatmap_free(&h);
+}
+
 // The "maf" priority of a site from its histogram: minor / (major + minor) of
 // the counts of wld_major_minor's symbols, in double, as a float; 0 for a site
 // without both.
@@ -810,6 +958,7 @@ int run_gpu_prepass(const Opt &opt, wld_siteset *siteset, wld_ctx *ctx) {
     std::vector<uint64_t> parent(L);
     if (L && (st = wld_site_map_copy(ctx, parent.data())) != WLD_OK) die(st, "site_map_copy");
     const std::vector<uint32_t> targets = resolve_targets(opt, parent);
+    const HeatCells heat_cells = resolve_heat_cells(opt, parent);
     if (!opt.pair_output.empty()) INFO("Beginning pairwise weighted LD computation");
     sw = clk::now();
     const uint64_t total_pairs = ((uint64_t)L - 1) * ((uint64_t)L - 2) / 2;  // main.rs:168 (sic, wraps)
@@ -823,6 +972,7 @@ int run_gpu_prepass(const Opt &opt, wld_siteset *siteset, wld_ctx *ctx) {
     }
     const auto dur = clk::now() - sw;
     write_summaries(opt, ctx, parent);
+    write_heatmap(opt, ctx, heat_cells);
     write_targets(opt, ctx, targets);
     // (a FASTA set has no site_map: a kept site's parent index is its index in the unfiltered set)
     write_prune(opt, ctx, parent, siteset, std::vector<size_t>(parent.begin(), parent.end()));
@@ -922,6 +1072,7 @@ int main(int argc, char **argv) {
     std::vector<uint64_t> parent(L);
     for (size_t i = 0; i < L; ++i) parent[i] = wld_siteset_parent_site_index(filtered, i);
     const std::vector<uint32_t> targets = resolve_targets(opt, parent);
+    const HeatCells heat_cells = resolve_heat_cells(opt, parent);
     if (!opt.pair_output.empty()) INFO("Beginning pairwise weighted LD computation");
     sw = clk::now();
     const uint64_t total_pairs = ((uint64_t)L - 1) * ((uint64_t)L - 2) / 2;  // main.rs:168 (sic, wraps)
@@ -939,6 +1090,7 @@ int main(int argc, char **argv) {
     }
     const auto dur = clk::now() - sw;
     write_summaries(opt, ctx, parent);
+    write_heatmap(opt, ctx, heat_cells);
     write_targets(opt, ctx, targets);
     std::vector<size_t> self(L);
     for (size_t i = 0; i < L; ++i) self[i] = i;

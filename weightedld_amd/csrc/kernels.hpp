@@ -138,6 +138,24 @@ struct SummaryArgs {
     uint32_t n_bins;
 };
 
+// The accumulators of a heat-map run (pair_heatmap.hip; wld_run_heatmap): all
+// zero before the launch (a max key of 0 lies below every finite value's,
+// heatmap_plan.hpp).  classes = {pairs, none, nonfinite}, one atomic each per
+// tile; count/sum/max_key have n_cells x n_cells entries, row-major.
+// site_cell: LP entries, -1 for a site on no cell and for padding; blk_lo /
+// blk_hi: per 64-site block the cells of its first and last site with a cell
+// (lo > hi: none), LP / 64 entries.  stat: WLD_HEAT_R2 / WLD_HEAT_ABS_DPRIME.
+struct HeatmapArgs {
+    unsigned long long *classes;
+    unsigned long long *count;
+    double *sum;
+    uint32_t *max_key;
+    const int32_t *site_cell;
+    const int32_t *blk_lo, *blk_hi;
+    uint32_t n_cells;
+    int stat;
+};
+
 // encode.hip
 // site_index: nullptr, or the kept-site map of the device pre-pass (row s of the
 // filtered set = raw row site_index[s])
@@ -211,6 +229,11 @@ void launch_ref_layout(const uint8_t *codes, const float *w_pad, size_t LP, size
 // in lib.rs's order and reduced into s; o gives the window (win_hi) only —
 // nothing of the row path's run state is read or written.
 void launch_pair_summary(const ValuLaunch &v, const OrderArgs &o, const SummaryArgs &s, hipStream_t st);
+
+// pair_heatmap.hip
+// The same sums over v's list (the heat map's own filtered tile list), every
+// considered pair reduced into its cell of h; o gives the window only.
+void launch_pair_heatmap(const ValuLaunch &v, const OrderArgs &o, const HeatmapArgs &h, hipStream_t st);
 
 // pair_targets.hip (wld_run_targets): one batch of target blocks against their
 // partner tiles.  Slot 16 b + j is the j-th target of the batch's block b.

@@ -215,7 +215,7 @@ void launch_pair_summary(const ValuLaunch &v, const OrderArgs &o, const SummaryA
     // one whole-tile workgroup per listed tile at every list size (the row
     // path's 16-row items below 3,072 tiles split a tile's columns over four
     // workgroups, which would issue four atomics per column)
-    hipLaunchKernelGGL((pair_valu_kernel<false, false, true, true, false, true>), dim3(v.n_tiles), dim3(256), 0, st,
+    hipLaunchKernelGGL((pair_valu_kernel<false, false, true, true, false, kReduceSummary>), dim3(v.n_tiles), dim3(256), 0, st,
                        v.codes, v.w, v.site_ok, v.tiles, v.n_tiles, (const unsigned *)nullptr,
                        (const uint32_t *)nullptr, (unsigned *)nullptr, (const unsigned *)nullptr, 0u, v.L, v.NP, 1u,
                        v.ref_cls / 64, v.ref_tail_n, v.n_chunk_rows, 0.0f, o, s, ScanArgs{});

@@ -45,9 +45,10 @@
 // the last workgroup runs the run's chunk scan (scan_tail).
 //
 // The kernel template lives in this header so that pair_valu.hip (the row
-// kernels) and pair_summary.hip (SUMMARY: the same operands, sums and
-// ld_epilogue, each tile reduced on chip instead of compacted into rows)
-// instantiate one body: there is no second copy of the sum stages to drift.
+// kernels), pair_summary.hip and pair_heatmap.hip (REDUCE: the same operands,
+// sums and ld_epilogue, each tile reduced on chip instead of compacted into
+// rows) instantiate one body: there is no second copy of the sum stages to
+// drift.
 #pragma once
 #include <type_traits>
 
@@ -77,24 +78,33 @@ typedef float v4f __attribute__((ext_vector_type(4)));
 #ifndef WLD_VALU_REF_WG
 #define WLD_VALU_REF_WG 3  // MF + REF: three workgroups per CU (<= 168 VGPRs; 2 leave 208)
 #endif
-// SUMMARY (pair_summary.hip; MF + REF, every sub-block of every listed tile):
-// no row is emitted; the tile's pairs are classified and reduced in the
-// workgroup (summary_epilogue) into the run's per-site, per-bin and total
-// accumulators.  The kernel then takes SummaryArgs where the row kernels take
-// DenseArgs; o gives it the window only.
+// REDUCE (MF + REF, every sub-block of every listed tile): no row is emitted;
+// the tile's pairs are classified and reduced in the workgroup into the run's
+// accumulators — kReduceSummary (pair_summary.hip, summary_epilogue): per
+// site, per bin and total; kReduceHeatmap (pair_heatmap.hip,
+// heatmap_epilogue): per cell of a site grid.  The kernel then takes
+// SummaryArgs / HeatmapArgs where the row kernels take DenseArgs; o gives it
+// the window only.
+constexpr int kReduceNone = 0, kReduceSummary = 1, kReduceHeatmap = 2;
 __device__ __attribute__((always_inline)) void summary_epilogue(const SummaryArgs &s, const OrderArgs &o,
                                                                 const uint8_t *site_ok, uint32_t L, uint32_t a0,
                                                                 uint32_t b0, uint32_t tid,
                                                                 const float (&tot)[4][4][4]);
-template <bool DENSE, bool SAFE, bool MF, bool REF, bool LOOP, bool SUMMARY = false>
+__device__ __attribute__((always_inline)) void heatmap_epilogue(const HeatmapArgs &h, const OrderArgs &o,
+                                                                const uint8_t *site_ok, uint32_t L, uint32_t a0,
+                                                                uint32_t b0, uint32_t tid,
+                                                                const float (&tot)[4][4][4]);
+template <bool DENSE, bool SAFE, bool MF, bool REF, bool LOOP, int REDUCE = kReduceNone>
 __global__ __launch_bounds__(256, MF ? (REF ? WLD_VALU_REF_WG : WLD_VALU_MF_WG) : 2) void pair_valu_kernel(
     const uint8_t *__restrict__ codes, const float *__restrict__ w, const uint8_t *__restrict__ site_ok,
     const uint32_t *__restrict__ tiles, uint32_t n_tiles, const unsigned *tile_count,
     const uint32_t *__restrict__ tile_bits, unsigned *tile_work, const unsigned *tile_buckets, uint32_t bucket_cap,
     uint32_t L, uint32_t NP, uint32_t flush,
     uint32_t ref_cs, uint32_t ref_tail_n, uint32_t n_chunk_rows, float thr, OrderArgs o,
-    std::conditional_t<SUMMARY, SummaryArgs, DenseArgs> dn, ScanArgs sa) {
-    static_assert(!SUMMARY || (MF && REF && !SAFE && !DENSE && !LOOP), "the summary runs lib.rs's order on f32 MFMA");
+    std::conditional_t<REDUCE == kReduceSummary, SummaryArgs,
+                       std::conditional_t<REDUCE == kReduceHeatmap, HeatmapArgs, DenseArgs>> dn,
+    ScanArgs sa) {
+    static_assert(!REDUCE || (MF && REF && !SAFE && !DENSE && !LOOP), "the reductions run lib.rs's order on f32 MFMA");
     constexpr int NS = 4;  // 16x16 slots per wave: a whole 64x64 tile per workgroup
     __shared__ __attribute__((aligned(16))) uint8_t sA[kTile * kStride];
     __shared__ __attribute__((aligned(16))) uint8_t sB[kTile * kStride];
@@ -397,10 +407,11 @@ __global__ __launch_bounds__(256, MF ? (REF ? WLD_VALU_REF_WG : WLD_VALU_MF_WG) 
             }
         }
 
-        if constexpr (SUMMARY) {
+        if constexpr (REDUCE != kReduceNone) {
             // (bits 0xFFFF: wave w holds a rows 16 w + 4 g + i against b column
-            // 16 j + r in tot[i][j], the mapping summary_epilogue assumes)
-            summary_epilogue(dn, o, site_ok, L, a0, b0, tid, tot);
+            // 16 j + r in tot[i][j], the mapping the reducing epilogues assume)
+            if constexpr (REDUCE == kReduceSummary) summary_epilogue(dn, o, site_ok, L, a0, b0, tid, tot);
+            else heatmap_epilogue(dn, o, site_ok, L, a0, b0, tid, tot);
             return;
         }
         // ---- epilogue ------------------------------------------------------
