@@ -265,6 +265,10 @@ int wld_set_kernel(wld_ctx *ctx, int kernel);
  *                      a batch always holds at least one block of 16 targets).
  *                      Changes no result; it exists so tests can force several
  *                      batches.
+ *   WLD_OPT_PARTNERS_BATCH_BYTES  wld_run_partners: the bytes of tile staging
+ *                      one batch may use (default 2^30; a batch always holds at
+ *                      least one tile).  Changes no bit of a result; it exists
+ *                      to bound memory and so tests can force several batches.
  *   WLD_OPT_TEST_GUARD 0 (default); 1 (tests only): before each candidate
  *                      launch the last candidate bucket's count is set one
  *                      past its capacity, so the launch meets an entry outside
@@ -290,6 +294,7 @@ int wld_set_kernel(wld_ctx *ctx, int kernel);
 #define WLD_OPT_FP6_A4 17
 #define WLD_OPT_TARGET_BATCH_SLOTS 18
 #define WLD_OPT_FP6_SHARED 19
+#define WLD_OPT_PARTNERS_BATCH_BYTES 20
 int wld_set_option(wld_ctx *ctx, int option, int64_t value);
 int wld_get_option(wld_ctx *ctx, int option, int64_t *value);
 
@@ -804,6 +809,84 @@ typedef struct {
 int  wld_run_targets(wld_ctx *ctx, const uint32_t *targets, uint32_t n_targets,
                      float r2_threshold, wld_target_rows *out);
 void wld_target_rows_free(wld_target_rows *r);
+
+/* ---- Best partners: the k strongest in-window LD partners of every site
+ * (not in the reference; the all-sites form of a proxy search: tag-SNP
+ * selection, imputation-panel design, the k-nearest-neighbour graph that
+ * clustering sites by LD starts from) ----
+ *
+ * wld_run_partners(ctx, k, r2_threshold, chunk_begin, chunk_end, &out) with
+ * 1 <= k <= WLD_PARTNERS_MAX_K.  For LOADED site s, a site p != s is a
+ * candidate iff the pair (a, b) = (min(s, p), max(s, p))
+ *   - lies in the linear chunk range [chunk_begin,chunk_end) (end 0 = all, as
+ *     wld_run_summary; a pair belongs to chunk (a/256, b/256)),
+ *   - lies in the context's current window (wld_set_window),
+ *   - has a statistic (single_weighted_ld_pair gives Some), and
+ *   - has r2 > r2_threshold strictly; NaN never passes, +inf does.
+ * That is the pass test of the default row path: p is a candidate of s iff
+ * the row path would emit the pair's row.
+ *
+ * Order.  The candidates of s are ordered by r2 descending under the total
+ * order of the f32 bit patterns (-0 sorts below +0; the heat map's max uses
+ * the same order), then by partner loaded index ascending.  Site s gets the
+ * first min(k, number of candidates) of them.
+ *
+ * Values.  d, d_prime and r2 are, bit for bit, the f32 values the default row
+ * path (WLD_OPT_REF_SUMS 1) puts in the row of pair (a, b); they are listed
+ * identically under both sites, d with the sign it has for the ordered pair
+ * (a, b).  The sums always run in lib.rs's order: the kernel choice,
+ * WLD_OPT_REF_SUMS and the screen options do not apply, and every 64x64 tile
+ * of the range and window is computed.
+ *
+ * Outputs (library-allocated; release with wld_partners_free), lists
+ * row-major [site * k + rank]:
+ *   n_sites, k  the shape of the lists;
+ *   count[n_sites]      the entries filled per site;
+ *   partner[n_sites*k]  LOADED indices; 0xFFFFFFFF past count;
+ *   d, d_prime, r2 [n_sites*k]  the pair's values; NaN past count;
+ *   pairs, none_pairs, passing_pairs  the considered pairs (in range and
+ *              window), those without a statistic, and those that pass (each
+ *              passing pair is a candidate of both of its sites); exact;
+ *   tiles      the 64x64 tiles launched;
+ *   kernel_ms  HIP-event time of the pair launch(es), summed over the batches;
+ *   merge_ms   HIP-event time of the merge launch(es), summed likewise
+ *              (device group: the slowest member's, both).
+ * The result is a pure function of the considered pairs: no value goes through
+ * an atomic, and everything but the two times is bitwise identical from run to
+ * run, across splits of the chunk range, across batch sizes
+ * (WLD_OPT_PARTNERS_BATCH_BYTES) and across device groups.
+ *
+ * wld_partners_merge(into, from) combines two results of the same shape over
+ * disjoint chunk ranges into the result of the union of the ranges: the lists
+ * merge under the same order, counters and tiles add, the times become the
+ * larger of the two.  On a device group (wld_create_multi) the range is
+ * sharded exactly as wld_run_summary shards it, the members run concurrently
+ * and their results are merged on the host in member order.
+ *
+ * WLD_E_ARG: k == 0 or k > WLD_PARTNERS_MAX_K; a NaN threshold; chunk_begin >
+ * chunk_end; non-finite weights (a load that takes the row path's select
+ * loop); wld_partners_merge on results of different shapes.  WLD_E_STATE:
+ * before a load, or while a run is in flight.  WLD_E_OOM leaves the context
+ * usable.  The call changes nothing a later row run depends on — it keeps its
+ * tile list in a buffer of its own — and wld_last_stats and the last run's
+ * rows stay as they were.  No progress callback. */
+#define WLD_PARTNERS_MAX_K 64
+#define WLD_PARTNERS_NONE 0xFFFFFFFFu
+typedef struct {
+    uint64_t n_sites;
+    uint32_t k;
+    uint32_t *count;   /* n_sites */
+    uint32_t *partner; /* n_sites*k, LOADED indices; WLD_PARTNERS_NONE past count */
+    float *d, *d_prime, *r2; /* n_sites*k; NaN past count */
+    uint64_t pairs, none_pairs, passing_pairs;
+    uint64_t tiles;    /* 64x64 tiles launched */
+    double kernel_ms;  /* HIP-event time of the pair launch(es) */
+    double merge_ms;   /* HIP-event time of the merge launch(es) */
+} wld_partners;
+int wld_run_partners(wld_ctx *ctx, uint32_t k, float r2_threshold, uint32_t chunk_begin, uint32_t chunk_end,
+                     wld_partners *out);
+int wld_partners_merge(wld_partners *into, const wld_partners *from);
+void wld_partners_free(wld_partners *p);
 
 #ifdef __cplusplus
 }

@@ -27,7 +27,7 @@ KERNEL_AUTO, KERNEL_VALU, KERNEL_MFMA = 0, 1, 2
 OPTIONS = {"prefilter": 1, "screen": 2, "tile_order": 3, "all_planes": 4, "mfma_layout": 5, "valu_plain": 6,
            "staging_rows": 7, "host_batch_pairs": 8, "ref_sums": 11, "fused_scan": 12, "screen_fp6": 13,
            "test_guard": 14, "fp6_pairs_min_tiles": 15, "i8_pairs": 16, "fp6_a4": 17,
-           "target_batch_slots": 18, "fp6_shared": 19}
+           "target_batch_slots": 18, "fp6_shared": 19, "partners_batch_bytes": 20}
 
 
 class WldError(RuntimeError):
@@ -141,6 +141,27 @@ class TargetRowsC(ctypes.Structure):
     ]
 
 
+PARTNERS_MAX_K, PARTNERS_NONE = 64, 0xFFFFFFFF
+
+
+class PartnersC(ctypes.Structure):
+    _fields_ = [
+        ("n_sites", ctypes.c_uint64),
+        ("k", ctypes.c_uint32),
+        ("count", ctypes.POINTER(ctypes.c_uint32)),
+        ("partner", ctypes.POINTER(ctypes.c_uint32)),
+        ("d", ctypes.POINTER(ctypes.c_float)),
+        ("d_prime", ctypes.POINTER(ctypes.c_float)),
+        ("r2", ctypes.POINTER(ctypes.c_float)),
+        ("pairs", ctypes.c_uint64),
+        ("none_pairs", ctypes.c_uint64),
+        ("passing_pairs", ctypes.c_uint64),
+        ("tiles", ctypes.c_uint64),
+        ("kernel_ms", ctypes.c_double),
+        ("merge_ms", ctypes.c_double),
+    ]
+
+
 PROGRESS_FN = ctypes.CFUNCTYPE(None, ctypes.c_uint64, ctypes.c_void_p)
 
 # name -> (restype, argtypes); every symbol include/weightedld.h declares.
@@ -227,6 +248,10 @@ SIGNATURES = {
                                ctypes.POINTER(ctypes.c_double)]),
     "wld_run_targets": (_int, [_vp, _u32p, ctypes.c_uint32, ctypes.c_float, ctypes.POINTER(TargetRowsC)]),
     "wld_target_rows_free": (None, [ctypes.POINTER(TargetRowsC)]),
+    "wld_run_partners": (_int, [_vp, ctypes.c_uint32, ctypes.c_float, ctypes.c_uint32, ctypes.c_uint32,
+                                ctypes.POINTER(PartnersC)]),
+    "wld_partners_merge": (_int, [ctypes.POINTER(PartnersC), ctypes.POINTER(PartnersC)]),
+    "wld_partners_free": (None, [ctypes.POINTER(PartnersC)]),
 }
 
 _lib = None

@@ -13,13 +13,14 @@ from collections import namedtuple
 
 import numpy as np
 
-from ._lib import (HEAT_ABS_DPRIME, HEAT_MAX_CELLS, HEAT_R2, KERNEL_AUTO, KERNEL_MFMA, KERNEL_VALU, OPTIONS, PROGRESS_FN,
-                   Heatmap, Pairs, Prune, RunStats, Summary, TargetRowsC, WldError, check, lib)
+from ._lib import (HEAT_ABS_DPRIME, HEAT_MAX_CELLS, HEAT_R2, KERNEL_AUTO, KERNEL_MFMA, KERNEL_VALU, OPTIONS,
+                   PARTNERS_MAX_K, PARTNERS_NONE, PROGRESS_FN, Heatmap, Pairs, PartnersC, Prune, RunStats, Summary,
+                   TargetRowsC, WldError, check, lib)
 
 __all__ = [
     "Symbol", "SymbolHistogram", "SiteSet", "LdStats", "PairStore", "read_fasta", "read_vcf",
     "is_site_of_interest", "henikoff_weights", "single_weighted_ld_pair", "all_weighted_ld_pairs",
-    "ld_summary", "LdSummary", "ld_heatmap", "LdHeatmap", "heatmap_cells", "ld_prune", "LdPrune", "maf_priority", "ld_targets", "TargetRows", "Context", "default_context", "KERNEL_AUTO", "KERNEL_VALU", "KERNEL_MFMA", "OPTIONS", "WldError",
+    "ld_summary", "LdSummary", "ld_heatmap", "LdHeatmap", "heatmap_cells", "ld_prune", "LdPrune", "maf_priority", "ld_targets", "TargetRows", "ld_partners", "LdPartners", "PARTNERS_MAX_K", "PARTNERS_NONE", "Context", "default_context", "KERNEL_AUTO", "KERNEL_VALU", "KERNEL_MFMA", "OPTIONS", "WldError",
 ]
 
 
@@ -248,6 +249,76 @@ class LdHeatmap:
 
 
 HEAT_STATS = {"r2": HEAT_R2, "dprime": HEAT_ABS_DPRIME}
+
+
+class LdPartners:
+    """wld_partners as numpy arrays and ints (Context.run_partners,
+    ld_partners): count (uint32, [L]) and the [L, k] lists partner (uint32
+    LOADED indices, PARTNERS_NONE past count), d, d_prime and r2 (float32, NaN
+    past count) — row s holds site s's best partners, r2 descending then
+    partner ascending — the counters pairs, none_pairs and passing_pairs,
+    tiles, kernel_ms and merge_ms."""
+
+    FIELDS = ("count", "partner", "d", "d_prime", "r2")
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    @property
+    def n_sites(self):
+        return int(self.count.shape[0])
+
+    @property
+    def k(self):
+        return int(self.partner.shape[1])
+
+    def parents(self, site_map=None):
+        """(site, partner) in parent coordinates: site [L] and partner [L, k]
+        as uint64, site_map[i] for loaded index i (None: the indices
+        themselves); partner is 2^64 - 1 past count."""
+        L = self.n_sites
+        sm = np.arange(L, dtype=np.uint64) if site_map is None else np.asarray(site_map, dtype=np.uint64).reshape(-1)
+        if sm.size != L:
+            raise ValueError("site_map has %d entries for %d sites" % (sm.size, L))
+        filled = self.partner != PARTNERS_NONE
+        part = np.full(self.partner.shape, np.iinfo(np.uint64).max, dtype=np.uint64)
+        part[filled] = sm[self.partner[filled].astype(np.int64)]
+        return sm.copy(), part
+
+    def rows(self, site_map=None):
+        """The flattened table (site, partner, rank, d, d_prime, r2) of the
+        filled entries, by site then rank (rank 0 = the best partner); site
+        and partner in parent coordinates when site_map is given."""
+        site, part = self.parents(site_map)
+        s, rank = np.nonzero(self.partner != PARTNERS_NONE)  # (row-major: by site, then rank)
+        return (site[s], part[s, rank], rank.astype(np.uint32), self.d[s, rank], self.d_prime[s, rank],
+                self.r2[s, rank])
+
+    def _to_c(self):
+        c = PartnersC()
+        keep = [np.ascontiguousarray(self.count, dtype=np.uint32),
+                np.ascontiguousarray(self.partner, dtype=np.uint32),
+                np.ascontiguousarray(self.d, dtype=np.float32), np.ascontiguousarray(self.d_prime, dtype=np.float32),
+                np.ascontiguousarray(self.r2, dtype=np.float32)]
+        keep = [a.copy() for a in keep]
+        c.n_sites, c.k = self.n_sites, self.k
+        c.count, c.partner = _p(keep[0], ctypes.c_uint32), _p(keep[1], ctypes.c_uint32)
+        c.d, c.d_prime, c.r2 = (_p(a, ctypes.c_float) for a in keep[2:])
+        c.pairs, c.none_pairs, c.passing_pairs = self.pairs, self.none_pairs, self.passing_pairs
+        c.tiles, c.kernel_ms, c.merge_ms = self.tiles, self.kernel_ms, self.merge_ms
+        return c, keep
+
+    def merge(self, other):
+        """wld_partners_merge: the result over the union of this result's and
+        other's (disjoint) chunk ranges, as a new LdPartners."""
+        a, keep = self._to_c()
+        b, keep_b = other._to_c()
+        check(lib().wld_partners_merge(ctypes.byref(a), ctypes.byref(b)), "wld_partners_merge")
+        L, k = self.n_sites, self.k
+        return LdPartners(count=keep[0], partner=keep[1].reshape(L, k), d=keep[2].reshape(L, k),
+                          d_prime=keep[3].reshape(L, k), r2=keep[4].reshape(L, k), pairs=int(a.pairs),
+                          none_pairs=int(a.none_pairs), passing_pairs=int(a.passing_pairs), tiles=int(a.tiles),
+                          kernel_ms=float(a.kernel_ms), merge_ms=float(a.merge_ms))
 
 
 def heatmap_cells(site_map_or_siteset, n_sites=None, *, sites_per_cell=None, cell_width=None, edges=None,
@@ -636,6 +707,32 @@ class Context:
         lib().wld_heatmap_free(ctypes.byref(out))
         return res
 
+    def run_partners(self, k, r2_threshold, chunk_begin=0, chunk_end=0):
+        """wld_run_partners: for every LOADED site its best k partners (r2 >
+        r2_threshold, r2 descending then partner ascending) among the pairs of
+        the linear chunk range (end 0 = all) under the context's window, as an
+        LdPartners; values bit-identical to the default row path's row of the
+        pair.  1 <= k <= PARTNERS_MAX_K."""
+        out = PartnersC()
+        k = int(k)
+        if k < 0 or k > 0xFFFFFFFF:
+            raise ValueError("k must be between 1 and %d" % PARTNERS_MAX_K)
+        check(lib().wld_run_partners(self._h, k, r2_threshold, chunk_begin, chunk_end, ctypes.byref(out)),
+              "wld_run_partners")
+        L, kk = int(out.n_sites), int(out.k)
+
+        def grab(p, shape, dt):
+            return (np.ctypeslib.as_array(p, shape=shape).astype(dt, copy=True) if L
+                    else np.zeros(shape, dtype=dt))
+
+        res = LdPartners(count=grab(out.count, (L,), np.uint32), partner=grab(out.partner, (L, kk), np.uint32),
+                         d=grab(out.d, (L, kk), np.float32), d_prime=grab(out.d_prime, (L, kk), np.float32),
+                         r2=grab(out.r2, (L, kk), np.float32), pairs=int(out.pairs), none_pairs=int(out.none_pairs),
+                         passing_pairs=int(out.passing_pairs), tiles=int(out.tiles), kernel_ms=float(out.kernel_ms),
+                         merge_ms=float(out.merge_ms))
+        lib().wld_partners_free(ctypes.byref(out))
+        return res
+
     def run_prune(self, r2_threshold, priority=None):
         """wld_run_prune: the greedy r2-independent set of the loaded sites at
         this threshold under the context's window, as an LdPrune (keep, tag in
@@ -947,6 +1044,29 @@ def ld_targets(site_set, weights, r2_threshold, targets=None, parents=None, max_
     finally:
         ctx.set_window(*before)
     res.targets = targets.astype(np.uint32)
+    return res
+
+
+def ld_partners(site_set, weights, k, r2_threshold, max_distance=None, max_sites=None, ctx=None):
+    """Best partners (not in the reference; the all-sites form of a proxy
+    search): loads site_set and runs Context.run_partners(k, r2_threshold)
+    under the window max_distance / max_sites (the context's own window is
+    restored afterwards).  Returns an LdPartners indexed by the set's own site
+    index, with site_map, the set's parent coordinates (None without a map)."""
+    ctx = ctx or default_context()
+    w = np.ascontiguousarray(weights, dtype=np.float32)
+    if w.size != site_set.n_seqs():
+        raise ValueError("weights must have n_seqs entries")
+    before = ctx.window()
+    if max_distance is not None or max_sites is not None:
+        ctx.set_window(max_distance, max_sites)
+    try:
+        sm = site_set.site_map
+        ctx.load(site_set.buffer, w, sm)
+        res = ctx.run_partners(k, r2_threshold)
+    finally:
+        ctx.set_window(*before)
+    res.site_map = sm
     return res
 
 

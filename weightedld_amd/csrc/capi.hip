@@ -26,6 +26,7 @@
 #include "window_plan.hpp"
 #include "summary_plan.hpp"
 #include "heatmap_plan.hpp"
+#include "partners_plan.hpp"
 #include "prune_plan.hpp"
 #include "targets_plan.hpp"
 #include "kernels.hpp"
@@ -138,6 +139,7 @@ struct wld_ctx {
     bool opt_ref_sums = true;  // WLD_OPT_REF_SUMS: lib.rs's own f32 summation order (default)
     uint64_t opt_staging_rows = 1ull << 25, opt_host_batch_pairs = 1ull << 31;
     uint64_t opt_target_slots = targets_plan::kDefaultBatchSlots;  // WLD_OPT_TARGET_BATCH_SLOTS
+    uint64_t opt_partners_bytes = partners_plan::kDefaultBatchBytes;  // WLD_OPT_PARTNERS_BATCH_BYTES
 
     // loaded SiteSet
     bool loaded = false;
@@ -235,6 +237,11 @@ struct wld_ctx {
     DevBuf heat_buf, heat_tiles, heat_map;
     hipEvent_t ev_heat[2] = {};
 
+    // wld_run_partners: its own tile list, a batch's staging (entries and
+    // counts), the batch's CSR, the running lists and the words {classes[3],
+    // guard}; its events are created per call
+    DevBuf pt_tiles, pt_stage, pt_cnt, pt_csr, pt_run, pt_words;
+
     // wld_run_prune: while it runs, the gathers leave loaded indices in
     // out_a/out_b (no site_map); its four events (created at the first prune:
     // before the CSR build, after it, after the rounds, after the tags) and
@@ -264,7 +271,7 @@ struct wld_ctx {
         // buffers: it completes before they are freed
         if (stream && stream != own_stream) (void)hipStreamSynchronize(stream);
         DevBuf *all[] = {&keep, &htab, &htab_kept, &site_index, &raw, &wraw, &codes, &w_pad, &wstats, &site_ok, &site_map, &planes, &frag, &rcodes, &rw, &w6, &w4, &f6a, &f6b, &f6marg, &i8a, &i8b, &tiles, &cand, &f6_pairs, &fp6_probe_buf,
-                         &seg_cnt, &seg_off, &chunk_total, &chunk_base, &counters, &chunk_left, &prog_n, &win_hi, &win_pairs, &sum_buf, &heat_buf, &heat_tiles, &heat_map, &st_a, &st_b, &st_d,
+                         &seg_cnt, &seg_off, &chunk_total, &chunk_base, &counters, &chunk_left, &prog_n, &win_hi, &win_pairs, &sum_buf, &heat_buf, &heat_tiles, &heat_map, &pt_tiles, &pt_stage, &pt_cnt, &pt_csr, &pt_run, &pt_words, &st_a, &st_b, &st_d,
                          &st_dp, &st_r2, &out_a, &out_b, &out_d, &out_dp, &out_r2};
         for (DevBuf *b : all) release(*b);
         for (DevBuf *b : tg.all()) release(*b);
@@ -288,7 +295,7 @@ namespace {
 
 // Every single-device entry point starts here; a device group (wld_create_multi)
 // supports only wld_load, wld_run_host, wld_all_weighted_ld_pairs,
-// wld_run_summary, wld_run_heatmap and the option/kernel/stats calls, which dispatch to its
+// wld_run_summary, wld_run_heatmap, wld_run_partners and the option/kernel/stats calls, which dispatch to its
 // members.
 int set_dev(wld_ctx *c) {
     if (!c) return fail(WLD_E_ARG, "null context");
@@ -1025,6 +1032,10 @@ int wld_set_option(wld_ctx *c, int option, int64_t value) {
             if (value < 1) return fail(WLD_E_ARG, "WLD_OPT_TARGET_BATCH_SLOTS must be >= 1");
             c->opt_target_slots = (uint64_t)value;
             break;
+        case WLD_OPT_PARTNERS_BATCH_BYTES:
+            if (value < 1) return fail(WLD_E_ARG, "WLD_OPT_PARTNERS_BATCH_BYTES must be >= 1");
+            c->opt_partners_bytes = (uint64_t)value;
+            break;
         case WLD_OPT_FUSED_SCAN: c->opt_fused_scan = value != 0; break;
         case WLD_OPT_I8_PAIRS: c->opt_i8_pairs = value != 0; break;
         case WLD_OPT_TEST_GUARD: c->opt_test_guard = value != 0; break;
@@ -1155,6 +1166,7 @@ int wld_get_option(wld_ctx *c, int option, int64_t *value) {
         case WLD_OPT_STAGING_ROWS: *value = (int64_t)c->opt_staging_rows; break;
         case WLD_OPT_HOST_BATCH_PAIRS: *value = (int64_t)c->opt_host_batch_pairs; break;
         case WLD_OPT_TARGET_BATCH_SLOTS: *value = (int64_t)c->opt_target_slots; break;
+        case WLD_OPT_PARTNERS_BATCH_BYTES: *value = (int64_t)c->opt_partners_bytes; break;
         case WLD_OPT_FUSED_SCAN: *value = c->opt_fused_scan; break;
         case WLD_OPT_TEST_GUARD: *value = c->opt_test_guard; break;
         case WLD_OPT_FP6_PAIRS_MIN_TILES: *value = c->opt_fp6_pairs_min; break;
@@ -2434,6 +2446,302 @@ void wld_heatmap_free(wld_heatmap *h) {
     free(h->sum);
     free(h->max);
     memset(h, 0, sizeof(*h));
+}
+
+
+namespace {
+// What wld_run_partners refuses, checked on a loaded single-device context
+// (every member of a group holds the same load).
+int partners_check(wld_ctx *c, uint32_t k, float thr) {
+    if (k == 0) return fail(WLD_E_ARG, "wld_run_partners: k 0");
+    if (k > WLD_PARTNERS_MAX_K)
+        return fail(WLD_E_ARG, "wld_run_partners: k %u exceeds %u", k, (unsigned)WLD_PARTNERS_MAX_K);
+    if (std::isnan(thr)) return fail(WLD_E_ARG, "wld_run_partners: the threshold is NaN");
+    if (c->safe)
+        return fail(WLD_E_ARG, "wld_run_partners needs finite weights (this load takes the select loop)");
+    return WLD_OK;
+}
+
+// The per-call events of a best-partner run: three per batch (before the pair
+// launch, after it, after the merge), destroyed on every path.
+struct PartnerEvents {
+    std::vector<hipEvent_t> ev;
+    ~PartnerEvents() {
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+};
+
+// The best partners of the linear chunks [lb, le) on one device (k, thr
+// checked): the range's tile list under the window in a buffer of its own —
+// the row path's cached list, its range and seg_clear are not touched — cut
+// into staging batches; per batch one pair launch and one merge launch; one
+// copy back of the running lists.  Touches no staging, segment count, chunk
+// total, run counter or row-path event of the row path.
+int partners_range(wld_ctx *c, uint32_t k, float thr, uint32_t lb, uint32_t le, partners_plan::Partners *out) {
+    WLD_TRY(set_dev(c));
+    if (!c->loaded) return fail(WLD_E_STATE, "wld_run_partners before wld_load");
+    if (c->pend.active) return fail(WLD_E_STATE, "wld_run_partners during a run");
+    const size_t L = c->L, LP = c->LP, TB = LP / kTile;
+    const uint32_t kp = std::min<uint32_t>(k, kTile);
+    *out = partners_plan::Partners{};
+    out->n_sites = (uint32_t)L;
+    out->k = k;
+    try {
+        out->list.assign(L * k, partners_plan::Entry{partners_plan::kNoKey, 0.0f, 0.0f});
+    } catch (const std::bad_alloc &) {
+        return fail(WLD_E_OOM, "host allocation of the partner lists (%zu sites x %u) failed", L, k);
+    }
+    if (lb >= le) return WLD_OK;
+    const bool windowed = window_on(c);
+    if (windowed && c->win_hi_host.size() != L) return fail(WLD_E_STATE, "internal: the window has no plan");
+    const uint32_t T_used = (uint32_t)((L + kTile - 1) / kTile), n = chunk_rows_of(L);
+    std::vector<uint32_t> t =
+        windowed ? window_plan::range_tiles(n, T_used, lb, le, c->win_hi_host) : tile_order::range_tiles(n, T_used, lb, le);
+    out->tiles = t.size();
+    const uint64_t expect =
+        partners_plan::considered_pairs(windowed ? c->win_hi_host.data() : nullptr, (uint32_t)L, lb, le);
+    if (t.empty()) {
+        if (expect) return fail(WLD_E_HIP, "internal: the partner run's tile list is empty; the range holds %llu pairs",
+                                (unsigned long long)expect);
+        return WLD_OK;
+    }
+    if (!c->opt_tile_rows && t.size() >= 4096 && T_used < 65535)
+        t = xcd_order(t, tile_order::super_block_side((uint32_t)c->NP));
+    WLD_TRY(ensure_ref_layout(c));
+    const auto cuts = partners_plan::batches(t.size(), c->opt_partners_bytes, kp);
+    uint64_t max_tiles = 0;
+    for (const auto &b : cuts) max_tiles = std::max(max_tiles, b.second - b.first);
+    if (partners_plan::parts_of(max_tiles) > 0xFFFFFFFFull)
+        return fail(WLD_E_ARG, "WLD_OPT_PARTNERS_BATCH_BYTES: a batch of %llu tiles is too large",
+                    (unsigned long long)max_tiles);
+    // the batches' CSRs, alive until the stream has copied them
+    std::vector<partners_plan::Csr> csr;
+    size_t max_ent = 0;
+    for (const auto &b : cuts) {
+        csr.push_back(partners_plan::build_csr(t.data(), b.first, b.second, T_used));
+        max_ent = std::max(max_ent, csr.back().ent.size());
+    }
+    const size_t n_parts_max = (size_t)partners_plan::parts_of(max_tiles);
+    const size_t run_bytes = TB * kTile * (size_t)k * sizeof(PartnerEntry), words_bytes = 4 * sizeof(unsigned long long);
+    // the staging goes back after the call where it is large
+    struct StageRelease {
+        wld_ctx *c;
+        ~StageRelease() {
+            if (c->pt_stage.bytes > (64u << 20)) {
+                (void)hipStreamSynchronize(c->stream);
+                release(c->pt_stage);
+                release(c->pt_cnt);
+            }
+        }
+    } stage_release{c};
+    WLD_TRY(ensure(c->pt_tiles, t.size() * sizeof(uint32_t)));
+    WLD_TRY(ensure(c->pt_stage, n_parts_max * kp * sizeof(PartnerEntry)));
+    WLD_TRY(ensure(c->pt_cnt, n_parts_max * sizeof(uint32_t)));
+    WLD_TRY(ensure(c->pt_csr, (T_used + 1 + max_ent) * sizeof(uint32_t)));
+    WLD_TRY(ensure(c->pt_run, run_bytes));
+    WLD_TRY(ensure(c->pt_words, words_bytes));
+    PartnerEvents pe;
+    pe.ev.assign(3 * cuts.size(), nullptr);
+    for (auto &e : pe.ev) HIP_TRY(hipEventCreate(&e));
+    HIP_TRY(hipMemcpyAsync(c->pt_tiles.p, t.data(), t.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(c->pt_run.p, 0, run_bytes, c->stream));
+    HIP_TRY(hipMemsetAsync(c->pt_words.p, 0, words_bytes, c->stream));
+    unsigned long long *d_cls = ptr<unsigned long long>(c->pt_words);
+    unsigned *d_guard = reinterpret_cast<unsigned *>(d_cls + 3);
+    OrderArgs o{};  // the window only
+    o.L = (uint32_t)L;
+    o.T = (uint32_t)TB;
+    o.win_hi = windowed ? ptr<uint32_t>(c->win_hi) : nullptr;
+    for (size_t bi = 0; bi < cuts.size(); ++bi) {
+        const uint64_t b0 = cuts[bi].first, nb = cuts[bi].second - b0;
+        const partners_plan::Csr &cs = csr[bi];
+        uint32_t *d_off = ptr<uint32_t>(c->pt_csr), *d_ent = d_off + T_used + 1;
+        HIP_TRY(hipMemcpyAsync(d_off, cs.off.data(), cs.off.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        if (!cs.ent.empty())
+            HIP_TRY(hipMemcpyAsync(d_ent, cs.ent.data(), cs.ent.size() * sizeof(uint32_t), hipMemcpyHostToDevice,
+                                   c->stream));
+        ValuLaunch v = ref_valu_launch(c, thr);  // (finite weights: partners_check)
+        v.tiles = ptr<uint32_t>(c->pt_tiles) + b0;
+        v.n_tiles = (uint32_t)nb;
+        const PartnersArgs pa{d_cls, ptr<PartnerEntry>(c->pt_stage), ptr<uint32_t>(c->pt_cnt), kp, d_guard};
+        const PartnersMerge pm{ptr<PartnerEntry>(c->pt_stage), ptr<uint32_t>(c->pt_cnt), kp, k,
+                               (uint32_t)partners_plan::parts_of(nb), d_off, d_ent, (uint32_t)cs.ent.size(), T_used,
+                               (uint32_t)L, ptr<PartnerEntry>(c->pt_run), d_guard};
+        HIP_TRY(hipEventRecord(pe.ev[3 * bi], c->stream));
+        launch_pair_partners(v, o, pa, c->stream);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(pe.ev[3 * bi + 1], c->stream));
+        launch_partners_merge(pm, c->stream);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(pe.ev[3 * bi + 2], c->stream));
+    }
+    unsigned long long words[4] = {0, 0, 0, 0};
+    static_assert(sizeof(partners_plan::Entry) == sizeof(PartnerEntry), "one entry layout on host and device");
+    if (L) HIP_TRY(hipMemcpyAsync(out->list.data(), c->pt_run.p, L * k * sizeof(PartnerEntry), hipMemcpyDeviceToHost,
+                                  c->stream));
+    HIP_TRY(hipMemcpyAsync(words, c->pt_words.p, words_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));  // (t and the CSRs are read by the copies)
+    for (size_t bi = 0; bi < cuts.size(); ++bi) {
+        out->kernel_ms += event_ms(pe.ev[3 * bi], pe.ev[3 * bi + 1]);
+        out->merge_ms += event_ms(pe.ev[3 * bi + 1], pe.ev[3 * bi + 2]);
+    }
+    const unsigned guard = (unsigned)(words[3] & 0xFFFFFFFFu);
+    if (guard)
+        return fail(WLD_E_STATE, "wld_run_partners: a kernel refused an index (guard %u: %s%s%s)", guard,
+                    guard & kPartnersGuardTile ? "tile " : "", guard & kPartnersGuardEntry ? "CSR entry " : "",
+                    guard & kPartnersGuardPart ? "part count" : "");
+    out->pairs = words[0];
+    out->none_pairs = words[1];
+    out->passing_pairs = words[2];
+    // the kernel's own accounting against the host's plan
+    uint64_t listed = 0;
+    for (const partners_plan::Entry &e : out->list) listed += e.key != partners_plan::kNoKey;
+    if (out->pairs != expect || out->none_pairs + out->passing_pairs > out->pairs || listed > 2 * out->passing_pairs)
+        return fail(WLD_E_HIP, "internal: partner run counted %llu pairs (%llu none, %llu passing, %llu listed); "
+                               "the range holds %llu",
+                    (unsigned long long)out->pairs, (unsigned long long)out->none_pairs,
+                    (unsigned long long)out->passing_pairs, (unsigned long long)listed, (unsigned long long)expect);
+    return WLD_OK;
+}
+
+// ... on a device group: member g takes its shard of the chunk sequence (as
+// summary_group deals them) cut to [lb, le), on its own host thread; the
+// members' results are merged in member order.
+int partners_group(wld_ctx *g, uint32_t k, float thr, uint32_t lb, uint32_t le, partners_plan::Partners *out) {
+    const int G = (int)g->members.size();
+    wld_ctx *c0 = g->members[0];
+    std::vector<uint32_t> sb(G), se(G);
+    for (int i = 0; i < G; ++i) {  // every range before any thread starts
+        if (window_on(c0)) WLD_TRY(wld_shard_chunks_window(c0, G, i, &sb[i], &se[i]));
+        else WLD_TRY(wld_shard_chunks(c0->L, G, i, &sb[i], &se[i]));
+        sb[i] = std::max(sb[i], lb);
+        se[i] = std::max(sb[i], std::min(se[i], le));
+    }
+    std::vector<partners_plan::Partners> part(G);
+    std::vector<int> status(G, WLD_OK);
+    std::vector<std::string> msg(G);
+    std::vector<std::thread> th;
+    for (int i = 0; i < G; ++i)
+        th.emplace_back([&, i] {
+            status[i] = partners_range(g->members[i], k, thr, sb[i], se[i], &part[i]);
+            if (status[i] != WLD_OK) msg[i] = wld_last_error();
+        });
+    for (auto &t : th) t.join();
+    for (int i = 0; i < G; ++i)
+        if (status[i] != WLD_OK)
+            return fail(status[i], "device %d (shard %d): %s", g->members[i]->device, i, msg[i].c_str());
+    *out = partners_plan::Partners{};
+    for (int i = 0; i < G; ++i) partners_plan::merge(*out, part[i]);
+    return WLD_OK;
+}
+
+// lists <-> the caller's arrays
+int partners_alloc(wld_partners *out, size_t L, uint32_t k) {
+    const size_t n = std::max<size_t>(L * k, 1);
+    out->count = (uint32_t *)malloc(std::max<size_t>(L, 1) * sizeof(uint32_t));
+    out->partner = (uint32_t *)malloc(n * sizeof(uint32_t));
+    out->d = (float *)malloc(n * sizeof(float));
+    out->d_prime = (float *)malloc(n * sizeof(float));
+    out->r2 = (float *)malloc(n * sizeof(float));
+    if (!out->count || !out->partner || !out->d || !out->d_prime || !out->r2) {
+        wld_partners_free(out);
+        return fail(WLD_E_OOM, "host allocation of the partner lists (%zu sites x %u) failed", L, k);
+    }
+    return WLD_OK;
+}
+void partners_store(const partners_plan::Partners &p, wld_partners *out) {
+    const size_t L = p.n_sites, k = p.k;
+    for (size_t s = 0; s < L; ++s) {
+        uint32_t cnt = 0;
+        for (size_t i = 0; i < k; ++i) {
+            const partners_plan::Entry &e = p.list[s * k + i];
+            const bool have = e.key != partners_plan::kNoKey;
+            cnt += have;
+            out->partner[s * k + i] = have ? partners_plan::key_partner(e.key) : WLD_PARTNERS_NONE;
+            out->d[s * k + i] = have ? e.d : std::nanf("");
+            out->d_prime[s * k + i] = have ? e.dp : std::nanf("");
+            out->r2[s * k + i] = have ? partners_plan::key_r2(e.key) : std::nanf("");
+        }
+        out->count[s] = cnt;
+    }
+    out->n_sites = L;
+    out->k = (uint32_t)k;
+    out->pairs = p.pairs;
+    out->none_pairs = p.none_pairs;
+    out->passing_pairs = p.passing_pairs;
+    out->tiles = p.tiles;
+    out->kernel_ms = p.kernel_ms;
+    out->merge_ms = p.merge_ms;
+}
+void partners_fetch(const wld_partners *in, partners_plan::Partners &p) {
+    p.n_sites = (uint32_t)in->n_sites;
+    p.k = in->k;
+    p.pairs = in->pairs;
+    p.none_pairs = in->none_pairs;
+    p.passing_pairs = in->passing_pairs;
+    p.tiles = in->tiles;
+    p.kernel_ms = in->kernel_ms;
+    p.merge_ms = in->merge_ms;
+    const size_t L = in->n_sites, k = in->k;
+    p.list.assign(L * k, partners_plan::Entry{partners_plan::kNoKey, 0.0f, 0.0f});
+    for (size_t s = 0; s < L; ++s)
+        for (size_t i = 0; i < std::min<size_t>(k, in->count[s]); ++i)
+            p.list[s * k + i] = partners_plan::Entry{partners_plan::pack_key(in->r2[s * k + i], in->partner[s * k + i]),
+                                                     in->d[s * k + i], in->d_prime[s * k + i]};
+}
+}  // namespace
+
+int wld_run_partners(wld_ctx *c, uint32_t k, float r2_threshold, uint32_t chunk_begin, uint32_t chunk_end,
+                     wld_partners *out) {
+    if (!out) return fail(WLD_E_ARG, "null out");
+    memset(out, 0, sizeof(*out));
+    if (!c) return fail(WLD_E_ARG, "null context");
+    wld_ctx *c0 = c->members.empty() ? c : c->members[0];
+    for (wld_ctx *m : c->members.empty() ? std::vector<wld_ctx *>{c} : c->members) {
+        if (!m->loaded) return fail(WLD_E_STATE, "wld_run_partners before wld_load");
+        if (m->pend.active) return fail(WLD_E_STATE, "wld_run_partners during a run");
+    }
+    WLD_TRY(partners_check(c0, k, r2_threshold));
+    const uint32_t m = chunks_of(c0->L);
+    if (chunk_end == 0 || chunk_end > m) chunk_end = m;
+    if (chunk_begin > chunk_end) return fail(WLD_E_ARG, "chunk range [%u,%u) invalid", chunk_begin, chunk_end);
+    partners_plan::Partners p;
+    if (c->members.empty()) WLD_TRY(partners_range(c, k, r2_threshold, chunk_begin, chunk_end, &p));
+    else WLD_TRY(partners_group(c, k, r2_threshold, chunk_begin, chunk_end, &p));
+    WLD_TRY(partners_alloc(out, p.n_sites, k));
+    partners_store(p, out);
+    return WLD_OK;
+}
+
+int wld_partners_merge(wld_partners *into, const wld_partners *from) {
+    if (!into || !from) return fail(WLD_E_ARG, "wld_partners_merge: null argument");
+    if (into->n_sites != from->n_sites || into->k != from->k || !into->k)
+        return fail(WLD_E_ARG, "wld_partners_merge: shapes differ (%llu x %u and %llu x %u)",
+                    (unsigned long long)into->n_sites, into->k, (unsigned long long)from->n_sites, from->k);
+    if (into->n_sites && (!into->count || !into->partner || !into->d || !into->d_prime || !into->r2 || !from->count ||
+                          !from->partner || !from->d || !from->d_prime || !from->r2))
+        return fail(WLD_E_ARG, "wld_partners_merge: null list");
+    try {
+        partners_plan::Partners a, b;
+        partners_fetch(into, a);
+        partners_fetch(from, b);
+        partners_plan::merge(a, b);
+        partners_store(a, into);
+    } catch (const std::bad_alloc &) {
+        return fail(WLD_E_OOM, "wld_partners_merge: host allocation failed");
+    }
+    return WLD_OK;
+}
+
+void wld_partners_free(wld_partners *p) {
+    if (!p) return;
+    free(p->count);
+    free(p->partner);
+    free(p->d);
+    free(p->d_prime);
+    free(p->r2);
+    memset(p, 0, sizeof(*p));
 }
 
 namespace {

@@ -43,6 +43,13 @@
 //                      --r2-threshold's value), by target, then partner
 //                      (wld_run_targets: targets x sites pairs, not the
 //                      triangle); with it --pair-output may be left out
+//   --partners-output FILE   best-partner TSV (site, partner, rank, d, d', r2):
+//   --partners-k K           for every site of interest its K (1 to 64) strongest
+//   --partners-r2 T          in-window partners with r2 > T (default:
+//                      --r2-threshold's value), r2 descending then partner
+//                      ascending, one line per (site, rank), rank from 0
+//                      (wld_run_partners; parent indices as in the pair TSV);
+//                      with it --pair-output may be left out
 #include <chrono>
 #include <cinttypes>
 #include <cmath>
@@ -237,6 +244,11 @@ struct Opt {
     std::string ld_sites_file, ld_sites_output;
     bool have_ld_sites = false, have_ld_sites_r2 = false;
     float ld_sites_r2 = 0.0f;
+    // --partners-output / --partners-k / --partners-r2: wld_run_partners
+    std::string partners_output;
+    uint32_t partners_k = 0;
+    bool have_partners_k = false, have_partners_r2 = false;
+    float partners_r2 = 0.0f;
 };
 
 void usage(FILE *f) {
@@ -306,6 +318,13 @@ void usage(FILE *f) {
             "                                             site, d, d', r2: every in-window partner above the\n"
             "                                             threshold); --pair-output may then be left out\n"
             "        --ld-sites-r2 <ld-sites-r2>          (addition) Minimum value of R2 of a target row [default:\n"
+            "                                             --r2-threshold's value]\n"
+            "        --partners-output <partners-output>  (addition) Filename to write every site's best partners to\n"
+            "                                             (site, partner, rank, d, d', r2); needs --partners-k;\n"
+            "                                             obeys --max-distance, --max-sites and --devices;\n"
+            "                                             --pair-output may then be left out\n"
+            "        --partners-k <partners-k>            (addition) partners per site, 1 to 64\n"
+            "        --partners-r2 <partners-r2>          (addition) Minimum value of R2 of a partner [default:\n"
             "                                             --r2-threshold's value]\n");
 }
 
@@ -461,6 +480,18 @@ Opt parse(int argc, char **argv) {
         } else if (a == "--ld-sites-r2") {
             o.ld_sites_r2 = parse_f32(need("--ld-sites-r2").c_str(), "ld-sites-r2");
             o.have_ld_sites_r2 = true;
+        } else if (a == "--partners-output") {
+            o.partners_output = need("--partners-output");
+        } else if (a == "--partners-k") {
+            const std::string v = need("--partners-k");
+            if (v.empty() || v.find_first_not_of("0123456789") != std::string::npos || v.size() > 9 ||
+                strtoull(v.c_str(), nullptr, 10) < 1 || strtoull(v.c_str(), nullptr, 10) > WLD_PARTNERS_MAX_K)
+                arg_error("Invalid value for '--partners-k' (1 to 64):", v.c_str());
+            o.partners_k = (uint32_t)strtoull(v.c_str(), nullptr, 10);
+            o.have_partners_k = true;
+        } else if (a == "--partners-r2") {
+            o.partners_r2 = parse_f32(need("--partners-r2").c_str(), "partners-r2");
+            o.have_partners_r2 = true;
         } else if (a == "--kernel") {
             std::string k = need("--kernel");
             o.kernel = k == "valu" ? WLD_KERNEL_VALU : k == "mfma" ? WLD_KERNEL_MFMA : WLD_KERNEL_AUTO;
@@ -479,9 +510,16 @@ Opt parse(int argc, char **argv) {
     if (!ld_sel && o.have_ld_sites_r2) arg_error("The argument '--ld-sites-r2' needs", "--ld-sites-output <ld-sites-output>");
     if (ld_sel && o.devices.size() > 1)
         arg_error("The argument '--ld-sites-output' cannot be used with", "--devices (target sites run on one device)");
-    if (!have_pair && !ld_sel)
+    if (!o.partners_output.empty() && !o.have_partners_k)
+        arg_error("The following required arguments were not provided:", "--partners-k <partners-k>");
+    if (o.partners_output.empty() && o.have_partners_k)
+        arg_error("The argument '--partners-k' needs", "--partners-output <partners-output>");
+    if (o.partners_output.empty() && o.have_partners_r2)
+        arg_error("The argument '--partners-r2' needs", "--partners-output <partners-output>");
+    if (!have_pair && !ld_sel && o.partners_output.empty())
         arg_error("The following required arguments were not provided:", "--pair-output <pair-output>");
     if (!o.have_ld_sites_r2) o.ld_sites_r2 = o.r2_threshold;
+    if (!o.have_partners_r2) o.partners_r2 = o.r2_threshold;
     if (!o.decay_output.empty() && !o.decay_bin_width)
         arg_error("The following required arguments were not provided:", "--decay-bin-width <decay-bin-width>");
     if (o.decay_output.empty() && o.decay_bin_width)
@@ -897,6 +935,48 @@ void write_targets(const Opt &opt, wld_ctx *ctx, const std::vector<uint32_t> &ta
     wld_target_rows_free(&r);
 }
 
+// --partners-output: every site's best --partners-k partners at --partners-r2
+// under the window (wld_run_partners), by site then rank; parent indices and
+// the three numbers formatted as the targets' rows.
+void write_partners(const Opt &opt, wld_ctx *ctx, const std::vector<uint64_t> &parent) {
+    if (opt.partners_output.empty()) return;
+    using clk = std::chrono::steady_clock;
+    const auto sw = clk::now();
+    wld_partners r;
+    const int st = wld_run_partners(ctx, opt.partners_k, opt.partners_r2, 0, 0, &r);
+    if (st != WLD_OK) die(st, "run_partners");
+    INFO("Computed the best %u partners of %" PRIu64 " sites: %s pairs above r2 %g in %s", opt.partners_k, r.n_sites,
+         human((double)r.passing_pairs).c_str(), (double)opt.partners_r2, fmt_duration(clk::now() - sw).c_str());
+    INFO("Writing output to %s", debug_path(opt.partners_output).c_str());
+    std::string out = "site\tpartner\trank\td\td'\tr2\n";
+    char line[200];
+    for (uint64_t s = 0; s < r.n_sites && s < parent.size(); ++s)
+        for (uint32_t k = 0; k < r.count[s]; ++k) {
+            const uint64_t i = s * r.k + k;
+            if (r.partner[i] >= parent.size()) continue;
+            int m = fmt_u64(line, parent[s]);
+            line[m++] = '\t';
+            m += fmt_u64(line + m, parent[r.partner[i]]);
+            line[m++] = '\t';
+            m += fmt_u64(line + m, k);
+            line[m++] = '\t';
+            m += fmt3(line + m, r.d[i]);
+            line[m++] = '\t';
+            m += fmt3(line + m, r.d_prime[i]);
+            line[m++] = '\t';
+            m += fmt3(line + m, r.r2[i]);
+            line[m++] = '\n';
+            out.append(line, m);
+        }
+    FILE *f = fopen(opt.partners_output.c_str(), "wb");
+    const bool ok = f && fwrite(out.data(), 1, out.size(), f) == out.size();
+    if ((f && fclose(f) != 0) || !ok) {
+        fprintf(stderr, "Error: cannot write %s\n", opt.partners_output.c_str());
+        quit(1);
+    }
+    wld_partners_free(&r);
+}
+
 // (debug level only, so info-level output is the reference's: the LD pass's
 // progress_report calls — progress(0), then one per 256x256 chunk)
 void log_progress(const ProgressBar &pb) {
@@ -974,6 +1054,7 @@ int run_gpu_prepass(const Opt &opt, wld_siteset *siteset, wld_ctx *ctx) {
     write_summaries(opt, ctx, parent);
     write_heatmap(opt, ctx, heat_cells);
     write_targets(opt, ctx, targets);
+    write_partners(opt, ctx, parent);
     // (a FASTA set has no site_map: a kept site's parent index is its index in the unfiltered set)
     write_prune(opt, ctx, parent, siteset, std::vector<size_t>(parent.begin(), parent.end()));
     return finish(opt, ctx, pairs, dur, total_pairs);
@@ -1092,6 +1173,7 @@ int main(int argc, char **argv) {
     write_summaries(opt, ctx, parent);
     write_heatmap(opt, ctx, heat_cells);
     write_targets(opt, ctx, targets);
+    write_partners(opt, ctx, parent);
     std::vector<size_t> self(L);
     for (size_t i = 0; i < L; ++i) self[i] = i;
     write_prune(opt, ctx, parent, filtered, self);

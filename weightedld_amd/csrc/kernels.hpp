@@ -156,6 +156,41 @@ struct HeatmapArgs {
     int stat;
 };
 
+// The staging of one batch of a best-partner run (pair_partners.hip;
+// wld_run_partners; layout in partners_plan.hpp).  Tile position p of the
+// launch's list (p < n_tiles, the workgroup id) owns the parts (2 p + side) *
+// 64 + local site: cnt[part] = its entries, min(kp, the site's candidates in
+// the tile), written for every part of a listed tile; stage[part * kp + rank]
+// = {key, d, d'}, rank < cnt[part], best first.  Nothing of it needs zeroing.
+// classes = {pairs, none, passing} (zero before the run's first launch), one
+// atomic each per tile.  guard: a device word, zero before the launch.
+struct PartnerEntry {
+    unsigned long long key;
+    float d, dp;
+};
+struct PartnersArgs {
+    unsigned long long *classes;
+    PartnerEntry *stage;
+    uint32_t *cnt;
+    uint32_t kp;  // list length per part: min(k, 64)
+    unsigned *guard;
+};
+// The merge of a batch into the running lists run[site * k + rank] (k entries
+// per site, best first, key 0 past the site's count; all zero before the first
+// batch): csr_off [n_blocks + 1] / csr_ent: per 64-site block the (2 position +
+// side) entries of the batch that hold parts of its sites.
+struct PartnersMerge {
+    const PartnerEntry *stage;
+    const uint32_t *cnt;
+    uint32_t kp, k;
+    uint32_t n_parts;  // 128 x the batch's tiles
+    const uint32_t *csr_off, *csr_ent;
+    uint32_t n_ent, n_blocks, L;
+    PartnerEntry *run;
+    unsigned *guard;
+};
+constexpr unsigned kPartnersGuardTile = 1, kPartnersGuardEntry = 2, kPartnersGuardPart = 4;
+
 // encode.hip
 // site_index: nullptr, or the kept-site map of the device pre-pass (row s of the
 // filtered set = raw row site_index[s])
@@ -234,6 +269,14 @@ void launch_pair_summary(const ValuLaunch &v, const OrderArgs &o, const SummaryA
 // The same sums over v's list (the heat map's own filtered tile list), every
 // considered pair reduced into its cell of h; o gives the window only.
 void launch_pair_heatmap(const ValuLaunch &v, const OrderArgs &o, const HeatmapArgs &h, hipStream_t st);
+
+// pair_partners.hip
+// The same sums over v's list (one batch of the run's own tile list, v.thr the
+// run's threshold); every tile's candidates selected per a row and per b
+// column into the batch's staging; o gives the window only.  Then the merge of
+// the staged parts into the running lists.
+void launch_pair_partners(const ValuLaunch &v, const OrderArgs &o, const PartnersArgs &p, hipStream_t st);
+void launch_partners_merge(const PartnersMerge &m, hipStream_t st);
 
 // pair_targets.hip (wld_run_targets): one batch of target blocks against their
 // partner tiles.  Slot 16 b + j is the j-th target of the batch's block b.

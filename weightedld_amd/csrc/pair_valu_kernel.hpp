@@ -45,10 +45,10 @@
 // the last workgroup runs the run's chunk scan (scan_tail).
 //
 // The kernel template lives in this header so that pair_valu.hip (the row
-// kernels), pair_summary.hip and pair_heatmap.hip (REDUCE: the same operands,
-// sums and ld_epilogue, each tile reduced on chip instead of compacted into
-// rows) instantiate one body: there is no second copy of the sum stages to
-// drift.
+// kernels), pair_summary.hip, pair_heatmap.hip and pair_partners.hip (REDUCE:
+// the same operands, sums and ld_epilogue, each tile reduced on chip instead of
+// compacted into rows) instantiate one body: there is no second copy of the
+// sum stages to drift.
 #pragma once
 #include <type_traits>
 
@@ -82,10 +82,12 @@ typedef float v4f __attribute__((ext_vector_type(4)));
 // the tile's pairs are classified and reduced in the workgroup into the run's
 // accumulators — kReduceSummary (pair_summary.hip, summary_epilogue): per
 // site, per bin and total; kReduceHeatmap (pair_heatmap.hip,
-// heatmap_epilogue): per cell of a site grid.  The kernel then takes
-// SummaryArgs / HeatmapArgs where the row kernels take DenseArgs; o gives it
+// heatmap_epilogue): per cell of a site grid; kReducePartners
+// (pair_partners.hip, partners_epilogue): the best candidates of every a row
+// and b column staged for the merge.  The kernel then takes SummaryArgs /
+// HeatmapArgs / PartnersArgs where the row kernels take DenseArgs; o gives it
 // the window only.
-constexpr int kReduceNone = 0, kReduceSummary = 1, kReduceHeatmap = 2;
+constexpr int kReduceNone = 0, kReduceSummary = 1, kReduceHeatmap = 2, kReducePartners = 3;
 __device__ __attribute__((always_inline)) void summary_epilogue(const SummaryArgs &s, const OrderArgs &o,
                                                                 const uint8_t *site_ok, uint32_t L, uint32_t a0,
                                                                 uint32_t b0, uint32_t tid,
@@ -94,6 +96,10 @@ __device__ __attribute__((always_inline)) void heatmap_epilogue(const HeatmapArg
                                                                 const uint8_t *site_ok, uint32_t L, uint32_t a0,
                                                                 uint32_t b0, uint32_t tid,
                                                                 const float (&tot)[4][4][4]);
+__device__ __attribute__((always_inline)) void partners_epilogue(const PartnersArgs &p, const OrderArgs &o,
+                                                                 const uint8_t *site_ok, uint32_t L, uint32_t a0,
+                                                                 uint32_t b0, uint32_t tid, float thr,
+                                                                 const float (&tot)[4][4][4]);
 template <bool DENSE, bool SAFE, bool MF, bool REF, bool LOOP, int REDUCE = kReduceNone>
 __global__ __launch_bounds__(256, MF ? (REF ? WLD_VALU_REF_WG : WLD_VALU_MF_WG) : 2) void pair_valu_kernel(
     const uint8_t *__restrict__ codes, const float *__restrict__ w, const uint8_t *__restrict__ site_ok,
@@ -102,7 +108,8 @@ __global__ __launch_bounds__(256, MF ? (REF ? WLD_VALU_REF_WG : WLD_VALU_MF_WG) 
     uint32_t L, uint32_t NP, uint32_t flush,
     uint32_t ref_cs, uint32_t ref_tail_n, uint32_t n_chunk_rows, float thr, OrderArgs o,
     std::conditional_t<REDUCE == kReduceSummary, SummaryArgs,
-                       std::conditional_t<REDUCE == kReduceHeatmap, HeatmapArgs, DenseArgs>> dn,
+                       std::conditional_t<REDUCE == kReduceHeatmap, HeatmapArgs,
+                                          std::conditional_t<REDUCE == kReducePartners, PartnersArgs, DenseArgs>>> dn,
     ScanArgs sa) {
     static_assert(!REDUCE || (MF && REF && !SAFE && !DENSE && !LOOP), "the reductions run lib.rs's order on f32 MFMA");
     constexpr int NS = 4;  // 16x16 slots per wave: a whole 64x64 tile per workgroup
@@ -411,7 +418,8 @@ __global__ __launch_bounds__(256, MF ? (REF ? WLD_VALU_REF_WG : WLD_VALU_MF_WG) 
             // (bits 0xFFFF: wave w holds a rows 16 w + 4 g + i against b column
             // 16 j + r in tot[i][j], the mapping the reducing epilogues assume)
             if constexpr (REDUCE == kReduceSummary) summary_epilogue(dn, o, site_ok, L, a0, b0, tid, tot);
-            else heatmap_epilogue(dn, o, site_ok, L, a0, b0, tid, tot);
+            else if constexpr (REDUCE == kReduceHeatmap) heatmap_epilogue(dn, o, site_ok, L, a0, b0, tid, tot);
+            else partners_epilogue(dn, o, site_ok, L, a0, b0, tid, thr, tot);
             return;
         }
         // ---- epilogue ------------------------------------------------------
@@ -507,6 +515,13 @@ __global__ __launch_bounds__(256, MF ? (REF ? WLD_VALU_REF_WG : WLD_VALU_MF_WG) 
 
     if constexpr (!LOOP) {
         const uint32_t tile = tiles[blockIdx.x];
+        if constexpr (REDUCE == kReducePartners) {
+            // (the tile addresses the staging's parts: checked like a candidate entry's)
+            if (tile != kNoTile && !tile_in_range(tile, L)) {
+                if (threadIdx.x == 0) atomicOr(dn.guard, kPartnersGuardTile);
+                return;
+            }
+        }
         if (tile != kNoTile)  // kNoTile: padding of an XCD-ordered list
             compute_tile(tile, threadIdx.x, 0xFFFFu, 0xFu);
     } else {
