@@ -888,6 +888,141 @@ int wld_run_partners(wld_ctx *ctx, uint32_t k, float r2_threshold, uint32_t chun
 int wld_partners_merge(wld_partners *into, const wld_partners *from);
 void wld_partners_free(wld_partners *p);
 
+/* ---- LD blocks: maximal runs of consecutive sites without a weak pair (not in
+ * the reference; Haploview's blocks, PLINK's --blocks, the segments behind
+ * tag-SNP selection and region-wise analyses) ----
+ *
+ * Pairs and classes.  A pair a < b of LOADED sites is considered iff it lies in
+ * the linear chunk range [chunk_begin,chunk_end) (end 0 = all, as
+ * wld_run_summary; a pair belongs to chunk (a/256, b/256)) and in the
+ * context's current window (wld_set_window).  Every considered pair is in
+ * exactly one class:
+ *   none        single_weighted_ld_pair gives None;
+ *   nonfinite   Some, but the chosen value is NaN or +-inf;
+ *   informative everything else.
+ * The value is, bit for bit, the f32 the default row path (WLD_OPT_REF_SUMS 1)
+ * puts in the pair's row: r2 (WLD_BLOCKS_R2) or fabsf(d_prime)
+ * (WLD_BLOCKS_ABS_DPRIME).  d_prime is the row path's value, which is the
+ * reference's and not the textbook |D'|: two sites that are copies of each
+ * other have r2 = 1 but |d_prime| near 0.5, so conventions phrased in D' do
+ * not transfer and r2 is the statistic to use by default.  An informative pair
+ * is strong iff value >= strong_min (an f32 compare), else weak.  none and
+ * nonfinite pairs never break a block.  The sums always run in lib.rs's order:
+ * the kernel choice, WLD_OPT_REF_SUMS and the screen options do not apply.
+ *
+ * Breaks (pass 1: wld_run_block_breaks, every in-window tile of the range).
+ * Per loaded site:
+ *   fwd_weak[a]  the smallest b of the weak considered pairs (a, b);
+ *   bwd_weak[b]  the largest a of the weak considered pairs (a, b);
+ *                WLD_BLOCKS_NONE where there is no such pair;
+ *   last[a]      the last in-window partner of a (the window's limit; n_sites
+ *                - 1 without a window), filled for the whole set whatever the
+ *                chunk range;
+ *   pairs, none_pairs, nonfinite_pairs, strong_pairs, weak_pairs
+ *                pairs = none + nonfinite + strong + weak =
+ *                wld_window_pairs_in_chunks(range);
+ *   tiles        the 64x64 tiles launched;
+ *   kernel_ms    HIP-event time of the launch (device group: the slowest
+ *                member's).
+ * wld_block_breaks_merge(into, from) combines breaks over disjoint chunk
+ * ranges into those of the union: fwd_weak by min, bwd_weak by max, totals and
+ * tiles by addition, kernel_ms the larger.  WLD_E_ARG when n_sites, stat,
+ * strong_min (as bits) or last differ.
+ *
+ * Validity of a run [s, e] of consecutive sites (every pair of it must be in
+ * the window: e <= last[s]):
+ *   WLD_BLOCKS_ALL    no pair of the run is weak;
+ *   WLD_BLOCKS_SPINE  (Haploview's solid spine) no pair (s, k) and no pair
+ *                     (k, e) of the run is weak; interior pairs may be.
+ * A single site is always valid.
+ *
+ * Partition.  Start at s = 0; e is the largest index in [s, last[s]] for which
+ * [s, e] is valid; the next s is e + 1.  Runs of at least min_sites (>= 2)
+ * sites are reported as blocks, in site order:
+ *   n_blocks, first[k], last[k]   LOADED indices, inclusive;
+ *   site_block[i]                 the block of site i, or -1.
+ * wld_blocks_partition computes this on the host from a breaks result (no
+ * device needed) and leaves the statistics NULL.
+ *
+ * Block statistics (pass 2: wld_blocks_from_breaks, only the tiles that hold a
+ * pair of a reported block).  Per block, over its considered pairs — all
+ * chunks, the current window:
+ *   pairs, informative, strong   counts (under WLD_BLOCKS_ALL strong ==
+ *                informative when the breaks cover every chunk);
+ *   value_sum    f64 sum of (double) value over the informative pairs;
+ *   value_min    their smallest value, ordered as floats over ALL finite
+ *                values; NaN when informative is 0;
+ *   tiles, kernel_ms   of pass 2.
+ * wld_run_blocks runs both passes over every chunk; the pass-1 totals, tiles
+ * and time are then in break_* (zero from wld_blocks_from_breaks, which takes
+ * them from nowhere).
+ *
+ * No value goes through a floating-point atomic on the way to a boundary: the
+ * counts, value_min, the break arrays and therefore the partition are
+ * identical from run to run, across splits of the chunk range and across
+ * device groups.  value_sum is NOT bitwise reproducible: tiles add to a block
+ * with f64 atomics in whatever order they finish.  Every term is exact
+ * ((double) of an f32), so each sum is within the rounding of an any-order f64
+ * sum of its terms: relative error at most about n 2^-53 for n nonnegative
+ * terms (the heat map's wording and bound).
+ *
+ * On a device group (wld_create_multi) pass 1 is sharded exactly as
+ * wld_run_summary shards it and merged on the host in member order; pass 2
+ * runs on member 0.
+ *
+ * WLD_E_ARG: an unknown stat or rule; a non-finite strong_min; min_sites < 2;
+ * non-finite weights (a load that takes the row path's select loop);
+ * chunk_begin > chunk_end; breaks whose n_sites is not the loaded set's (or
+ * with a NULL array).  WLD_E_STATE: before a load, or while a run is in
+ * flight.  WLD_E_OOM leaves the context usable.  A blocks run changes nothing
+ * a later row run depends on — it keeps its tile lists and accumulators in
+ * buffers of its own — and wld_last_stats and the last run's rows stay as they
+ * were.  No progress callback. */
+#define WLD_BLOCKS_R2 0         /* value = r2 */
+#define WLD_BLOCKS_ABS_DPRIME 1 /* value = fabsf(d_prime) */
+#define WLD_BLOCKS_ALL 0
+#define WLD_BLOCKS_SPINE 1
+#define WLD_BLOCKS_NONE 0xFFFFFFFFu
+typedef struct {
+    uint64_t n_sites;
+    int stat;
+    float strong_min;
+    uint32_t *fwd_weak; /* n_sites; WLD_BLOCKS_NONE: no weak pair (i, b) */
+    uint32_t *bwd_weak; /* n_sites; WLD_BLOCKS_NONE: no weak pair (a, i) */
+    uint32_t *last;     /* n_sites: the last in-window partner */
+    uint64_t pairs, none_pairs, nonfinite_pairs, strong_pairs, weak_pairs;
+    uint64_t tiles;     /* 64x64 tiles launched */
+    double kernel_ms;   /* HIP-event time of the launch (device group: slowest member) */
+} wld_block_breaks;
+typedef struct {
+    uint64_t n_sites;
+    uint32_t n_blocks;
+    int stat, rule;
+    float strong_min;
+    uint32_t min_sites;
+    uint32_t *first, *last; /* n_blocks: LOADED indices, inclusive */
+    int32_t *site_block;    /* n_sites: block id or -1 */
+    /* n_blocks each; all NULL from wld_blocks_partition */
+    uint64_t *pairs, *informative, *strong;
+    double *value_sum;
+    float *value_min;       /* NaN where informative == 0 */
+    uint64_t tiles;         /* pass 2: 64x64 tiles launched */
+    double kernel_ms;       /* pass 2: HIP-event time of the launch */
+    /* pass 1 (wld_run_blocks only) */
+    uint64_t break_pairs, break_none_pairs, break_nonfinite_pairs, break_strong_pairs, break_weak_pairs;
+    uint64_t break_tiles;
+    double break_kernel_ms;
+} wld_blocks;
+int wld_run_block_breaks(wld_ctx *ctx, int stat, float strong_min, uint32_t chunk_begin, uint32_t chunk_end,
+                         wld_block_breaks *out);
+int wld_block_breaks_merge(wld_block_breaks *into, const wld_block_breaks *from);
+void wld_block_breaks_free(wld_block_breaks *b);
+int wld_blocks_partition(const wld_block_breaks *breaks, int rule, uint32_t min_sites, wld_blocks *out);
+int wld_blocks_from_breaks(wld_ctx *ctx, const wld_block_breaks *breaks, int rule, uint32_t min_sites,
+                           wld_blocks *out);
+int wld_run_blocks(wld_ctx *ctx, int stat, float strong_min, int rule, uint32_t min_sites, wld_blocks *out);
+void wld_blocks_free(wld_blocks *b);
+
 #ifdef __cplusplus
 }
 #endif

@@ -111,6 +111,55 @@ class Heatmap(ctypes.Structure):
     ]
 
 
+BLOCKS_R2, BLOCKS_ABS_DPRIME, BLOCKS_ALL, BLOCKS_SPINE, BLOCKS_NONE = 0, 1, 0, 1, 0xFFFFFFFF
+
+
+class BlockBreaksC(ctypes.Structure):
+    _fields_ = [
+        ("n_sites", ctypes.c_uint64),
+        ("stat", ctypes.c_int),
+        ("strong_min", ctypes.c_float),
+        ("fwd_weak", ctypes.POINTER(ctypes.c_uint32)),
+        ("bwd_weak", ctypes.POINTER(ctypes.c_uint32)),
+        ("last", ctypes.POINTER(ctypes.c_uint32)),
+        ("pairs", ctypes.c_uint64),
+        ("none_pairs", ctypes.c_uint64),
+        ("nonfinite_pairs", ctypes.c_uint64),
+        ("strong_pairs", ctypes.c_uint64),
+        ("weak_pairs", ctypes.c_uint64),
+        ("tiles", ctypes.c_uint64),
+        ("kernel_ms", ctypes.c_double),
+    ]
+
+
+class BlocksC(ctypes.Structure):
+    _fields_ = [
+        ("n_sites", ctypes.c_uint64),
+        ("n_blocks", ctypes.c_uint32),
+        ("stat", ctypes.c_int),
+        ("rule", ctypes.c_int),
+        ("strong_min", ctypes.c_float),
+        ("min_sites", ctypes.c_uint32),
+        ("first", ctypes.POINTER(ctypes.c_uint32)),
+        ("last", ctypes.POINTER(ctypes.c_uint32)),
+        ("site_block", ctypes.POINTER(ctypes.c_int32)),
+        ("pairs", ctypes.POINTER(ctypes.c_uint64)),
+        ("informative", ctypes.POINTER(ctypes.c_uint64)),
+        ("strong", ctypes.POINTER(ctypes.c_uint64)),
+        ("value_sum", ctypes.POINTER(ctypes.c_double)),
+        ("value_min", ctypes.POINTER(ctypes.c_float)),
+        ("tiles", ctypes.c_uint64),
+        ("kernel_ms", ctypes.c_double),
+        ("break_pairs", ctypes.c_uint64),
+        ("break_none_pairs", ctypes.c_uint64),
+        ("break_nonfinite_pairs", ctypes.c_uint64),
+        ("break_strong_pairs", ctypes.c_uint64),
+        ("break_weak_pairs", ctypes.c_uint64),
+        ("break_tiles", ctypes.c_uint64),
+        ("break_kernel_ms", ctypes.c_double),
+    ]
+
+
 class Prune(ctypes.Structure):
     _fields_ = [
         ("n_sites", ctypes.c_uint64),
@@ -252,6 +301,15 @@ SIGNATURES = {
                                 ctypes.POINTER(PartnersC)]),
     "wld_partners_merge": (_int, [ctypes.POINTER(PartnersC), ctypes.POINTER(PartnersC)]),
     "wld_partners_free": (None, [ctypes.POINTER(PartnersC)]),
+    "wld_run_block_breaks": (_int, [_vp, _int, ctypes.c_float, ctypes.c_uint32, ctypes.c_uint32,
+                                    ctypes.POINTER(BlockBreaksC)]),
+    "wld_block_breaks_merge": (_int, [ctypes.POINTER(BlockBreaksC), ctypes.POINTER(BlockBreaksC)]),
+    "wld_block_breaks_free": (None, [ctypes.POINTER(BlockBreaksC)]),
+    "wld_blocks_partition": (_int, [ctypes.POINTER(BlockBreaksC), _int, ctypes.c_uint32, ctypes.POINTER(BlocksC)]),
+    "wld_blocks_from_breaks": (_int, [_vp, ctypes.POINTER(BlockBreaksC), _int, ctypes.c_uint32,
+                                      ctypes.POINTER(BlocksC)]),
+    "wld_run_blocks": (_int, [_vp, _int, ctypes.c_float, _int, ctypes.c_uint32, ctypes.POINTER(BlocksC)]),
+    "wld_blocks_free": (None, [ctypes.POINTER(BlocksC)]),
 }
 
 _lib = None

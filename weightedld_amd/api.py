@@ -13,14 +13,15 @@ from collections import namedtuple
 
 import numpy as np
 
-from ._lib import (HEAT_ABS_DPRIME, HEAT_MAX_CELLS, HEAT_R2, KERNEL_AUTO, KERNEL_MFMA, KERNEL_VALU, OPTIONS,
+from ._lib import (BLOCKS_ABS_DPRIME, BLOCKS_ALL, BLOCKS_NONE, BLOCKS_R2, BLOCKS_SPINE, BlockBreaksC, BlocksC,
+                   HEAT_ABS_DPRIME, HEAT_MAX_CELLS, HEAT_R2, KERNEL_AUTO, KERNEL_MFMA, KERNEL_VALU, OPTIONS,
                    PARTNERS_MAX_K, PARTNERS_NONE, PROGRESS_FN, Heatmap, Pairs, PartnersC, Prune, RunStats, Summary,
                    TargetRowsC, WldError, check, lib)
 
 __all__ = [
     "Symbol", "SymbolHistogram", "SiteSet", "LdStats", "PairStore", "read_fasta", "read_vcf",
     "is_site_of_interest", "henikoff_weights", "single_weighted_ld_pair", "all_weighted_ld_pairs",
-    "ld_summary", "LdSummary", "ld_heatmap", "LdHeatmap", "heatmap_cells", "ld_prune", "LdPrune", "maf_priority", "ld_targets", "TargetRows", "ld_partners", "LdPartners", "PARTNERS_MAX_K", "PARTNERS_NONE", "Context", "default_context", "KERNEL_AUTO", "KERNEL_VALU", "KERNEL_MFMA", "OPTIONS", "WldError",
+    "ld_summary", "LdSummary", "ld_heatmap", "LdHeatmap", "heatmap_cells", "ld_prune", "LdPrune", "maf_priority", "ld_targets", "TargetRows", "ld_partners", "LdPartners", "PARTNERS_MAX_K", "PARTNERS_NONE", "ld_blocks", "LdBlocks", "LdBlockBreaks", "BLOCKS_NONE", "Context", "default_context", "KERNEL_AUTO", "KERNEL_VALU", "KERNEL_MFMA", "OPTIONS", "WldError",
 ]
 
 
@@ -319,6 +320,152 @@ class LdPartners:
                           d_prime=keep[3].reshape(L, k), r2=keep[4].reshape(L, k), pairs=int(a.pairs),
                           none_pairs=int(a.none_pairs), passing_pairs=int(a.passing_pairs), tiles=int(a.tiles),
                           kernel_ms=float(a.kernel_ms), merge_ms=float(a.merge_ms))
+
+
+BLOCK_STATS = {"r2": BLOCKS_R2, "dprime": BLOCKS_ABS_DPRIME}
+BLOCK_RULES = {"all": BLOCKS_ALL, "spine": BLOCKS_SPINE}
+
+
+def _block_code(table, what, value):
+    if isinstance(value, str):
+        if value not in table:
+            raise ValueError("%s must be one of %s" % (what, ", ".join("\"%s\"" % k for k in table)))
+        return table[value]
+    return int(value)
+
+
+def _block_name(table, code):
+    return next((k for k, v in table.items() if v == int(code)), int(code))
+
+
+class LdBlockBreaks:
+    """wld_block_breaks as numpy arrays and ints (Context.run_block_breaks):
+    fwd_weak, bwd_weak (uint32, BLOCKS_NONE where a site has no weak pair) and
+    last (uint32) per LOADED site, stat ("r2" or "dprime"), strong_min, the
+    class totals pairs = none_pairs + nonfinite_pairs + strong_pairs +
+    weak_pairs, tiles and kernel_ms."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    @property
+    def n_sites(self):
+        return int(self.fwd_weak.shape[0])
+
+    def _to_c(self):
+        c = BlockBreaksC()
+        keep = [np.ascontiguousarray(a, dtype=np.uint32).copy() for a in (self.fwd_weak, self.bwd_weak, self.last)]
+        c.n_sites, c.stat, c.strong_min = self.n_sites, _block_code(BLOCK_STATS, "stat", self.stat), self.strong_min
+        c.fwd_weak, c.bwd_weak, c.last = (_p(a, ctypes.c_uint32) for a in keep)
+        c.pairs, c.none_pairs, c.nonfinite_pairs = self.pairs, self.none_pairs, self.nonfinite_pairs
+        c.strong_pairs, c.weak_pairs, c.tiles, c.kernel_ms = self.strong_pairs, self.weak_pairs, self.tiles, self.kernel_ms
+        return c, keep
+
+    @staticmethod
+    def _from_c(c, arrays):
+        return LdBlockBreaks(fwd_weak=arrays[0], bwd_weak=arrays[1], last=arrays[2],
+                             stat=_block_name(BLOCK_STATS, c.stat), strong_min=float(c.strong_min),
+                             pairs=int(c.pairs), none_pairs=int(c.none_pairs),
+                             nonfinite_pairs=int(c.nonfinite_pairs), strong_pairs=int(c.strong_pairs),
+                             weak_pairs=int(c.weak_pairs), tiles=int(c.tiles), kernel_ms=float(c.kernel_ms))
+
+    def merge(self, other):
+        """wld_block_breaks_merge: the breaks over the union of this result's
+        and other's (disjoint) chunk ranges, as a new LdBlockBreaks."""
+        a, keep = self._to_c()
+        b, keep_b = other._to_c()
+        check(lib().wld_block_breaks_merge(ctypes.byref(a), ctypes.byref(b)), "wld_block_breaks_merge")
+        return LdBlockBreaks._from_c(a, keep)
+
+    def partition(self, rule="all", min_sites=2):
+        """wld_blocks_partition: the blocks of these breaks, on the host (no
+        device); an LdBlocks without statistics."""
+        a, keep = self._to_c()
+        out = BlocksC()
+        check(lib().wld_blocks_partition(ctypes.byref(a), _block_code(BLOCK_RULES, "rule", rule), int(min_sites),
+                                         ctypes.byref(out)), "wld_blocks_partition")
+        return _take_blocks(out)
+
+
+class LdBlocks:
+    """wld_blocks as numpy arrays and ints (Context.run_blocks,
+    Context.blocks_from_breaks, LdBlockBreaks.partition, ld_blocks): first and
+    last (uint32 LOADED indices, inclusive) per block in site order,
+    site_block (int32 per site: its block or -1), stat, rule, strong_min,
+    min_sites; the per-block statistics pairs, informative, strong (uint64),
+    value_sum (float64) and value_min (float32, NaN without an informative
+    pair) — None after a host-only partition — with pass 2's tiles and
+    kernel_ms and, from run_blocks, pass 1's break_* totals."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    @property
+    def n_sites(self):
+        return int(self.site_block.shape[0])
+
+    @property
+    def n_blocks(self):
+        return int(self.first.shape[0])
+
+    @property
+    def sites(self):
+        """Sites per block."""
+        return (self.last.astype(np.int64) - self.first.astype(np.int64) + 1).astype(np.uint32)
+
+    @property
+    def mean(self):
+        """Per-block mean of the value over the informative pairs (NaN where
+        there is none); None without statistics."""
+        if self.value_sum is None:
+            return None
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(self.informative > 0, self.value_sum / self.informative, np.nan)
+
+    def parents(self, site_map=None):
+        """(first, last) in parent coordinates as uint64: site_map[i] for
+        loaded index i (None: this result's site_map if it has one, else the
+        indices themselves)."""
+        if site_map is None:
+            site_map = getattr(self, "site_map", None)
+        L = self.n_sites
+        sm = np.arange(L, dtype=np.uint64) if site_map is None else np.asarray(site_map, dtype=np.uint64).reshape(-1)
+        if sm.size != L:
+            raise ValueError("site_map has %d entries for %d sites" % (sm.size, L))
+        return sm[self.first.astype(np.int64)], sm[self.last.astype(np.int64)]
+
+    def site_cell(self):
+        """The blocks as a heat map's cells: the int32 site -> cell map
+        Context.run_heatmap accepts (with n_cells = n_blocks), for up to
+        HEAT_MAX_CELLS blocks."""
+        if self.n_blocks > HEAT_MAX_CELLS:
+            raise ValueError("%d blocks; a heat map has at most %d cells per side" % (self.n_blocks, HEAT_MAX_CELLS))
+        return np.ascontiguousarray(self.site_block, dtype=np.int32).copy()
+
+
+def _take_blocks(out):
+    """Library-allocated wld_blocks -> LdBlocks (copies, then frees)."""
+    L, nb = int(out.n_sites), int(out.n_blocks)
+
+    def grab(p, n, dt):
+        return np.ctypeslib.as_array(p, shape=(n,)).astype(dt, copy=True) if n else np.zeros(0, dtype=dt)
+
+    have = bool(out.pairs)
+    res = LdBlocks(first=grab(out.first, nb, np.uint32), last=grab(out.last, nb, np.uint32),
+                   site_block=grab(out.site_block, L, np.int32), stat=_block_name(BLOCK_STATS, out.stat),
+                   rule=_block_name(BLOCK_RULES, out.rule), strong_min=float(out.strong_min),
+                   min_sites=int(out.min_sites),
+                   pairs=grab(out.pairs, nb, np.uint64) if have else None,
+                   informative=grab(out.informative, nb, np.uint64) if have else None,
+                   strong=grab(out.strong, nb, np.uint64) if have else None,
+                   value_sum=grab(out.value_sum, nb, np.float64) if have else None,
+                   value_min=grab(out.value_min, nb, np.float32) if have else None,
+                   tiles=int(out.tiles), kernel_ms=float(out.kernel_ms), break_pairs=int(out.break_pairs),
+                   break_none_pairs=int(out.break_none_pairs), break_nonfinite_pairs=int(out.break_nonfinite_pairs),
+                   break_strong_pairs=int(out.break_strong_pairs), break_weak_pairs=int(out.break_weak_pairs),
+                   break_tiles=int(out.break_tiles), break_kernel_ms=float(out.break_kernel_ms))
+    lib().wld_blocks_free(ctypes.byref(out))
+    return res
 
 
 def heatmap_cells(site_map_or_siteset, n_sites=None, *, sites_per_cell=None, cell_width=None, edges=None,
@@ -733,6 +880,41 @@ class Context:
         lib().wld_partners_free(ctypes.byref(out))
         return res
 
+    def run_block_breaks(self, strong_min, stat="r2", chunk_begin=0, chunk_end=0):
+        """wld_run_block_breaks: pass 1 of the LD blocks over the linear chunk
+        range (end 0 = all) under the context's window, as an LdBlockBreaks.
+        An informative pair is weak iff its value (stat: "r2", or "dprime" for
+        the row path's |d_prime|) is below strong_min."""
+        out = BlockBreaksC()
+        check(lib().wld_run_block_breaks(self._h, _block_code(BLOCK_STATS, "stat", stat), strong_min, chunk_begin,
+                                         chunk_end, ctypes.byref(out)), "wld_run_block_breaks")
+        L = int(out.n_sites)
+        arrays = [np.ctypeslib.as_array(p, shape=(L,)).astype(np.uint32, copy=True) if L
+                  else np.zeros(0, dtype=np.uint32) for p in (out.fwd_weak, out.bwd_weak, out.last)]
+        res = LdBlockBreaks._from_c(out, arrays)
+        lib().wld_block_breaks_free(ctypes.byref(out))
+        return res
+
+    def blocks_from_breaks(self, breaks, rule="all", min_sites=2):
+        """wld_blocks_from_breaks: the partition of an LdBlockBreaks of the
+        loaded set and the statistics of its blocks (pass 2), as an LdBlocks."""
+        a, keep = breaks._to_c()
+        out = BlocksC()
+        check(lib().wld_blocks_from_breaks(self._h, ctypes.byref(a), _block_code(BLOCK_RULES, "rule", rule),
+                                           int(min_sites), ctypes.byref(out)), "wld_blocks_from_breaks")
+        return _take_blocks(out)
+
+    def run_blocks(self, strong_min, stat="r2", rule="all", min_sites=2):
+        """wld_run_blocks: both passes over every chunk under the context's
+        window, as an LdBlocks: maximal runs of consecutive LOADED sites
+        without a weak pair (rule "all") or with a solid spine (rule "spine"),
+        of at least min_sites sites, with their statistics."""
+        out = BlocksC()
+        check(lib().wld_run_blocks(self._h, _block_code(BLOCK_STATS, "stat", stat), strong_min,
+                                   _block_code(BLOCK_RULES, "rule", rule), int(min_sites), ctypes.byref(out)),
+              "wld_run_blocks")
+        return _take_blocks(out)
+
     def run_prune(self, r2_threshold, priority=None):
         """wld_run_prune: the greedy r2-independent set of the loaded sites at
         this threshold under the context's window, as an LdPrune (keep, tag in
@@ -1064,6 +1246,32 @@ def ld_partners(site_set, weights, k, r2_threshold, max_distance=None, max_sites
         sm = site_set.site_map
         ctx.load(site_set.buffer, w, sm)
         res = ctx.run_partners(k, r2_threshold)
+    finally:
+        ctx.set_window(*before)
+    res.site_map = sm
+    return res
+
+
+def ld_blocks(site_set, weights, strong_min, stat="r2", rule="all", min_sites=2, max_distance=None, max_sites=None,
+              ctx=None):
+    """LD blocks (not in the reference; Haploview's blocks, PLINK's --blocks):
+    loads site_set and runs Context.run_blocks(strong_min, stat, rule,
+    min_sites) under the window max_distance / max_sites (the context's own
+    window is restored afterwards).  stat "dprime" is the row path's |d_prime|,
+    not the textbook |D'|: r2 is the default.  Returns an LdBlocks indexed by
+    the set's own site index, with site_map, the set's parent coordinates (None
+    without a map)."""
+    ctx = ctx or default_context()
+    w = np.ascontiguousarray(weights, dtype=np.float32)
+    if w.size != site_set.n_seqs():
+        raise ValueError("weights must have n_seqs entries")
+    before = ctx.window()
+    if max_distance is not None or max_sites is not None:
+        ctx.set_window(max_distance, max_sites)
+    try:
+        sm = site_set.site_map
+        ctx.load(site_set.buffer, w, sm)
+        res = ctx.run_blocks(strong_min, stat, rule, min_sites)
     finally:
         ctx.set_window(*before)
     res.site_map = sm

@@ -26,6 +26,7 @@
 #include "window_plan.hpp"
 #include "summary_plan.hpp"
 #include "heatmap_plan.hpp"
+#include "blocks_plan.hpp"
 #include "partners_plan.hpp"
 #include "prune_plan.hpp"
 #include "targets_plan.hpp"
@@ -242,6 +243,13 @@ struct wld_ctx {
     // guard}; its events are created per call
     DevBuf pt_tiles, pt_stage, pt_cnt, pt_csr, pt_run, pt_words;
 
+    // the LD blocks: pass 1's accumulators {classes[5], fwd[LP], bwd + 1 [LP]},
+    // pass 2's per-block accumulators and its site -> block map with the
+    // per-block id limits, a tile list of their own (either pass), and the
+    // two events around each pass's launch (created at the first call)
+    DevBuf blk_brk, blk_acc, blk_map, blk_tiles;
+    hipEvent_t ev_blk[4] = {};
+
     // wld_run_prune: while it runs, the gathers leave loaded indices in
     // out_a/out_b (no site_map); its four events (created at the first prune:
     // before the CSR build, after it, after the rounds, after the tags) and
@@ -271,7 +279,7 @@ struct wld_ctx {
         // buffers: it completes before they are freed
         if (stream && stream != own_stream) (void)hipStreamSynchronize(stream);
         DevBuf *all[] = {&keep, &htab, &htab_kept, &site_index, &raw, &wraw, &codes, &w_pad, &wstats, &site_ok, &site_map, &planes, &frag, &rcodes, &rw, &w6, &w4, &f6a, &f6b, &f6marg, &i8a, &i8b, &tiles, &cand, &f6_pairs, &fp6_probe_buf,
-                         &seg_cnt, &seg_off, &chunk_total, &chunk_base, &counters, &chunk_left, &prog_n, &win_hi, &win_pairs, &sum_buf, &heat_buf, &heat_tiles, &heat_map, &pt_tiles, &pt_stage, &pt_cnt, &pt_csr, &pt_run, &pt_words, &st_a, &st_b, &st_d,
+                         &seg_cnt, &seg_off, &chunk_total, &chunk_base, &counters, &chunk_left, &prog_n, &win_hi, &win_pairs, &sum_buf, &heat_buf, &heat_tiles, &heat_map, &pt_tiles, &pt_stage, &pt_cnt, &pt_csr, &pt_run, &pt_words, &blk_brk, &blk_acc, &blk_map, &blk_tiles, &st_a, &st_b, &st_d,
                          &st_dp, &st_r2, &out_a, &out_b, &out_d, &out_dp, &out_r2};
         for (DevBuf *b : all) release(*b);
         for (DevBuf *b : tg.all()) release(*b);
@@ -282,6 +290,8 @@ struct wld_ctx {
         for (auto &e : ev_sum)
             if (e) (void)hipEventDestroy(e);
         for (auto &e : ev_heat)
+            if (e) (void)hipEventDestroy(e);
+        for (auto &e : ev_blk)
             if (e) (void)hipEventDestroy(e);
         for (auto &e : ev_pr)
             if (e) (void)hipEventDestroy(e);
@@ -295,8 +305,8 @@ namespace {
 
 // Every single-device entry point starts here; a device group (wld_create_multi)
 // supports only wld_load, wld_run_host, wld_all_weighted_ld_pairs,
-// wld_run_summary, wld_run_heatmap, wld_run_partners and the option/kernel/stats calls, which dispatch to its
-// members.
+// wld_run_summary, wld_run_heatmap, wld_run_partners, the LD-block calls and the option/kernel/stats calls,
+// which dispatch to its members.
 int set_dev(wld_ctx *c) {
     if (!c) return fail(WLD_E_ARG, "null context");
     if (!c->members.empty())
@@ -2742,6 +2752,423 @@ void wld_partners_free(wld_partners *p) {
     free(p->d_prime);
     free(p->r2);
     memset(p, 0, sizeof(*p));
+}
+
+namespace {
+// What the LD-block calls refuse, checked on a loaded single-device context
+// (every member of a group holds the same load).
+int blocks_check_stat(wld_ctx *c, const char *who, int stat, float strong_min) {
+    const int a = blocks_plan::check_stat(stat, strong_min);
+    if (a == blocks_plan::kArgStat) return fail(WLD_E_ARG, "%s: unknown stat %d", who, stat);
+    if (a == blocks_plan::kArgStrongMin) return fail(WLD_E_ARG, "%s: strong_min is not finite", who);
+    if (c && c->safe) return fail(WLD_E_ARG, "%s needs finite weights (this load takes the select loop)", who);
+    return WLD_OK;
+}
+int blocks_check_rule(const char *who, int rule, uint32_t min_sites) {
+    const int a = blocks_plan::check_rule(rule, min_sites);
+    if (a == blocks_plan::kArgRule) return fail(WLD_E_ARG, "%s: unknown rule %d", who, rule);
+    if (a == blocks_plan::kArgMinSites) return fail(WLD_E_ARG, "%s: min_sites %u is below 2", who, min_sites);
+    return WLD_OK;
+}
+
+// the tile list of a blocks pass into the context's own buffer
+int blocks_tiles_upload(wld_ctx *c, std::vector<uint32_t> &t, uint32_t T_used) {
+    if (!c->opt_tile_rows && t.size() >= 4096 && T_used < 65535)
+        t = xcd_order(t, tile_order::super_block_side((uint32_t)c->NP));
+    WLD_TRY(ensure(c->blk_tiles, t.size() * sizeof(uint32_t)));
+    HIP_TRY(hipMemcpyAsync(c->blk_tiles.p, t.data(), t.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    return WLD_OK;
+}
+
+// Pass 1 over the linear chunks [lb, le) on one device (stat, strong_min
+// checked): the range's tile list under the window in a buffer of its own —
+// the row path's cached list, its range and seg_clear are not touched — the
+// break arrays at their neutral values, one launch, one copy back.  Touches
+// no staging, segment count, chunk total, run counter or row-path event.
+int breaks_range(wld_ctx *c, int stat, float strong_min, uint32_t lb, uint32_t le, blocks_plan::Breaks *out) {
+    WLD_TRY(set_dev(c));
+    if (!c->loaded) return fail(WLD_E_STATE, "wld_run_block_breaks before wld_load");
+    if (c->pend.active) return fail(WLD_E_STATE, "wld_run_block_breaks during a run");
+    const size_t L = c->L, LP = c->LP, TB = LP / kTile;
+    const bool windowed = window_on(c);
+    if (windowed && c->win_hi_host.size() != L) return fail(WLD_E_STATE, "internal: the window has no plan");
+    *out = blocks_plan::Breaks{};
+    out->n_sites = (uint32_t)L;
+    out->stat = stat;
+    out->strong_min = strong_min;
+    try {
+        out->fwd.assign(L, blocks_plan::kNone);
+        out->bwd.assign(L, blocks_plan::kNone);
+        out->last.assign(L, L ? (uint32_t)(L - 1) : 0u);
+    } catch (const std::bad_alloc &) {
+        return fail(WLD_E_OOM, "host allocation of the break arrays (%zu sites) failed", L);
+    }
+    if (windowed)
+        for (size_t i = 0; i < L; ++i) out->last[i] = std::min<uint32_t>(c->win_hi_host[i], (uint32_t)(L - 1));
+    if (lb >= le) return WLD_OK;
+    const uint32_t T_used = (uint32_t)((L + kTile - 1) / kTile), n = chunk_rows_of(L);
+    std::vector<uint32_t> t =
+        windowed ? window_plan::range_tiles(n, T_used, lb, le, c->win_hi_host) : tile_order::range_tiles(n, T_used, lb, le);
+    out->tiles = t.size();
+    const uint64_t expect = run_pairs(c, lb, le);
+    if (t.empty()) {
+        if (expect) return fail(WLD_E_HIP, "internal: the break run's tile list is empty; the range holds %llu pairs",
+                                (unsigned long long)expect);
+        return WLD_OK;
+    }
+    WLD_TRY(ensure_ref_layout(c));
+    for (auto &e : c->ev_blk)
+        if (!e) HIP_TRY(hipEventCreate(&e));
+    // {classes[8]} u64 | fwd[LP] u32 (all ones) | bwd + 1 [LP] u32 (zero)
+    const size_t bytes = 8 * 8 + 4 * LP + 4 * LP;
+    WLD_TRY(ensure(c->blk_brk, bytes));
+    WLD_TRY(blocks_tiles_upload(c, t, T_used));
+    unsigned long long *d_cls = ptr<unsigned long long>(c->blk_brk);
+    uint32_t *d_fwd = reinterpret_cast<uint32_t *>(d_cls + 8), *d_bwd1 = d_fwd + LP;
+    HIP_TRY(hipMemsetAsync(c->blk_brk.p, 0, bytes, c->stream));
+    HIP_TRY(hipMemsetAsync(d_fwd, 0xFF, 4 * LP, c->stream));
+    const BlockBreakArgs ba{d_cls, d_fwd, d_bwd1, stat, strong_min};
+    ValuLaunch v = ref_valu_launch(c, 0.0f);  // (finite weights: blocks_check_stat)
+    v.tiles = ptr<uint32_t>(c->blk_tiles);
+    v.n_tiles = (uint32_t)t.size();
+    OrderArgs o{};  // the window only
+    o.L = (uint32_t)L;
+    o.T = (uint32_t)TB;
+    o.win_hi = windowed ? ptr<uint32_t>(c->win_hi) : nullptr;
+    HIP_TRY(hipEventRecord(c->ev_blk[0], c->stream));
+    launch_pair_block_breaks(v, o, ba, c->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c->ev_blk[1], c->stream));
+    uint64_t cls[8] = {};
+    std::vector<uint32_t> bwd1(L);
+    HIP_TRY(hipMemcpyAsync(cls, d_cls, sizeof(cls), hipMemcpyDeviceToHost, c->stream));
+    if (L) {
+        HIP_TRY(hipMemcpyAsync(out->fwd.data(), d_fwd, 4 * L, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(bwd1.data(), d_bwd1, 4 * L, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));  // (t is read by the copy)
+    out->kernel_ms = event_ms(c->ev_blk[0], c->ev_blk[1]);
+    for (size_t i = 0; i < L; ++i) out->bwd[i] = bwd1[i] ? bwd1[i] - 1 : blocks_plan::kNone;
+    out->pairs = cls[0];
+    out->none_pairs = cls[1];
+    out->nonfinite_pairs = cls[2];
+    out->strong_pairs = cls[3];
+    out->weak_pairs = cls[4];
+    // the kernel's own accounting against the host's plan
+    if (out->pairs != expect ||
+        out->pairs != out->none_pairs + out->nonfinite_pairs + out->strong_pairs + out->weak_pairs)
+        return fail(WLD_E_HIP, "internal: break run counted %llu pairs (%llu none, %llu nonfinite, %llu strong, "
+                               "%llu weak); the range holds %llu",
+                    (unsigned long long)out->pairs, (unsigned long long)out->none_pairs,
+                    (unsigned long long)out->nonfinite_pairs, (unsigned long long)out->strong_pairs,
+                    (unsigned long long)out->weak_pairs, (unsigned long long)expect);
+    return WLD_OK;
+}
+
+// ... on a device group: member k takes its shard of the chunk sequence (as
+// summary_group deals them) cut to [lb, le), on its own host thread; the
+// members' breaks are merged in member order.
+int breaks_group(wld_ctx *g, int stat, float strong_min, uint32_t lb, uint32_t le, blocks_plan::Breaks *out) {
+    const int G = (int)g->members.size();
+    wld_ctx *c0 = g->members[0];
+    std::vector<uint32_t> sb(G), se(G);
+    for (int k = 0; k < G; ++k) {  // every range before any thread starts
+        if (window_on(c0)) WLD_TRY(wld_shard_chunks_window(c0, G, k, &sb[k], &se[k]));
+        else WLD_TRY(wld_shard_chunks(c0->L, G, k, &sb[k], &se[k]));
+        sb[k] = std::max(sb[k], lb);
+        se[k] = std::max(sb[k], std::min(se[k], le));
+    }
+    std::vector<blocks_plan::Breaks> part(G);
+    std::vector<int> status(G, WLD_OK);
+    std::vector<std::string> msg(G);
+    std::vector<std::thread> th;
+    for (int k = 0; k < G; ++k)
+        th.emplace_back([&, k] {
+            status[k] = breaks_range(g->members[k], stat, strong_min, sb[k], se[k], &part[k]);
+            if (status[k] != WLD_OK) msg[k] = wld_last_error();
+        });
+    for (auto &t : th) t.join();
+    for (int k = 0; k < G; ++k)
+        if (status[k] != WLD_OK)
+            return fail(status[k], "device %d (shard %d): %s", g->members[k]->device, k, msg[k].c_str());
+    *out = blocks_plan::Breaks{};
+    for (int k = 0; k < G; ++k) blocks_plan::merge(*out, part[k]);
+    return WLD_OK;
+}
+
+int breaks_run(wld_ctx *c, const char *who, int stat, float strong_min, uint32_t chunk_begin, uint32_t chunk_end,
+               blocks_plan::Breaks *b) {
+    if (!c) return fail(WLD_E_ARG, "null context");
+    wld_ctx *c0 = c->members.empty() ? c : c->members[0];
+    for (wld_ctx *m : c->members.empty() ? std::vector<wld_ctx *>{c} : c->members) {
+        if (!m->loaded) return fail(WLD_E_STATE, "%s before wld_load", who);
+        if (m->pend.active) return fail(WLD_E_STATE, "%s during a run", who);
+    }
+    WLD_TRY(blocks_check_stat(c0, who, stat, strong_min));
+    const uint32_t m = chunks_of(c0->L);
+    if (chunk_end == 0 || chunk_end > m) chunk_end = m;
+    if (chunk_begin > chunk_end) return fail(WLD_E_ARG, "chunk range [%u,%u) invalid", chunk_begin, chunk_end);
+    if (c->members.empty()) return breaks_range(c, stat, strong_min, chunk_begin, chunk_end, b);
+    return breaks_group(c, stat, strong_min, chunk_begin, chunk_end, b);
+}
+
+int breaks_store(const blocks_plan::Breaks &b, wld_block_breaks *out) {
+    const size_t L = b.n_sites, n = std::max<size_t>(L, 1) * sizeof(uint32_t);
+    out->fwd_weak = (uint32_t *)malloc(n);
+    out->bwd_weak = (uint32_t *)malloc(n);
+    out->last = (uint32_t *)malloc(n);
+    if (!out->fwd_weak || !out->bwd_weak || !out->last) {
+        wld_block_breaks_free(out);
+        return fail(WLD_E_OOM, "host allocation of the break arrays (%zu sites) failed", L);
+    }
+    std::copy(b.fwd.begin(), b.fwd.end(), out->fwd_weak);
+    std::copy(b.bwd.begin(), b.bwd.end(), out->bwd_weak);
+    std::copy(b.last.begin(), b.last.end(), out->last);
+    out->n_sites = L;
+    out->stat = b.stat;
+    out->strong_min = b.strong_min;
+    out->pairs = b.pairs;
+    out->none_pairs = b.none_pairs;
+    out->nonfinite_pairs = b.nonfinite_pairs;
+    out->strong_pairs = b.strong_pairs;
+    out->weak_pairs = b.weak_pairs;
+    out->tiles = b.tiles;
+    out->kernel_ms = b.kernel_ms;
+    return WLD_OK;
+}
+
+// a breaks result a call can read: arrays present, every index in its place
+int breaks_arrays_check(const char *who, const wld_block_breaks *b) {
+    if (!b) return fail(WLD_E_ARG, "%s: null breaks", who);
+    if (b->n_sites > 0xFFFFFFFEull)
+        return fail(WLD_E_ARG, "%s: breaks of %llu sites", who, (unsigned long long)b->n_sites);
+    if (b->n_sites && (!b->fwd_weak || !b->bwd_weak || !b->last)) return fail(WLD_E_ARG, "%s: null break array", who);
+    for (uint64_t i = 0; i < b->n_sites; ++i) {
+        const uint32_t f = b->fwd_weak[i], w = b->bwd_weak[i], l = b->last[i];
+        if ((f != WLD_BLOCKS_NONE && (f >= b->n_sites || f <= i)) || (w != WLD_BLOCKS_NONE && w >= i) ||
+            l >= b->n_sites || l < i)
+            return fail(WLD_E_ARG, "%s: the break arrays hold an index out of place at site %llu", who,
+                        (unsigned long long)i);
+    }
+    return WLD_OK;
+}
+
+// the partition of a breaks result into out (statistics NULL)
+int blocks_partition_into(const char *who, const wld_block_breaks *b, int rule, uint32_t min_sites,
+                          blocks_plan::Partition *p, wld_blocks *out) {
+    WLD_TRY(breaks_arrays_check(who, b));
+    WLD_TRY(blocks_check_stat(nullptr, who, b->stat, b->strong_min));
+    WLD_TRY(blocks_check_rule(who, rule, min_sites));
+    const uint32_t n = (uint32_t)b->n_sites;
+    try {
+        *p = blocks_plan::partition(b->fwd_weak, b->bwd_weak, b->last, n, rule, min_sites);
+    } catch (const std::bad_alloc &) {
+        return fail(WLD_E_OOM, "%s: host allocation of the partition (%u sites) failed", who, n);
+    }
+    const size_t nb = p->first.size();
+    out->first = (uint32_t *)malloc(std::max<size_t>(nb, 1) * sizeof(uint32_t));
+    out->last = (uint32_t *)malloc(std::max<size_t>(nb, 1) * sizeof(uint32_t));
+    out->site_block = (int32_t *)malloc(std::max<size_t>(n, 1) * sizeof(int32_t));
+    if (!out->first || !out->last || !out->site_block) {
+        wld_blocks_free(out);
+        return fail(WLD_E_OOM, "%s: host allocation of the blocks (%zu blocks, %u sites) failed", who, nb, n);
+    }
+    std::copy(p->first.begin(), p->first.end(), out->first);
+    std::copy(p->last.begin(), p->last.end(), out->last);
+    std::copy(p->site_block.begin(), p->site_block.end(), out->site_block);
+    out->n_sites = n;
+    out->n_blocks = (uint32_t)nb;
+    out->stat = b->stat;
+    out->rule = rule;
+    out->strong_min = b->strong_min;
+    out->min_sites = min_sites;
+    return WLD_OK;
+}
+
+// Pass 2 on one device: the statistics of partition p's blocks under stat /
+// strong_min, over the tiles the blocks touch (a list of its own), zeroed
+// accumulators, one launch, one copy back.  Fills out's statistics.
+int blocks_stats(wld_ctx *c, const blocks_plan::Partition &p, int stat, float strong_min, wld_blocks *out) {
+    WLD_TRY(set_dev(c));
+    const size_t L = c->L, LP = c->LP, TB = LP / kTile, nb = p.first.size();
+    const size_t na = std::max<size_t>(nb, 1);
+    out->pairs = (uint64_t *)calloc(na, sizeof(uint64_t));
+    out->informative = (uint64_t *)calloc(na, sizeof(uint64_t));
+    out->strong = (uint64_t *)calloc(na, sizeof(uint64_t));
+    out->value_sum = (double *)calloc(na, sizeof(double));
+    out->value_min = (float *)calloc(na, sizeof(float));
+    if (!out->pairs || !out->informative || !out->strong || !out->value_sum || !out->value_min)
+        return fail(WLD_E_OOM, "host allocation of the block statistics (%zu blocks) failed", nb);
+    if (!nb) return WLD_OK;
+    const bool windowed = window_on(c);
+    if (windowed && c->win_hi_host.size() != L) return fail(WLD_E_STATE, "internal: the window has no plan");
+    const uint32_t T_used = (uint32_t)((L + kTile - 1) / kTile);
+    std::vector<uint32_t> t = blocks_plan::stats_tiles(p);
+    out->tiles = t.size();
+    const heatmap_plan::Blocks lim = blocks_plan::id_limits(p, (uint32_t)TB);
+    for (size_t b = 0; b < TB; ++b)
+        if (lim.lo[b] <= lim.hi[b] && (uint32_t)(lim.hi[b] - lim.lo[b]) >= blocks_plan::kTableIds)
+            return fail(WLD_E_STATE, "internal: 64-site block %zu holds block ids %d..%d", b, lim.lo[b], lim.hi[b]);
+    WLD_TRY(ensure_ref_layout(c));
+    for (auto &e : c->ev_blk)
+        if (!e) HIP_TRY(hipEventCreate(&e));
+    // {sum[nb]} f64 | {pairs, informative, strong}[nb] u64 | min_key[nb] u32: one memset
+    const size_t bytes = 8 * nb + 3 * 8 * nb + 4 * nb;
+    WLD_TRY(ensure(c->blk_acc, bytes));
+    WLD_TRY(ensure(c->blk_map, (LP + 2 * TB) * sizeof(int32_t)));
+    WLD_TRY(blocks_tiles_upload(c, t, T_used));
+    std::vector<int32_t> map(LP + 2 * TB, -1);  // site_block[LP] (-1 past L), blk_lo[TB], blk_hi[TB]
+    std::copy(p.site_block.begin(), p.site_block.end(), map.begin());
+    std::copy(lim.lo.begin(), lim.lo.end(), map.begin() + LP);
+    std::copy(lim.hi.begin(), lim.hi.end(), map.begin() + LP + TB);
+    HIP_TRY(hipMemcpyAsync(c->blk_map.p, map.data(), map.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(c->blk_acc.p, 0, bytes, c->stream));
+    double *d_sum = ptr<double>(c->blk_acc);
+    unsigned long long *d_pairs = reinterpret_cast<unsigned long long *>(d_sum + nb);
+    uint32_t *d_key = reinterpret_cast<uint32_t *>(d_pairs + 3 * nb);
+    const int32_t *d_map = ptr<int32_t>(c->blk_map);
+    const BlockStatsArgs sa{d_pairs, d_pairs + nb, d_pairs + 2 * nb, d_sum, d_key, d_map, d_map + LP, d_map + LP + TB,
+                            (uint32_t)nb, stat, strong_min};
+    ValuLaunch v = ref_valu_launch(c, 0.0f);
+    v.tiles = ptr<uint32_t>(c->blk_tiles);
+    v.n_tiles = (uint32_t)t.size();
+    OrderArgs o{};  // the window only
+    o.L = (uint32_t)L;
+    o.T = (uint32_t)TB;
+    o.win_hi = windowed ? ptr<uint32_t>(c->win_hi) : nullptr;
+    HIP_TRY(hipEventRecord(c->ev_blk[2], c->stream));
+    launch_pair_block_stats(v, o, sa, c->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c->ev_blk[3], c->stream));
+    std::vector<uint32_t> key(nb);
+    HIP_TRY(hipMemcpyAsync(out->value_sum, d_sum, 8 * nb, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(out->pairs, d_pairs, 8 * nb, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(out->informative, d_pairs + nb, 8 * nb, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(out->strong, d_pairs + 2 * nb, 8 * nb, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(key.data(), d_key, 4 * nb, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));  // (map and t are read by the copies)
+    out->kernel_ms = event_ms(c->ev_blk[2], c->ev_blk[3]);
+    uint64_t counted = 0;
+    for (size_t k = 0; k < nb; ++k) {
+        counted += out->pairs[k];
+        out->value_min[k] = out->informative[k] ? blocks_plan::inv_key_float(key[k]) : std::nanf("");
+    }
+    // the kernel's own accounting against the host's plan, where every pair
+    // of every block is in the current window (breaks of this window: always)
+    bool in_window = true;
+    for (size_t k = 0; k < nb && windowed; ++k) in_window &= p.last[k] <= c->win_hi_host[p.first[k]];
+    const uint64_t expect = blocks_plan::block_pairs(p);
+    if (in_window && counted != expect)
+        return fail(WLD_E_HIP, "internal: block statistics counted %llu pairs; the blocks hold %llu",
+                    (unsigned long long)counted, (unsigned long long)expect);
+    return WLD_OK;
+}
+
+// partition + pass 2 of breaks b on the loaded set (a group: member 0)
+int blocks_from_breaks(wld_ctx *c, const char *who, const wld_block_breaks *b, int rule, uint32_t min_sites,
+                       wld_blocks *out) {
+    if (!c) return fail(WLD_E_ARG, "null context");
+    wld_ctx *c0 = c->members.empty() ? c : c->members[0];
+    for (wld_ctx *m : c->members.empty() ? std::vector<wld_ctx *>{c} : c->members) {
+        if (!m->loaded) return fail(WLD_E_STATE, "%s before wld_load", who);
+        if (m->pend.active) return fail(WLD_E_STATE, "%s during a run", who);
+    }
+    if (!b) return fail(WLD_E_ARG, "%s: null breaks", who);
+    WLD_TRY(blocks_check_stat(c0, who, b->stat, b->strong_min));
+    WLD_TRY(blocks_check_rule(who, rule, min_sites));
+    if (b->n_sites != c0->L)
+        return fail(WLD_E_ARG, "%s: the breaks cover %llu sites, the loaded set has %zu", who,
+                    (unsigned long long)b->n_sites, c0->L);
+    blocks_plan::Partition p;
+    WLD_TRY(blocks_partition_into(who, b, rule, min_sites, &p, out));
+    const int st = blocks_stats(c0, p, b->stat, b->strong_min, out);
+    if (st != WLD_OK) wld_blocks_free(out);
+    return st;
+}
+}  // namespace
+
+int wld_run_block_breaks(wld_ctx *c, int stat, float strong_min, uint32_t chunk_begin, uint32_t chunk_end,
+                         wld_block_breaks *out) {
+    if (!out) return fail(WLD_E_ARG, "null out");
+    memset(out, 0, sizeof(*out));
+    blocks_plan::Breaks b;
+    WLD_TRY(breaks_run(c, "wld_run_block_breaks", stat, strong_min, chunk_begin, chunk_end, &b));
+    return breaks_store(b, out);
+}
+
+int wld_block_breaks_merge(wld_block_breaks *into, const wld_block_breaks *from) {
+    WLD_TRY(breaks_arrays_check("wld_block_breaks_merge", into));
+    WLD_TRY(breaks_arrays_check("wld_block_breaks_merge", from));
+    if (!blocks_plan::mergeable(into->n_sites, into->stat, into->strong_min, into->last, from->n_sites, from->stat,
+                                from->strong_min, from->last))
+        return fail(WLD_E_ARG, "wld_block_breaks_merge: the results differ in n_sites, stat, strong_min or last");
+    blocks_plan::merge_arrays(into->fwd_weak, into->bwd_weak, from->fwd_weak, from->bwd_weak, into->n_sites);
+    into->pairs += from->pairs;
+    into->none_pairs += from->none_pairs;
+    into->nonfinite_pairs += from->nonfinite_pairs;
+    into->strong_pairs += from->strong_pairs;
+    into->weak_pairs += from->weak_pairs;
+    into->tiles += from->tiles;
+    into->kernel_ms = std::max(into->kernel_ms, from->kernel_ms);
+    return WLD_OK;
+}
+
+void wld_block_breaks_free(wld_block_breaks *b) {
+    if (!b) return;
+    free(b->fwd_weak);
+    free(b->bwd_weak);
+    free(b->last);
+    memset(b, 0, sizeof(*b));
+}
+
+int wld_blocks_partition(const wld_block_breaks *breaks, int rule, uint32_t min_sites, wld_blocks *out) {
+    if (!out) return fail(WLD_E_ARG, "null out");
+    memset(out, 0, sizeof(*out));
+    blocks_plan::Partition p;
+    return blocks_partition_into("wld_blocks_partition", breaks, rule, min_sites, &p, out);
+}
+
+int wld_blocks_from_breaks(wld_ctx *c, const wld_block_breaks *breaks, int rule, uint32_t min_sites, wld_blocks *out) {
+    if (!out) return fail(WLD_E_ARG, "null out");
+    memset(out, 0, sizeof(*out));
+    return blocks_from_breaks(c, "wld_blocks_from_breaks", breaks, rule, min_sites, out);
+}
+
+int wld_run_blocks(wld_ctx *c, int stat, float strong_min, int rule, uint32_t min_sites, wld_blocks *out) {
+    if (!out) return fail(WLD_E_ARG, "null out");
+    memset(out, 0, sizeof(*out));
+    WLD_TRY(blocks_check_rule("wld_run_blocks", rule, min_sites));  // (before pass 1 runs)
+    blocks_plan::Breaks b;
+    WLD_TRY(breaks_run(c, "wld_run_blocks", stat, strong_min, 0, 0, &b));
+    wld_block_breaks view{};  // (the plan's vectors, not owned)
+    view.n_sites = b.n_sites;
+    view.stat = b.stat;
+    view.strong_min = b.strong_min;
+    view.fwd_weak = b.fwd.data();
+    view.bwd_weak = b.bwd.data();
+    view.last = b.last.data();
+    WLD_TRY(blocks_from_breaks(c, "wld_run_blocks", &view, rule, min_sites, out));
+    out->break_pairs = b.pairs;
+    out->break_none_pairs = b.none_pairs;
+    out->break_nonfinite_pairs = b.nonfinite_pairs;
+    out->break_strong_pairs = b.strong_pairs;
+    out->break_weak_pairs = b.weak_pairs;
+    out->break_tiles = b.tiles;
+    out->break_kernel_ms = b.kernel_ms;
+    return WLD_OK;
+}
+
+void wld_blocks_free(wld_blocks *b) {
+    if (!b) return;
+    free(b->first);
+    free(b->last);
+    free(b->site_block);
+    free(b->pairs);
+    free(b->informative);
+    free(b->strong);
+    free(b->value_sum);
+    free(b->value_min);
+    memset(b, 0, sizeof(*b));
 }
 
 namespace {

@@ -50,6 +50,15 @@
 //                      ascending, one line per (site, rank), rank from 0
 //                      (wld_run_partners; parent indices as in the pair TSV);
 //                      with it --pair-output may be left out
+//   --blocks-output FILE     LD-block TSV (block, first, last, sites, pairs,
+//   --blocks-r2 T            informative, strong, mean, min): maximal runs of
+//   --blocks-dprime T        consecutive sites of interest without a weak pair
+//   --blocks-rule all|spine  (value < T; exactly one of r2 and the row path's
+//   --blocks-min-sites M     |d'|) under the window, of at least M (default 2)
+//                      sites; rule spine asks only a block's first and last
+//                      site to have no weak pair inside it (wld_run_blocks;
+//                      first/last as --prune-output prints sites); with it
+//                      --pair-output may be left out
 #include <chrono>
 #include <cinttypes>
 #include <cmath>
@@ -249,6 +258,12 @@ struct Opt {
     uint32_t partners_k = 0;
     bool have_partners_k = false, have_partners_r2 = false;
     float partners_r2 = 0.0f;
+    // --blocks-output / --blocks-r2 / --blocks-dprime / --blocks-rule / --blocks-min-sites: wld_run_blocks
+    std::string blocks_output;
+    bool have_blocks_r2 = false, have_blocks_dprime = false, have_blocks_rule = false, have_blocks_min = false;
+    float blocks_min_value = 0.0f;
+    int blocks_rule = WLD_BLOCKS_ALL;
+    uint32_t blocks_min_sites = 2;
 };
 
 void usage(FILE *f) {
@@ -325,7 +340,17 @@ void usage(FILE *f) {
             "                                             --pair-output may then be left out\n"
             "        --partners-k <partners-k>            (addition) partners per site, 1 to 64\n"
             "        --partners-r2 <partners-r2>          (addition) Minimum value of R2 of a partner [default:\n"
-            "                                             --r2-threshold's value]\n");
+            "                                             --r2-threshold's value]\n"
+            "        --blocks-output <blocks-output>      (addition) Filename to write the LD blocks to (block, first,\n"
+            "                                             last, sites, pairs, informative, strong, mean, min): runs\n"
+            "                                             of consecutive sites without a weak pair; needs exactly one\n"
+            "                                             of --blocks-r2 and --blocks-dprime; obeys --max-distance,\n"
+            "                                             --max-sites and --devices; --pair-output may then be left out\n"
+            "        --blocks-r2 <blocks-r2>              (addition) a pair is weak when its R2 is below this\n"
+            "        --blocks-dprime <blocks-dprime>      (addition) a pair is weak when the row's |D'| is below this\n"
+            "        --blocks-rule <blocks-rule>          (addition) all: no weak pair in a block; spine: none with its\n"
+            "                                             first or last site [default: all]\n"
+            "        --blocks-min-sites <blocks-min-sites>  (addition) smallest block reported, at least 2 [default: 2]\n");
 }
 
 [[noreturn]] void arg_error(const char *msg, const char *arg) {
@@ -492,6 +517,27 @@ Opt parse(int argc, char **argv) {
         } else if (a == "--partners-r2") {
             o.partners_r2 = parse_f32(need("--partners-r2").c_str(), "partners-r2");
             o.have_partners_r2 = true;
+        } else if (a == "--blocks-output") {
+            o.blocks_output = need("--blocks-output");
+        } else if (a == "--blocks-r2" || a == "--blocks-dprime") {
+            const bool r2 = a == "--blocks-r2";
+            o.blocks_min_value = parse_f32(need(a.c_str()).c_str(), r2 ? "blocks-r2" : "blocks-dprime");
+            if (!std::isfinite(o.blocks_min_value))
+                arg_error(r2 ? "Invalid value for '--blocks-r2' (a finite number):"
+                             : "Invalid value for '--blocks-dprime' (a finite number):", argv[i]);
+            (r2 ? o.have_blocks_r2 : o.have_blocks_dprime) = true;
+        } else if (a == "--blocks-rule") {
+            const std::string k = need("--blocks-rule");
+            if (k != "all" && k != "spine") arg_error("Invalid value for '--blocks-rule':", k.c_str());
+            o.blocks_rule = k == "spine" ? WLD_BLOCKS_SPINE : WLD_BLOCKS_ALL;
+            o.have_blocks_rule = true;
+        } else if (a == "--blocks-min-sites") {
+            const std::string v = need("--blocks-min-sites");
+            if (v.empty() || v.find_first_not_of("0123456789") != std::string::npos || v.size() > 9 ||
+                strtoull(v.c_str(), nullptr, 10) < 2)
+                arg_error("Invalid value for '--blocks-min-sites' (at least 2):", v.c_str());
+            o.blocks_min_sites = (uint32_t)strtoull(v.c_str(), nullptr, 10);
+            o.have_blocks_min = true;
         } else if (a == "--kernel") {
             std::string k = need("--kernel");
             o.kernel = k == "valu" ? WLD_KERNEL_VALU : k == "mfma" ? WLD_KERNEL_MFMA : WLD_KERNEL_AUTO;
@@ -516,7 +562,18 @@ Opt parse(int argc, char **argv) {
         arg_error("The argument '--partners-k' needs", "--partners-output <partners-output>");
     if (o.partners_output.empty() && o.have_partners_r2)
         arg_error("The argument '--partners-r2' needs", "--partners-output <partners-output>");
-    if (!have_pair && !ld_sel && o.partners_output.empty())
+    if (!o.blocks_output.empty() && !o.have_blocks_r2 && !o.have_blocks_dprime)
+        arg_error("The following required arguments were not provided:",
+                  "--blocks-r2 <blocks-r2> or --blocks-dprime <blocks-dprime>");
+    if (o.have_blocks_r2 && o.have_blocks_dprime)
+        arg_error("The argument '--blocks-r2' cannot be used with", "--blocks-dprime");
+    if (o.blocks_output.empty() && (o.have_blocks_r2 || o.have_blocks_dprime || o.have_blocks_rule || o.have_blocks_min))
+        arg_error(o.have_blocks_r2       ? "The argument '--blocks-r2' needs"
+                  : o.have_blocks_dprime ? "The argument '--blocks-dprime' needs"
+                  : o.have_blocks_rule   ? "The argument '--blocks-rule' needs"
+                                         : "The argument '--blocks-min-sites' needs",
+                  "--blocks-output <blocks-output>");
+    if (!have_pair && !ld_sel && o.partners_output.empty() && o.blocks_output.empty())
         arg_error("The following required arguments were not provided:", "--pair-output <pair-output>");
     if (!o.have_ld_sites_r2) o.ld_sites_r2 = o.r2_threshold;
     if (!o.have_partners_r2) o.partners_r2 = o.r2_threshold;
@@ -977,6 +1034,48 @@ void write_partners(const Opt &opt, wld_ctx *ctx, const std::vector<uint64_t> &p
     wld_partners_free(&r);
 }
 
+// --blocks-output: the LD blocks of the loaded set under the window
+// (wld_run_blocks), one line per block in site order; first and last are
+// parent indices as --prune-output prints sites, mean (rounded to f32) and min
+// formatted as the pair TSV's numbers, nan without an informative pair.
+void write_blocks(const Opt &opt, wld_ctx *ctx, const std::vector<uint64_t> &parent) {
+    if (opt.blocks_output.empty()) return;
+    using clk = std::chrono::steady_clock;
+    const auto sw = clk::now();
+    wld_blocks r;
+    const int st = wld_run_blocks(ctx, opt.have_blocks_dprime ? WLD_BLOCKS_ABS_DPRIME : WLD_BLOCKS_R2,
+                                  opt.blocks_min_value, opt.blocks_rule, opt.blocks_min_sites, &r);
+    if (st != WLD_OK) die(st, "run_blocks");
+    INFO("Found %u LD blocks in %" PRIu64 " sites (%s weak of %s pairs at %s %g) in %s", r.n_blocks, r.n_sites,
+         human((double)r.break_weak_pairs).c_str(), human((double)r.break_pairs).c_str(),
+         opt.have_blocks_dprime ? "|d'|" : "r2", (double)opt.blocks_min_value, fmt_duration(clk::now() - sw).c_str());
+    INFO("Writing output to %s", debug_path(opt.blocks_output).c_str());
+    std::string out = "block\tfirst\tlast\tsites\tpairs\tinformative\tstrong\tmean\tmin\n";
+    char line[256];
+    for (uint32_t k = 0; k < r.n_blocks; ++k) {
+        if (r.first[k] >= parent.size() || r.last[k] >= parent.size()) continue;
+        const uint64_t cols[7] = {k, parent[r.first[k]], parent[r.last[k]], (uint64_t)r.last[k] - r.first[k] + 1,
+                                  r.pairs[k], r.informative[k], r.strong[k]};
+        int m = 0;
+        for (const uint64_t c : cols) {
+            m += fmt_u64(line + m, c);
+            line[m++] = '\t';
+        }
+        m += fmt3(line + m, r.informative[k] ? (float)(r.value_sum[k] / (double)r.informative[k]) : std::nanf(""));
+        line[m++] = '\t';
+        m += fmt3(line + m, r.value_min[k]);
+        line[m++] = '\n';
+        out.append(line, m);
+    }
+    FILE *f = fopen(opt.blocks_output.c_str(), "wb");
+    const bool ok = f && fwrite(out.data(), 1, out.size(), f) == out.size();
+    if ((f && fclose(f) != 0) || !ok) {
+        fprintf(stderr, "Error: cannot write %s\n", opt.blocks_output.c_str());
+        quit(1);
+    }
+    wld_blocks_free(&r);
+}
+
 // (debug level only, so info-level output is the reference's: the LD pass's
 // progress_report calls — progress(0), then one per 256x256 chunk)
 void log_progress(const ProgressBar &pb) {
@@ -1055,6 +1154,7 @@ int run_gpu_prepass(const Opt &opt, wld_siteset *siteset, wld_ctx *ctx) {
     write_heatmap(opt, ctx, heat_cells);
     write_targets(opt, ctx, targets);
     write_partners(opt, ctx, parent);
+    write_blocks(opt, ctx, parent);
     // (a FASTA set has no site_map: a kept site's parent index is its index in the unfiltered set)
     write_prune(opt, ctx, parent, siteset, std::vector<size_t>(parent.begin(), parent.end()));
     return finish(opt, ctx, pairs, dur, total_pairs);
@@ -1174,6 +1274,7 @@ int main(int argc, char **argv) {
     write_heatmap(opt, ctx, heat_cells);
     write_targets(opt, ctx, targets);
     write_partners(opt, ctx, parent);
+    write_blocks(opt, ctx, parent);
     std::vector<size_t> self(L);
     for (size_t i = 0; i < L; ++i) self[i] = i;
     write_prune(opt, ctx, parent, filtered, self);

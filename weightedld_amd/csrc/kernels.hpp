@@ -156,6 +156,39 @@ struct HeatmapArgs {
     int stat;
 };
 
+// Pass 1 of the LD blocks (pair_blocks.hip blocks_break_epilogue;
+// wld_run_block_breaks).  classes = {pairs, none, nonfinite, strong, weak},
+// zero before the launch, one atomic each per tile.  fwd_weak: LP entries,
+// 0xFFFFFFFF before the launch, atomicMin of b over the weak pairs (a, b).
+// bwd_weak1: LP entries, zero before the launch, atomicMax of a + 1 over the
+// weak pairs (a, b) (0: none; the host takes the 1 off).  stat:
+// WLD_BLOCKS_R2 / WLD_BLOCKS_ABS_DPRIME.
+struct BlockBreakArgs {
+    unsigned long long *classes;
+    uint32_t *fwd_weak;
+    uint32_t *bwd_weak1;
+    int stat;
+    float strong_min;
+};
+
+// Pass 2 of the LD blocks (pair_blocks.hip blocks_stats_epilogue;
+// wld_blocks_from_breaks): per reported block, all zero before the launch,
+// the considered pairs whose two sites carry its id (pairs), the informative
+// and the strong ones, the f64 sum of the informative values and the largest
+// blocks_plan::inv_key of them (0: none).  site_block: LP entries, -1 for a
+// site in no block and for padding; blk_lo / blk_hi: per 64-site block the ids
+// of its first and last site with one (lo > hi: none), LP / 64 entries.
+struct BlockStatsArgs {
+    unsigned long long *pairs, *informative, *strong;
+    double *sum;
+    uint32_t *min_key;
+    const int32_t *site_block;
+    const int32_t *blk_lo, *blk_hi;
+    uint32_t n_blocks;
+    int stat;
+    float strong_min;
+};
+
 // The staging of one batch of a best-partner run (pair_partners.hip;
 // wld_run_partners; layout in partners_plan.hpp).  Tile position p of the
 // launch's list (p < n_tiles, the workgroup id) owns the parts (2 p + side) *
@@ -269,6 +302,14 @@ void launch_pair_summary(const ValuLaunch &v, const OrderArgs &o, const SummaryA
 // The same sums over v's list (the heat map's own filtered tile list), every
 // considered pair reduced into its cell of h; o gives the window only.
 void launch_pair_heatmap(const ValuLaunch &v, const OrderArgs &o, const HeatmapArgs &h, hipStream_t st);
+
+// pair_blocks.hip
+// The same sums over v's list: pass 1 (every tile of the range and window)
+// reduces the weak pairs to the per-site break arrays of b; pass 2 (the tiles
+// the reported blocks touch, a list of its own) reduces the pairs inside a
+// block to its statistics.  o gives the window only.
+void launch_pair_block_breaks(const ValuLaunch &v, const OrderArgs &o, const BlockBreakArgs &b, hipStream_t st);
+void launch_pair_block_stats(const ValuLaunch &v, const OrderArgs &o, const BlockStatsArgs &b, hipStream_t st);
 
 // pair_partners.hip
 // The same sums over v's list (one batch of the run's own tile list, v.thr the

@@ -45,10 +45,10 @@
 // the last workgroup runs the run's chunk scan (scan_tail).
 //
 // The kernel template lives in this header so that pair_valu.hip (the row
-// kernels), pair_summary.hip, pair_heatmap.hip and pair_partners.hip (REDUCE:
-// the same operands, sums and ld_epilogue, each tile reduced on chip instead of
-// compacted into rows) instantiate one body: there is no second copy of the
-// sum stages to drift.
+// kernels), pair_summary.hip, pair_heatmap.hip, pair_partners.hip and
+// pair_blocks.hip (REDUCE: the same operands, sums and ld_epilogue, each tile
+// reduced on chip instead of compacted into rows) instantiate one body: there
+// is no second copy of the sum stages to drift.
 #pragma once
 #include <type_traits>
 
@@ -84,10 +84,21 @@ typedef float v4f __attribute__((ext_vector_type(4)));
 // site, per bin and total; kReduceHeatmap (pair_heatmap.hip,
 // heatmap_epilogue): per cell of a site grid; kReducePartners
 // (pair_partners.hip, partners_epilogue): the best candidates of every a row
-// and b column staged for the merge.  The kernel then takes SummaryArgs /
-// HeatmapArgs / PartnersArgs where the row kernels take DenseArgs; o gives it
-// the window only.
+// and b column staged for the merge; kReduceBreaks and kReduceBlockStats
+// (pair_blocks.hip, blocks_break_epilogue / blocks_stats_epilogue): the weak
+// pairs' per-site break arrays, and the statistics of the pairs inside a
+// block.  The kernel then takes SummaryArgs / HeatmapArgs / PartnersArgs /
+// BlockBreakArgs / BlockStatsArgs where the row kernels take DenseArgs; o
+// gives it the window only.
 constexpr int kReduceNone = 0, kReduceSummary = 1, kReduceHeatmap = 2, kReducePartners = 3;
+constexpr int kReduceBreaks = 4, kReduceBlockStats = 5;
+template <int REDUCE>
+struct ReduceArgsOf { using type = DenseArgs; };
+template <> struct ReduceArgsOf<kReduceSummary> { using type = SummaryArgs; };
+template <> struct ReduceArgsOf<kReduceHeatmap> { using type = HeatmapArgs; };
+template <> struct ReduceArgsOf<kReducePartners> { using type = PartnersArgs; };
+template <> struct ReduceArgsOf<kReduceBreaks> { using type = BlockBreakArgs; };
+template <> struct ReduceArgsOf<kReduceBlockStats> { using type = BlockStatsArgs; };
 __device__ __attribute__((always_inline)) void summary_epilogue(const SummaryArgs &s, const OrderArgs &o,
                                                                 const uint8_t *site_ok, uint32_t L, uint32_t a0,
                                                                 uint32_t b0, uint32_t tid,
@@ -100,6 +111,14 @@ __device__ __attribute__((always_inline)) void partners_epilogue(const PartnersA
                                                                  const uint8_t *site_ok, uint32_t L, uint32_t a0,
                                                                  uint32_t b0, uint32_t tid, float thr,
                                                                  const float (&tot)[4][4][4]);
+__device__ __attribute__((always_inline)) void blocks_break_epilogue(const BlockBreakArgs &k, const OrderArgs &o,
+                                                                     const uint8_t *site_ok, uint32_t L, uint32_t a0,
+                                                                     uint32_t b0, uint32_t tid,
+                                                                     const float (&tot)[4][4][4]);
+__device__ __attribute__((always_inline)) void blocks_stats_epilogue(const BlockStatsArgs &k, const OrderArgs &o,
+                                                                     const uint8_t *site_ok, uint32_t L, uint32_t a0,
+                                                                     uint32_t b0, uint32_t tid,
+                                                                     const float (&tot)[4][4][4]);
 template <bool DENSE, bool SAFE, bool MF, bool REF, bool LOOP, int REDUCE = kReduceNone>
 __global__ __launch_bounds__(256, MF ? (REF ? WLD_VALU_REF_WG : WLD_VALU_MF_WG) : 2) void pair_valu_kernel(
     const uint8_t *__restrict__ codes, const float *__restrict__ w, const uint8_t *__restrict__ site_ok,
@@ -107,9 +126,7 @@ __global__ __launch_bounds__(256, MF ? (REF ? WLD_VALU_REF_WG : WLD_VALU_MF_WG) 
     const uint32_t *__restrict__ tile_bits, unsigned *tile_work, const unsigned *tile_buckets, uint32_t bucket_cap,
     uint32_t L, uint32_t NP, uint32_t flush,
     uint32_t ref_cs, uint32_t ref_tail_n, uint32_t n_chunk_rows, float thr, OrderArgs o,
-    std::conditional_t<REDUCE == kReduceSummary, SummaryArgs,
-                       std::conditional_t<REDUCE == kReduceHeatmap, HeatmapArgs,
-                                          std::conditional_t<REDUCE == kReducePartners, PartnersArgs, DenseArgs>>> dn,
+    typename ReduceArgsOf<REDUCE>::type dn,
     ScanArgs sa) {
     static_assert(!REDUCE || (MF && REF && !SAFE && !DENSE && !LOOP), "the reductions run lib.rs's order on f32 MFMA");
     constexpr int NS = 4;  // 16x16 slots per wave: a whole 64x64 tile per workgroup
@@ -419,7 +436,9 @@ __global__ __launch_bounds__(256, MF ? (REF ? WLD_VALU_REF_WG : WLD_VALU_MF_WG) 
             // 16 j + r in tot[i][j], the mapping the reducing epilogues assume)
             if constexpr (REDUCE == kReduceSummary) summary_epilogue(dn, o, site_ok, L, a0, b0, tid, tot);
             else if constexpr (REDUCE == kReduceHeatmap) heatmap_epilogue(dn, o, site_ok, L, a0, b0, tid, tot);
-            else partners_epilogue(dn, o, site_ok, L, a0, b0, tid, thr, tot);
+            else if constexpr (REDUCE == kReducePartners) partners_epilogue(dn, o, site_ok, L, a0, b0, tid, thr, tot);
+            else if constexpr (REDUCE == kReduceBreaks) blocks_break_epilogue(dn, o, site_ok, L, a0, b0, tid, tot);
+            else blocks_stats_epilogue(dn, o, site_ok, L, a0, b0, tid, tot);
             return;
         }
         // ---- epilogue ------------------------------------------------------
