@@ -259,6 +259,19 @@ int wld_set_kernel(wld_ctx *ctx, int kernel);
  *                      WLD_OPT_FP6_A4 chooses.  Every scaled sum is exact: same
  *                      sums, candidates and rows.  Setting it discards the
  *                      built images, as WLD_OPT_FP6_A4.
+ *   WLD_OPT_FP6_THREE  1 (default, auto): where the fp6 screen runs on tile
+ *                      pairs and its sample run (WLD_OPT_SCREEN_FP6 1) found it
+ *                      worthwhile at this threshold or a lower one, the screen
+ *                      forms three of the four masked sums per pair, decides
+ *                      every pair it can from the interval they leave for the
+ *                      fourth (the missing-by-missing sum), and forms the
+ *                      fourth, in a second pass over the entry, only for
+ *                      entries with a pair in doubt (at most an eighth of the
+ *                      sampled entries, else four sums); lists that are not
+ *                      sampled stay on four sums.  2: three sums wherever the
+ *                      tile-pair fp6 screen runs; 0: always four.  A pair the
+ *                      three sums reject is rejected on four: same candidate
+ *                      tiles, sub-blocks and rows.
  *   WLD_OPT_TARGET_BATCH_SLOTS  wld_run_targets: the pair slots (16 x target
  *                      blocks x padded site count, three floats each) of the
  *                      dense staging one batch may use (default 2^26: 768 MiB;
@@ -295,6 +308,7 @@ int wld_set_kernel(wld_ctx *ctx, int kernel);
 #define WLD_OPT_TARGET_BATCH_SLOTS 18
 #define WLD_OPT_FP6_SHARED 19
 #define WLD_OPT_PARTNERS_BATCH_BYTES 20
+#define WLD_OPT_FP6_THREE 21
 int wld_set_option(wld_ctx *ctx, int option, int64_t value);
 int wld_get_option(wld_ctx *ctx, int option, int64_t *value);
 
@@ -532,6 +546,10 @@ typedef struct {
                                 or, where fp6_shared is 1, on a load whose codes would have taken it */
     int fp6_shared;          /* 1: the pass screened on fp6 (screen_fp6 == 1) with one code image for both
                                 operands and no A image (WLD_OPT_FP6_SHARED) */
+    int fp6_three;           /* 1: the pass screened on fp6 (screen_fp6 == 1) with three masked sums per pair
+                                (WLD_OPT_FP6_THREE), the fourth only for the entries counted below */
+    uint64_t fp6_rechecked;  /* fp6_three == 1: the screen's entries (tile pairs or single tiles) that ran the
+                                second pass for the fourth sum; else 0 */
 } wld_run_stats;
 int wld_last_stats(wld_ctx *ctx, wld_run_stats *out);
 /* The fp6 screen's weight codes of the loaded set (tests, diagnostics): the

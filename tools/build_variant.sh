@@ -10,8 +10,8 @@ set -e
 cd "$(dirname "$0")/.."
 name=$1; flags=$2
 src=${SRC:-pair_mfma}
-make -s build/obj/encode.o build/obj/prepass.o build/obj/pair_valu.o build/obj/pair_summary.o build/obj/pair_mfma.o \
-  build/obj/prune.o build/obj/order.o build/obj/pair_targets.o build/obj/capi.o build/obj/host.o
+all="encode prepass pair_valu pair_summary pair_heatmap pair_partners pair_blocks pair_mfma prune order pair_targets capi host"
+make -s $(for o in $all; do echo build/obj/$o.o; done)
 out=build/exp/$name; mkdir -p $out
 slp=-fno-slp-vectorize
 [ "${SLP:-0}" = 1 ] && slp=
@@ -20,7 +20,7 @@ for one in $src; do
     -Iweightedld_amd/csrc $flags -x hip -c ${SRCFILE:-weightedld_amd/csrc/$one.hip} -o $out/$one.o
 done
 objs=""
-for o in encode prepass pair_valu pair_summary pair_mfma prune order pair_targets capi host; do
+for o in $all; do
   if [[ " $src " == *" $o "* ]]; then objs="$objs $out/$o.o"; else objs="$objs build/obj/$o.o"; fi
 done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o $out/libweightedld.so $objs -lpthread

@@ -30,6 +30,8 @@ buf = bench.synth(L, N)
 w = W.henikoff_weights(W.SiteSet.from_buffer(buf))
 ctx = W.Context(0, W.KERNEL_MFMA)
 ctx.set_option("screen_fp6", 2)  # forced: the pass completes on fp6 whatever the candidate count
+for kv in filter(None, os.environ.get("WLD_AB_OPTS", "").split(";")):  # opt=v;opt=v, as tools/ab_builds.py
+    ctx.set_option(kv.split("=", 1)[0], int(kv.split("=", 1)[1]))
 ctx.load(buf, w)
 t0, runs = time.time(), 0
 while time.time() - t0 < secs or runs < 3:
@@ -49,4 +51,5 @@ print(json.dumps({"lib": sys.argv[1], "config": cfg, "runs": runs, "slots": int(
                   "clock_ghz_p90": float(np.percentile(ghz, 90)), "loop_cycles_med": float(np.median(a[:, 0])),
                   "loop_us_med": float(np.median(a[:, 1]) / 100.0), "screen_ms": st["screen_ms"],
                   "pair_kernel_ms": st["pair_kernel_ms"], "candidate_tiles": st["candidate_tiles"],
-                  "tiles": st["tiles"], "screen_fp6": st["screen_fp6"]}))
+                  "tiles": st["tiles"], "screen_fp6": st["screen_fp6"], "fp6_three": st["fp6_three"],
+                  "fp6_rechecked": st["fp6_rechecked"]}))

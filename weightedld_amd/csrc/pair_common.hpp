@@ -285,6 +285,111 @@ __host__ __device__ __forceinline__ void f6s_direct(float &x0, float &y0, float 
     x1 = fmaf(-v, x1, ma2);
     y1 = v * y1;
 }
+// The fp6 screen on three sums (pair_mfma.hip, kThree): the missing-by-missing
+// sum P00 is not formed, and the pair is decided from the other three where
+// that is possible.  P00 enters the direct coding's sums through X0 alone,
+//   X0 = X0lo + 2 P00,  X0lo = X0 restored with aX = aY (P00 = 0: aX = P01),
+// and it is bracketed by the sequences where a is missing split by b's symbol
+// (M_a = P00 + P01 + sum_k w6_k [a missing][b major]) and the same for b:
+//   0 <= P00 <= c = min(M_a - P01, M_b - P10).
+// In the restored sums P01 = m_b - Y0 and 2 P10 = 2 m_a - X1 - Y1, so
+//   cap2 = 2 c = min(2 M_a + (2 Y0 - 2 m_b), 2 M_b + ((X1 + Y1) - 2 m_a))
+// (f6_cap2: operands on the 1/8 grid below 2^19 as everywhere here, exact in
+// any order), and X0 lies in [X0lo, X0hi = X0lo + cap2], both exact.
+// r2_screen_terms_xy2_t is r2_screen_terms_xy2 with X0 known only as that
+// interval.  It is implied-conservative: wherever it skips (t1 <= 0 and mlo >=
+// mloc), r2_screen_terms_xy2 on the true X0, in f32 as written above, skips
+// too, so the kernel that decides on three sums where it can and forms the
+// fourth where it cannot leaves the four-sum kernel's candidate sets and
+// sub-block masks, and the four-sum test's soundness proof is all it needs.
+//   * Marginals.  m1 and m4 do not contain X0; m2 = (X0 - R2) + Y0 - A2 and m3
+//     = (X0 - R2) - Y0 are exact and nondecreasing in X0.  Taken at X0lo they
+//     are <= the true ones, so mlo(t) <= mlo(true): mlo(t) >= mloc implies the
+//     true test's mlo >= mloc.
+//   * Product.  A skip has mlo(t) >= mloc >= 0, so all four marginals at X0lo,
+//     and the true ones above them, are nonnegative.  A rounded f32 product
+//     of nonnegative factors is nondecreasing in each factor (rounding is
+//     monotone), so fl(m1 m2), fl(m3 m4), their rounded product and its
+//     rounded product with thr_c >= 0 at X0lo are each <= the same at the
+//     true X0: Pt <= P.
+//   * Numerator.  q = fl(X1 Y0) is the same f32 number in both tests, and n(X)
+//     = fl(X Y1 - q) (one fmaf: a single rounding of the exact value) is
+//     nondecreasing in X because Y1 = P11 >= 0 and rounding is monotone.  So
+//     the true test's n(X0) lies in [n(X0lo), n(X0hi)] as computed, and
+//     |n(X0)| <= max(|n(X0lo)|, |n(X0hi)|) =: nt with no allowance at all: the
+//     roundings of the two ends bracket the rounding of the true one.
+//   * nub(t) = fl(2 nt + E) >= fl(2 |n(X0)| + E) = nub >= 0 (E >= 0; one fmaf
+//     each, monotone), hence nub(t)^2 - Pt >= nub^2 - P exactly, and t1(t) =
+//     fl(nub(t)^2 - Pt) >= fl(nub^2 - P) = t1.  So t1(t) <= 0 implies t1 <= 0.
+// With cap2 = 0 the two ends coincide and the function is r2_screen_terms_xy2
+// bit for bit.  The a site's other allele (r2_screen_terms_xy2's note) needs
+// nothing more: the fp6 screen passes the minor channel to both tests.  The
+// shared image's counts come through f6s_direct with aX's count = aY's, the
+// other images' sums through f6c_direct with aX = aY: the same X0lo, Y0, X1,
+// Y1, so one function serves the three formats
+// (tests/cpp/f6_three_check.cpp).
+__host__ __device__ __forceinline__ float f6_cap2(float Ma2, float ma2, float Mb2, float mb2, float Y0, float X1,
+                                                  float Y1) {
+    return fminf(Ma2 + fmaf(2.0f, Y0, -mb2), Mb2 + ((X1 + Y1) - ma2));
+}
+__host__ __device__ __forceinline__ float r2_screen_terms_xy2_t(float X0lo, float Y0, float X1, float Y1, float cap2,
+                                                                float R2, float thr_c, float E, float &mlo) {
+    const float X0r = X0lo - R2;
+    const float T2r = X0r + Y0, m3 = X0r - Y0, m4 = fmaf(2.0f, Y0, -R2);
+    const float A2 = X1 + Y1;
+    const float m1 = A2 - R2, m2 = T2r - A2;
+    mlo = fminf(fminf(m1, m2), fminf(m3, m4));
+    const float q = -(X1 * Y0);
+    const float nt = fmaxf(fabsf(fmaf(X0lo, Y1, q)), fabsf(fmaf(X0lo + cap2, Y1, q)));
+    const float nub = fmaf(2.0f, nt, E);
+    return fmaf(nub, nub, -(thr_c * ((m1 * m2) * (m3 * m4))));
+}
+// The same test straight from the three complement-coded sums p = aY = P01, s
+// = bX = 2 P10 + P11, t = bY = P11, with what depends on one site alone formed
+// once per row and per column of a lane's pairs: 30 operations per pair where
+// restoring X0lo, Y0, X1, Y1 and calling r2_screen_terms_xy2_t takes 37 (the
+// kernel's epilogue is bound by exactly these: three waves per SIMD reach it
+// together).  With d = s - t = 2 P10:
+//   m1 = (2 m_a - R2) - d                        m4 = (2 m_b - R2) - 2 p
+//   m2 = ((row - R2 - 2 m_a) + (col + m_b)) + d  m3 = 2 p + ((row - R2) + (col - m_b))
+//   cap2 = min(2 M_a - 2 p, 2 M_b - d)           X0lo = p + (row + col)
+//   X1 = 2 m_a - s, Y0 = m_b - p, Y1 = t.
+// Every operand and intermediate is a multiple of 1/16 of magnitude below
+// 2^20 (the 1/8 grid of f6c_direct's argument, and R2 = 2 R with R a multiple
+// of 1/32 below 2^17: capi.hip fp6_screen_args), at most 24 significant bits,
+// so each value above is exact however it is associated and equals, bit for
+// bit, what r2_screen_terms_xy2_t forms from the restored sums; the rounded
+// operations (the products, q, the two fmaf of the numerator, nub, t1) are
+// the same operations on the same values.  So t1 and mlo are
+// r2_screen_terms_xy2_t's bit for bit (tests/cpp/f6_three_check.cpp compares
+// them on every table), and its implication holds here unchanged.
+struct F6tRow {  // of the a site
+    float rA, rA2, c1, Ma2, ma2, row;
+};
+struct F6tCol {  // of the b site
+    float cB2, cB3, c4, Mb2, mb, col;
+};
+__host__ __device__ __forceinline__ F6tRow f6t_row(float W6, float Ma, float ma, float R2) {
+    const float row = f6c_row_term(W6, Ma), ma2 = 2.0f * ma, rA = row - R2;
+    return F6tRow{rA, rA - ma2, ma2 - R2, 2.0f * Ma, ma2, row};
+}
+__host__ __device__ __forceinline__ F6tCol f6t_col(float Mb, float mb, float R2) {
+    const float col = f6c_col_term(Mb, mb);
+    return F6tCol{col + mb, col - mb, fmaf(2.0f, mb, -R2), 2.0f * Mb, mb, col};
+}
+__host__ __device__ __forceinline__ float r2_screen_terms_f6t(float p, float s, float t, const F6tRow &a,
+                                                              const F6tCol &b, float thr_c, float E, float &mlo) {
+    const float d = s - t;
+    const float m1 = a.c1 - d, m2 = (a.rA2 + b.cB2) + d;
+    const float m3 = fmaf(2.0f, p, a.rA + b.cB3), m4 = fmaf(-2.0f, p, b.c4);
+    mlo = fminf(fminf(m1, m2), fminf(m3, m4));
+    const float cap2 = fminf(fmaf(-2.0f, p, a.Ma2), b.Mb2 - d);
+    const float q = -((a.ma2 - s) * (b.mb - p));
+    const float X0lo = p + (a.row + b.col);
+    const float nt = fmaxf(fabsf(fmaf(X0lo, t, q)), fabsf(fmaf(X0lo + cap2, t, q)));
+    const float nub = fmaf(2.0f, nt, E);
+    return fmaf(nub, nub, -(thr_c * ((m1 * m2) * (m3 * m4))));
+}
 __host__ __device__ __forceinline__ float r2_screen_violation(float T, float A, float B, float AB, float R,
                                                               float thr_c) {
     float E, mloc, t2;
@@ -446,8 +551,12 @@ __device__ inline void chunk_scan_block(const ScanArgs &a) {
             a.host_out[1] = run;
             a.host_out[2] = cand;
             a.host_out[3] = blocks;
+            if (a.rechecked) a.host_out[5] = ld32(a.rechecked);  // ([4]: the guard word)
             __threadfence_system();
         }
+        // (every screen workgroup that counted has finished: the scan runs
+        // in a launch behind the screen's)
+        if (a.rechecked) *a.rechecked = 0;
     }
     __syncthreads();
     unsigned long long base = sw[wv] + v - s;

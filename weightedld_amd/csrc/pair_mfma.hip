@@ -410,6 +410,9 @@ struct ScreenArgs {
     // probe[1] its tiles (no candidate list, counts or progress written)
     unsigned *probe;
     uint32_t probe_stride;
+    // the fp6 tile-pair screen on three sums: the entries that formed the
+    // fourth sum are counted here (a pass) or in probe[2] (the sample run)
+    unsigned *rechecked;
 };
 
 // Reference epilogue of one pair from its exact sums (fixed-point units):
@@ -1213,6 +1216,59 @@ __device__ __forceinline__ void f6c_rebuild(v4f (&acc)[4][2][2], const float2 *s
         }
     }
 }
+// The three-sum epilogue of one wave's 16 rows x 64 columns: is any of its
+// pairs in doubt, that is, not rejected by r2_screen_terms_f6t on the three
+// sums aY, bX, bY (acc[n][0][0], the missing x raw sum, is not read)?  The
+// accumulators are left as summed, for f6c_rebuild after the second pass.  A
+// pair not in doubt is rejected by the four-sum test too (pair_common.hpp
+// r2_screen_terms_xy2_t), so a wave without doubt has no candidate.  kShared:
+// the accumulators are counts, scaled by the load's one weight value (exact,
+// f6s_direct's argument).
+template <bool kShared>
+__device__ __forceinline__ bool f6t_any_doubt(const v4f (&acc)[4][2][2], const F6Epi &ep, const float2 *sA,
+                                              const float2 *sB, float W6, float wv) {
+    F6tCol cb[4];
+#pragma unroll
+    for (int n = 0; n < 4; ++n) {
+        const float2 b = sB[(ep.lane & 15) + 16 * n];
+        cb[n] = f6t_col(b.x, b.y, ep.R2);
+    }
+    auto terms = [&](const F6tRow &ra, int n, int e, float &mlo) {
+        float p = acc[n][0][1][e], s = acc[n][1][0][e], t = acc[n][1][1][e];
+        if constexpr (kShared) p *= 0.5f * wv, s *= wv, t *= wv;
+        return r2_screen_terms_f6t(p, s, t, ra, cb[n], ep.thr_c, ep.E, mlo);
+    };
+    if (ep.okA == ~0ull && ep.okB == ~0ull && ep.ta != ep.tb) {
+        // every pair valid: branch-free, as F6Epi::any
+        int worst = -1;
+        float mlo_all = INFINITY;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float2 a = sA[16 * ep.wq + 4 * (ep.lane >> 4) + e];
+            const F6tRow ra = f6t_row(W6, a.x, a.y, ep.R2);
+#pragma unroll
+            for (int n = 0; n < 4; ++n) {
+                float mlo;
+                worst = max(worst, __float_as_int(terms(ra, n, e, mlo)));
+                mlo_all = fminf(mlo_all, mlo);
+            }
+        }
+        return worst > 0 || !(mlo_all >= ep.mloc);
+    }
+    bool doubt = false;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const float2 a = sA[16 * ep.wq + 4 * (ep.lane >> 4) + e];
+        const F6tRow ra = f6t_row(W6, a.x, a.y, ep.R2);
+#pragma unroll
+        for (int n = 0; n < 4; ++n) {
+            float mlo;
+            const float t1 = terms(ra, n, e, mlo);
+            if (ep.valid_pair(4 * n + e) && (t1 > 0.0f || !(mlo >= ep.mloc))) doubt = true;
+        }
+    }
+    return doubt;
+}
 }  // namespace
 
 // one 64x64 tile per 4-wave workgroup, four per CU (tile lists past 2^15
@@ -1360,7 +1416,22 @@ extern "C" int wld_debug_f6_clock(unsigned long long *out) {
     return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(gF6Clock), sizeof(gF6Clock));
 }
 #endif
-template <int kFmt>
+// kThree: three masked sums per pair in the stage loop (24 MFMAs per stage and
+// wave instead of 32, 96 accumulators instead of 128): the missing x raw
+// products (aX = 2 P00 + P01, of which only P00 is new: aY = P01) are not
+// formed, and each wave tests its pairs on the interval the three sums leave
+// for P00 (f6t_any_doubt; pair_common.hpp r2_screen_terms_xy2_t).  Where no
+// pair of the entry is in doubt both tiles are rejected as the four-sum
+// kernel rejects them.  Else the whole workgroup runs the stage loop again
+// with the 8 missing x raw MFMAs per stage and wave alone, into the 32
+// accumulators the first pass left free, and the four-sum epilogue decides
+// on the completed set: the same sums (every one exact), so the same
+// verdicts, candidate tiles and sub-block masks.  The flag is one LDS word
+// per half, read by every wave after a workgroup barrier that also follows
+// every wave's last LDS read of the first pass: the second pass's first copy
+// is issued behind it, and no wave skips a barrier another reaches.  On C4
+// 5 of 24,649 entries take the second pass.
+template <int kFmt, bool kThree = false>
 __global__ __launch_bounds__(256, 3) void pair_fp6_screen2w_kernel(
     const uint8_t *__restrict__ a6, const uint8_t *__restrict__ b6, const float2 *__restrict__ marg, float W6,
     const uint64_t *__restrict__ ok_bits,
@@ -1372,6 +1443,7 @@ __global__ __launch_bounds__(256, 3) void pair_fp6_screen2w_kernel(
     __shared__ float2 sMarg[3 * kTile];  // {M, m} of the row tile's sites, then each half's column tile's
     __shared__ unsigned long long sMask[2];
     __shared__ uint32_t sBail, sCand[2];
+    __shared__ uint32_t sDoubt[2];  // kThree: some pair of the half's tile is in doubt on three sums
     if (!sc.probe && blockIdx.x == 0 && threadIdx.x == 0) *sc.cand_work = 0u;  // for the launch after it
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const uint32_t half = wave >> 1, rp = wave & 1, ltid = tid & 127;
@@ -1430,6 +1502,8 @@ __global__ __launch_bounds__(256, 3) void pair_fp6_screen2w_kernel(
             }
             sBail = v;
         }
+        if constexpr (kThree)
+            if (tid < 2) sDoubt[tid] = 0u;  // (published by the first stage barrier, set after the loop)
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         const uint64_t okA = ok_bits[ta], okB = ok_bits[tb];
         v4f acc[2][4][2][2];  // [row block 2 rp + j][b block n][channel_a][X, Y]
@@ -1476,9 +1550,10 @@ __global__ __launch_bounds__(256, 3) void pair_fp6_screen2w_kernel(
             for (int n = 0; n < 4; ++n) {
                 v8i &b = bs[n & 1];
                 constexpr int kMinor = 0x22222222;  // fp4 1.0 (minor) nibbles; 2.0 (missing) is 0x4
-                acc[0][n][0][0] = f6_mfma<F::kCbsz>(ai0, b, kFirst ? kZero : acc[0][n][0][0]);
+                // (kThree: the missing x raw sums wait for the second pass)
+                if constexpr (!kThree) acc[0][n][0][0] = f6_mfma<F::kCbsz>(ai0, b, kFirst ? kZero : acc[0][n][0][0]);
                 acc[0][n][1][0] = f6_mfma<F::kCbsz>(am0, b, kFirst ? kZero : acc[0][n][1][0]);
-                acc[1][n][0][0] = f6_mfma<F::kCbsz>(ai1, b, kFirst ? kZero : acc[1][n][0][0]);
+                if constexpr (!kThree) acc[1][n][0][0] = f6_mfma<F::kCbsz>(ai1, b, kFirst ? kZero : acc[1][n][0][0]);
                 acc[1][n][1][0] = f6_mfma<F::kCbsz>(am1, b, kFirst ? kZero : acc[1][n][1][0]);
                 __builtin_amdgcn_sched_barrier(0);
                 b = v8i{b[0] & kMinor, b[1] & kMinor, b[2] & kMinor, b[3] & kMinor, 0, 0, 0, 0};
@@ -1507,6 +1582,59 @@ __global__ __launch_bounds__(256, 3) void pair_fp6_screen2w_kernel(
 #endif
         const F6Epi ep0{ta, tb, 2 * rp, lane, okA, okB, 2.0f * sc.Rf, thr * (1.0f - 0x1p-7f), sc.E, sc.mloc};
         const F6Epi ep1{ta, tb, 2 * rp + 1, lane, okA, okB, 2.0f * sc.Rf, thr * (1.0f - 0x1p-7f), sc.E, sc.mloc};
+        if constexpr (kThree) {
+            const float2 *sB = sMarg + kTile * (1 + half);
+            const bool doubt = !idle && (f6t_any_doubt<F::kShared>(acc[0], ep0, sMarg, sB, W6, wv) ||
+                                         f6t_any_doubt<F::kShared>(acc[1], ep1, sMarg, sB, W6, wv));
+            if (doubt) sDoubt[half] = 1u;  // (benign race: every writer stores 1)
+            // every wave's LDS reads of the first pass lie before this barrier
+            // (the last stage's wait, the marginals just read)
+            __syncthreads();
+#ifdef WLD_EXP_ZERO_IMG  // (every zero-image pair is in doubt: keep the reject path's work)
+            const bool again = (sDoubt[0] | sDoubt[1]) == 0x5EEDu;
+#else
+            const bool again = (sDoubt[0] | sDoubt[1]) != 0;  // (uniform: the whole workgroup)
+#endif
+            if (!again) {  // both tiles rejected on three sums
+                if (sc.probe) {
+                    if (ltid == 0 && !idle) atomicAdd(sc.probe + 1, 1u);
+                } else if (!idle) {
+                    screen_verdict(0u, ta, tb, ltid, n_chunk_rows, o, sc);
+                }
+                return;
+            }
+            if (unsigned *const cnt = sc.probe ? sc.probe + 2 : sc.rechecked; tid == 0 && cnt) atomicAdd(cnt, 1u);
+            // The second pass: every stage again, the missing channel of the
+            // wave's two row blocks against the raw B blocks (8 MFMAs), with
+            // the first pass's copies, buffers and barriers.
+#pragma unroll
+            for (int n = 0; n < 4; ++n) acc[0][n][0][0] = acc[1][n][0][0] = v4f{0.0f, 0.0f, 0.0f, 0.0f};
+            issue(cur, 0, buf);
+            for (uint32_t kb = 0; kb < NK; ++kb) {
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's copies of the stage landed
+                __builtin_amdgcn_s_barrier();                     // ... and every other wave's; the other buffer is free
+                asm volatile("" ::: "memory");
+                if (kb + 1 < NK) issue(cur, kb + 1, buf ^ 1);
+                const uint8_t *g = smem + buf * kF6PStage;
+                v8i ai0, ai1;
+                if constexpr (F::kShared) {
+                    v8i am0, am1;  // (the masked minor channels: not used here)
+                    f6_ld_rows<kFmt>(g + aoff, lane, ai0, am0);
+                    f6_ld_rows<kFmt>(g + aoff + kF6ABytes, lane, ai1, am1);
+                } else {
+                    ai0 = f6_lda<kFmt>(g + aoff, lane);
+                    ai1 = f6_lda<kFmt>(g + aoff + kF6ABytes, lane);
+                }
+#pragma unroll
+                for (int n = 0; n < 4; ++n) {
+                    const v8i b = f6_ldb(g + boff + n * kF6BBytes, lane);
+                    acc[0][n][0][0] = f6_mfma<F::kCbsz>(ai0, b, acc[0][n][0][0]);
+                    acc[1][n][0][0] = f6_mfma<F::kCbsz>(ai1, b, acc[1][n][0][0]);
+                }
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // reads of this buffer done before the next barrier
+                buf ^= 1;
+            }
+        }
         if (!idle) {
             f6c_rebuild<F::kShared>(acc[0], sMarg, sMarg + kTile * (1 + half), 2 * rp, lane, W6, wv);
             f6c_rebuild<F::kShared>(acc[1], sMarg, sMarg + kTile * (1 + half), 2 * rp + 1, lane, W6, wv);
@@ -1879,7 +2007,13 @@ void fp6_screen_args(const MfmaLaunch &m, ScreenArgs &sc) {
 template <int kFmt>
 void launch_fp6_screen_fmt(const MfmaLaunch &m, const uint64_t *ok_bits, const OrderArgs &o, const ScreenArgs &sc,
                            uint32_t stride, hipStream_t s) {
-    if (m.f6_pairs) {
+    if (m.f6_pairs && m.fp6_three) {
+        // (three sums per pair, the fourth where an entry needs it)
+        hipLaunchKernelGGL((pair_fp6_screen2w_kernel<kFmt, true>), dim3((m.f6_n_pairs + stride - 1) / stride),
+                           dim3(256), 0, s, m.fp6->a6, m.fp6->b6, reinterpret_cast<const float2 *>(m.fp6->marg),
+                           m.fp6->W6, ok_bits, m.f6_pairs, m.f6_n_pairs, m.fp6->NK, m.L, m.n_chunk_rows, m.thr, o, sc,
+                           m.fp6->wv);
+    } else if (m.f6_pairs) {
         // (a tile group per workgroup, the XCD-ordered group list)
         hipLaunchKernelGGL(pair_fp6_screen2w_kernel<kFmt>, dim3((m.f6_n_pairs + stride - 1) / stride), dim3(256), 0, s,
                            m.fp6->a6, m.fp6->b6, reinterpret_cast<const float2 *>(m.fp6->marg), m.fp6->W6, ok_bits,
@@ -1911,7 +2045,7 @@ void launch_fp6_probe(const MfmaLaunch &m, unsigned *probe, uint32_t stride, hip
     fp6_screen_args(m, sc);
     sc.probe = probe;
     sc.probe_stride = std::max<uint32_t>(stride, 1);
-    (void)hipMemsetAsync(probe, 0, 2 * sizeof(unsigned), s);
+    (void)hipMemsetAsync(probe, 0, 3 * sizeof(unsigned), s);
     launch_fp6_screen(m, ok_bits, OrderArgs{}, sc, sc.probe_stride, s);
 }
 
@@ -2023,6 +2157,7 @@ void launch_pair_mfma(const MfmaLaunch &m, const OrderArgs &o, const DenseArgs *
             begin_screen();
             fp6_screen_args(m, sc);
             sc.bail = m.fp6_bail;
+            sc.rechecked = m.f6_rechecked;
             launch_fp6_screen(m, ok_bits, o, sc, 1, s);
             break;
         case Route::I8PairScreen:

@@ -56,6 +56,13 @@ constexpr uint64_t kCandidatePairsKeep = 10;
 // Tile lists shorter than this take the fp6 pass itself as the test (it gives
 // up past a sixteenth); longer ones are sampled first.
 constexpr uint32_t kSampleMinTiles = 2048;
+// The tile-pair fp6 screen on three masked sums per pair runs the stage loop
+// a second time (a quarter of the MFMAs again, with every copy and barrier)
+// for an entry with a pair the three sums leave in doubt.  By MFMA count it
+// breaks even with the four-sum kernel near 0.45 of the entries; auto takes
+// it only where the sample run found the second pass on at most an eighth of
+// its entries: a cap well inside the break-even, not a tuned value.
+constexpr uint64_t kFp6ThreeKeep = 8;
 
 // What the auto policy has learned on this load, window and option set.
 struct Learned {
@@ -72,6 +79,11 @@ struct Learned {
     // the smallest threshold at which the fp6 screen's sample run found few
     // enough candidate tiles (there and above no sample run is needed)
     float fp6_good = INFINITY;
+    // the smallest threshold at which the sample run found the three-sum
+    // screen's second pass on at most an eighth of its entries (there and
+    // above the screen runs on three sums: a higher threshold leaves fewer
+    // pairs in doubt)
+    float fp6_three_good = INFINITY;
 
     void reset() { *this = Learned{}; }
 };
@@ -80,6 +92,9 @@ struct Options {
     int screen;  // WLD_OPT_SCREEN: 0 never, 1 auto, 2 always, 3 two-plane, 4 exact candidate pairs
     int fp6;     // WLD_OPT_SCREEN_FP6: 0 off, 1 auto, 2 whenever it applies, 3 auto without the sample run
     bool ref_sums, prefilter, i8_pairs;
+    // WLD_OPT_FP6_THREE: 0 four sums, 1 auto (where a sample run allowed it),
+    // 2 three sums wherever the tile-pair fp6 screen runs
+    int fp6_three = 1;
 };
 struct LoadFacts {
     bool mfma;            // the load runs on the integer kernel (WLD_KERNEL_MFMA)
@@ -107,7 +122,19 @@ struct Plan {
     uint32_t fp6_bail = 0;
     // I8PairScreen: the pass needs the pre-multiplied images (settle_i8)
     bool i8_images = false;
+    // Fp6Screen on the tile-pair list: three masked sums per pair, the fourth
+    // only for entries with a pair in doubt (the same candidates either way)
+    bool fp6_three = false;
 };
+
+// Whether a tile-pair fp6 screen at thr runs on three sums.  Auto needs a
+// sample run's word for this threshold or a lower one: lists that are never
+// sampled (fewer than kSampleMinTiles tiles, WLD_OPT_SCREEN_FP6 2 or 3) stay
+// on four sums.  (NaN thresholds compare false: four sums.)
+static inline bool fp6_three(const Options &o, const PassFacts &p, const Learned &s) {
+    if (!p.have_pairs) return false;
+    return o.fp6_three == 2 || (o.fp6_three == 1 && p.thr >= s.fp6_three_good);
+}
 
 static inline Plan decide(const Options &o, const LoadFacts &l, const PassFacts &p, const Learned &s) {
     Plan plan;
@@ -141,6 +168,7 @@ static inline Plan decide(const Options &o, const LoadFacts &l, const PassFacts 
         const bool fp6_auto = o.fp6 == 1 || o.fp6 == 3;
         if (l.fp6_ok && (o.fp6 == 2 || (fp6_auto && l.fp6_better && thr > s.fp6_bad))) {
             plan.route = Route::Fp6Screen;
+            plan.fp6_three = fp6_three(o, p, s);
             // auto: past a sixteenth of the tiles as candidates the fp6 screen
             // gives the pass up and the pass is re-run on the i8 screen (not
             // with per-chunk progress, which a re-run does not report again,
@@ -196,15 +224,24 @@ static inline bool wants_sample(Options o, const LoadFacts &l, PassFacts p, cons
 
 // The sample run's verdict: of `sampled` tiles, `candidates` hold a pair the
 // fp6 bound cannot reject.
+// three: the sample ran on three sums (the tile-pair list, WLD_OPT_FP6_THREE
+// not 0) and `rechecked` of its entries took the second pass.  An entry holds
+// at most two tiles, so (sampled + 1) / 2 is a lower bound of the sampled
+// entries: the eighth is taken of that.
 struct Sample {
     float thr;
     uint64_t candidates, sampled;
+    bool three = false;
+    uint64_t rechecked = 0;
 };
 static inline void learn(Learned &s, const Sample &r) {
-    if (r.candidates * kFp6Keep > r.sampled)
+    if (r.candidates * kFp6Keep > r.sampled) {
         s.fp6_bad = std::max(s.fp6_bad, r.thr);
-    else
-        s.fp6_good = std::min(s.fp6_good, r.thr);
+        return;
+    }
+    s.fp6_good = std::min(s.fp6_good, r.thr);
+    if (r.three && r.sampled && r.rechecked * kFp6ThreeKeep <= (r.sampled + 1) / 2)
+        s.fp6_three_good = std::min(s.fp6_three_good, r.thr);
 }
 
 // A completed pass.
@@ -248,6 +285,8 @@ static inline int stat_screened(Route r) {
 }
 // wld_run_stats.screen_fp6 of a pass that was not given up
 static inline int stat_screen_fp6(Route r) { return r == Route::Fp6Screen ? 1 : 0; }
+// wld_run_stats.fp6_three of a pass that was not given up
+static inline int stat_fp6_three(const Plan &p) { return p.route == Route::Fp6Screen && p.fp6_three ? 1 : 0; }
 // wld_run_stats.pair_kernel_launches of a pass with tiles (exact candidate
 // pairs: the i8 pass, ref_sums_kernel, ref_compact_kernel)
 static inline int stat_launches(Route r) { return r == Route::CandidatePairs ? 3 : ran_screen(r) ? 2 : 1; }
