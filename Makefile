@@ -14,12 +14,12 @@ PKG := weightedld_amd
 CSRC := $(PKG)/csrc
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -fno-slp-vectorize -Wall -Iinclude -I$(CSRC)
 HIP_SRCS := $(CSRC)/encode.hip $(CSRC)/prepass.hip $(CSRC)/pair_valu.hip $(CSRC)/pair_summary.hip \
-            $(CSRC)/pair_heatmap.hip $(CSRC)/pair_partners.hip $(CSRC)/pair_blocks.hip $(CSRC)/pair_mfma.hip $(CSRC)/prune.hip $(CSRC)/order.hip $(CSRC)/pair_targets.hip $(CSRC)/capi.hip
+            $(CSRC)/pair_heatmap.hip $(CSRC)/pair_annot.hip $(CSRC)/pair_partners.hip $(CSRC)/pair_blocks.hip $(CSRC)/pair_mfma.hip $(CSRC)/prune.hip $(CSRC)/order.hip $(CSRC)/pair_targets.hip $(CSRC)/capi.hip
 CXX_SRCS := $(CSRC)/host.cpp
 HDRS := include/weightedld.h $(CSRC)/common.hpp $(CSRC)/kernels.hpp $(CSRC)/pair_common.hpp $(CSRC)/tile_order.hpp \
         $(CSRC)/window_plan.hpp $(CSRC)/pair_valu_kernel.hpp $(CSRC)/summary_plan.hpp $(CSRC)/prune_plan.hpp \
         $(CSRC)/screen_policy.hpp $(CSRC)/fp6_scale.hpp $(CSRC)/fp6_pack.hpp $(CSRC)/targets_plan.hpp \
-        $(CSRC)/heatmap_plan.hpp $(CSRC)/partners_plan.hpp $(CSRC)/blocks_plan.hpp
+        $(CSRC)/heatmap_plan.hpp $(CSRC)/partners_plan.hpp $(CSRC)/blocks_plan.hpp $(CSRC)/annot_plan.hpp
 OBJDIR := build/obj
 OBJS := $(patsubst $(CSRC)/%.hip,$(OBJDIR)/%.o,$(HIP_SRCS)) $(patsubst $(CSRC)/%.cpp,$(OBJDIR)/%.o,$(CXX_SRCS))
 
@@ -36,7 +36,7 @@ $(OBJDIR)/%.o: $(CSRC)/%.cpp $(HDRS)
 $(PKG)/libweightedld.so: $(OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -o $@ $(OBJS) -lpthread
 
-$(PKG)/bin/weighted_ld: $(CSRC)/cli.cpp $(CSRC)/tsv_format.hpp $(PKG)/libweightedld.so include/weightedld.h
+$(PKG)/bin/weighted_ld: $(CSRC)/cli.cpp $(CSRC)/tsv_format.hpp $(CSRC)/annot_plan.hpp $(PKG)/libweightedld.so include/weightedld.h
 	@mkdir -p $(PKG)/bin
 	g++ -O2 -std=c++17 -Wall -Iinclude -I$(CSRC) -o $@ $(CSRC)/cli.cpp -L$(PKG) -lweightedld -Wl,-rpath,'$$ORIGIN/..' -lpthread
 
@@ -58,7 +58,7 @@ $(SANDIR)/host.o: $(CSRC)/host.cpp $(HDRS)
 $(SANDIR)/libweightedld.so: $(DEV_OBJS) $(SANDIR)/host.o
 	g++ -shared $(SAN) -o $@ $^ -L/opt/rocm/lib -lamdhip64 -lpthread -Wl,-rpath,/opt/rocm/lib
 
-$(SANDIR)/weighted_ld: $(CSRC)/cli.cpp $(CSRC)/tsv_format.hpp $(SANDIR)/libweightedld.so include/weightedld.h
+$(SANDIR)/weighted_ld: $(CSRC)/cli.cpp $(CSRC)/tsv_format.hpp $(CSRC)/annot_plan.hpp $(SANDIR)/libweightedld.so include/weightedld.h
 	g++ $(SAN) -std=c++17 -Wall -Iinclude -I$(CSRC) -o $@ $< -L$(SANDIR) -lweightedld -Wl,-rpath,'$$ORIGIN' -lpthread
 
 sanitize: $(SANDIR)/libweightedld.so $(SANDIR)/weighted_ld oracle

@@ -710,6 +710,88 @@ int wld_run_heatmap(wld_ctx *ctx, const int32_t *site_cell, uint32_t n_cells, in
                     uint32_t chunk_end, wld_heatmap *out);
 void wld_heatmap_free(wld_heatmap *h);
 
+/* ---- Partitioned LD scores: sum of r2 times site annotations, reduced on the
+ * device (not in the reference; what stratified LD-score regression,
+ * partitioned heritability and annotation-aware PRS need: LDSC's --l2 --annot) ----
+ *
+ * wld_run_annot_scores computes, for every loaded site i and every column c of
+ * a caller-given annotation matrix,
+ *     score[i][c] = sum over the counted pairs {i, k} of r2(i, k) annot[k][c].
+ * annot is a host array of n_sites x n_annot floats, row-major
+ * [site * n_annot + c], indexed by LOADED site index (wld_loaded_sites): binary
+ * or continuous, any sign, all finite; 1 <= n_annot <= WLD_ANNOT_MAX.  It goes
+ * to the device once per call.  No row is produced, staged or copied.
+ *
+ * The considered pairs and their classes are exactly wld_run_summary's: every
+ * pair a < b of the linear chunk range [chunk_begin,chunk_end) (end 0 = all)
+ * that is in the context's current window (wld_set_window) is none, nonfinite
+ * or counted.  r2 is the f32 value the default row path (WLD_OPT_REF_SUMS 1)
+ * puts in the pair's row, bit for bit.  WLD_OPT_REF_SUMS, the kernel choice and
+ * the screen options do not apply, and no threshold applies.  pairs, the three
+ * class counts and partners[] equal wld_run_summary's for the same range and
+ * window, exactly.
+ *
+ * Outputs (library-allocated; release with wld_annot_scores_free), indexed by
+ * LOADED site index:
+ *   pairs, none_pairs, nonfinite_pairs, counted_pairs   as wld_summary's;
+ *   score      n_sites x n_annot, row-major [site * n_annot + c].  A counted
+ *              pair (a, b) adds (double) r2 * (double) annot[b][c] to
+ *              score[a][c] and (double) r2 * (double) annot[a][c] to
+ *              score[b][c];
+ *   partners[i] the counted pairs that contain site i (the self term is not
+ *              one);
+ *   tiles      the 64x64 tiles launched;
+ *   kernel_ms  HIP-event time of the launch (device group: the slowest
+ *              member's).
+ * With WLD_ANNOT_SELF in flags (LDSC counts r2(i, i) = 1) site i additionally
+ * gets the term (double) annot[i][c], iff the site has a major and a minor
+ * symbol (the sites whose pairs are not all none) and its diagonal chunk
+ * (i/256, i/256) lies in the chunk range — so results over disjoint ranges
+ * still combine without counting it twice.
+ *
+ * All counts are exact.  Every term is exact (the product of two 24-bit
+ * significands fits in 53 bits).  The sums are any-order f64 sums — products
+ * accumulated per tile, tiles added with f64 atomics in whatever order they
+ * finish — and NOT bitwise reproducible from run to run.  Each is a chain of
+ * f64 roundings over its terms: for annotations of any sign
+ *     |score[i][c] - exact| <= n 2^-52 sum |term|,
+ * n the site's term count (partners[i], + 1 with the self term) and the sum
+ * over the absolute values of its terms.
+ *
+ * wld_annot_scores_merge adds `from` into `into`: counts, scores, partners and
+ * tiles by addition, kernel_ms the larger.  Results over disjoint chunk ranges
+ * merge to the whole run's (counts exactly, scores to the bound above).
+ * WLD_E_ARG when n_sites, n_annot or flags differ.
+ *
+ * On a device group (wld_create_multi) the range is sharded exactly as
+ * wld_run_summary shards it, the members run concurrently and their results
+ * are merged on the host in member order.
+ *
+ * WLD_E_ARG: n_annot == 0 or > WLD_ANNOT_MAX; annot NULL; a non-finite
+ * annotation value (the message names the first offending site and column);
+ * unknown flag bits; chunk_begin > chunk_end; non-finite weights (a load that
+ * takes the row path's select loop).  WLD_E_STATE: before a load, or while a
+ * run is in flight.  WLD_E_OOM leaves the context usable.  The call keeps its
+ * tile list, image and accumulators in buffers of its own: it changes nothing
+ * a later row run depends on, and wld_last_stats and the last run's rows stay
+ * as they were.  No progress callback. */
+#define WLD_ANNOT_MAX 128
+#define WLD_ANNOT_SELF 1 /* flags: every site with both symbols also counts r2(i, i) = 1 */
+typedef struct {
+    uint64_t n_sites;
+    uint32_t n_annot;
+    int flags;
+    uint64_t pairs, none_pairs, nonfinite_pairs, counted_pairs;
+    double *score;      /* n_sites*n_annot, row-major [site*n_annot + c], LOADED site index */
+    uint32_t *partners; /* n_sites */
+    uint64_t tiles;     /* 64x64 tiles launched */
+    double kernel_ms;   /* HIP-event time of the launch (device group: slowest member) */
+} wld_annot_scores;
+int wld_run_annot_scores(wld_ctx *ctx, const float *annot /* n_sites*n_annot, row-major, host */, uint32_t n_annot,
+                         int flags, uint32_t chunk_begin, uint32_t chunk_end, wld_annot_scores *out);
+int wld_annot_scores_merge(wld_annot_scores *into, const wld_annot_scores *from);
+void wld_annot_scores_free(wld_annot_scores *s);
+
 /* ---- LD pruning: a greedy r2-independent site set with tags (not in the
  * reference; PLINK's --indep-pairwise, bcftools +prune) ----
  *

@@ -113,6 +113,25 @@ class Heatmap(ctypes.Structure):
     ]
 
 
+ANNOT_MAX, ANNOT_SELF = 128, 1
+
+
+class AnnotScoresC(ctypes.Structure):
+    _fields_ = [
+        ("n_sites", ctypes.c_uint64),
+        ("n_annot", ctypes.c_uint32),
+        ("flags", ctypes.c_int),
+        ("pairs", ctypes.c_uint64),
+        ("none_pairs", ctypes.c_uint64),
+        ("nonfinite_pairs", ctypes.c_uint64),
+        ("counted_pairs", ctypes.c_uint64),
+        ("score", ctypes.POINTER(ctypes.c_double)),
+        ("partners", ctypes.POINTER(ctypes.c_uint32)),
+        ("tiles", ctypes.c_uint64),
+        ("kernel_ms", ctypes.c_double),
+    ]
+
+
 BLOCKS_R2, BLOCKS_ABS_DPRIME, BLOCKS_ALL, BLOCKS_SPINE, BLOCKS_NONE = 0, 1, 0, 1, 0xFFFFFFFF
 
 
@@ -292,6 +311,10 @@ SIGNATURES = {
     "wld_run_heatmap": (_int, [_vp, ctypes.POINTER(ctypes.c_int32), ctypes.c_uint32, _int, ctypes.c_uint32,
                                ctypes.c_uint32, ctypes.POINTER(Heatmap)]),
     "wld_heatmap_free": (None, [ctypes.POINTER(Heatmap)]),
+    "wld_run_annot_scores": (_int, [_vp, ctypes.POINTER(ctypes.c_float), ctypes.c_uint32, _int, ctypes.c_uint32,
+                                    ctypes.c_uint32, ctypes.POINTER(AnnotScoresC)]),
+    "wld_annot_scores_merge": (_int, [ctypes.POINTER(AnnotScoresC), ctypes.POINTER(AnnotScoresC)]),
+    "wld_annot_scores_free": (None, [ctypes.POINTER(AnnotScoresC)]),
     "wld_run_prune": (_int, [_vp, ctypes.c_float, _f32p, ctypes.POINTER(Prune)]),
     "wld_prune_free": (None, [ctypes.POINTER(Prune)]),
     "wld_loaded_sites": (_sz, [_vp]),

@@ -13,7 +13,7 @@ from collections import namedtuple
 
 import numpy as np
 
-from ._lib import (BLOCKS_ABS_DPRIME, BLOCKS_ALL, BLOCKS_NONE, BLOCKS_R2, BLOCKS_SPINE, BlockBreaksC, BlocksC,
+from ._lib import (ANNOT_MAX, ANNOT_SELF, AnnotScoresC, BLOCKS_ABS_DPRIME, BLOCKS_ALL, BLOCKS_NONE, BLOCKS_R2, BLOCKS_SPINE, BlockBreaksC, BlocksC,
                    HEAT_ABS_DPRIME, HEAT_MAX_CELLS, HEAT_R2, KERNEL_AUTO, KERNEL_MFMA, KERNEL_VALU, OPTIONS,
                    PARTNERS_MAX_K, PARTNERS_NONE, PROGRESS_FN, Heatmap, Pairs, PartnersC, Prune, RunStats, Summary,
                    TargetRowsC, WldError, check, lib)
@@ -21,7 +21,7 @@ from ._lib import (BLOCKS_ABS_DPRIME, BLOCKS_ALL, BLOCKS_NONE, BLOCKS_R2, BLOCKS
 __all__ = [
     "Symbol", "SymbolHistogram", "SiteSet", "LdStats", "PairStore", "read_fasta", "read_vcf",
     "is_site_of_interest", "henikoff_weights", "single_weighted_ld_pair", "all_weighted_ld_pairs",
-    "ld_summary", "LdSummary", "ld_heatmap", "LdHeatmap", "heatmap_cells", "ld_prune", "LdPrune", "maf_priority", "ld_targets", "TargetRows", "ld_partners", "LdPartners", "PARTNERS_MAX_K", "PARTNERS_NONE", "ld_blocks", "LdBlocks", "LdBlockBreaks", "BLOCKS_NONE", "Context", "default_context", "KERNEL_AUTO", "KERNEL_VALU", "KERNEL_MFMA", "OPTIONS", "WldError",
+    "ld_summary", "LdSummary", "ld_heatmap", "LdHeatmap", "heatmap_cells", "ld_annot_scores", "LdAnnotScores", "annot_matrix", "ANNOT_MAX", "ld_prune", "LdPrune", "maf_priority", "ld_targets", "TargetRows", "ld_partners", "LdPartners", "PARTNERS_MAX_K", "PARTNERS_NONE", "ld_blocks", "LdBlocks", "LdBlockBreaks", "BLOCKS_NONE", "Context", "default_context", "KERNEL_AUTO", "KERNEL_VALU", "KERNEL_MFMA", "OPTIONS", "WldError",
 ]
 
 
@@ -250,6 +250,71 @@ class LdHeatmap:
 
 
 HEAT_STATS = {"r2": HEAT_R2, "dprime": HEAT_ABS_DPRIME}
+
+
+class LdAnnotScores:
+    """wld_annot_scores as numpy arrays and ints (Context.run_annot_scores,
+    ld_annot_scores): score, the [n_sites, n_annot] float64 partitioned LD
+    scores (row i: sum over site i's counted pairs of r2 times the partner's
+    annotation row, plus the site's own row with self_term), partners (uint32,
+    [n_sites], the counted pairs of each site), the class counts (pairs =
+    none_pairs + nonfinite_pairs + counted_pairs), self_term, tiles and
+    kernel_ms.  From ld_annot_scores also names, where given."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    @property
+    def n_sites(self):
+        return int(self.score.shape[0])
+
+    @property
+    def n_annot(self):
+        return int(self.score.shape[1])
+
+    def merge(self, other):
+        """Adds other — the result of a disjoint chunk range of the same load,
+        annotations and self_term — into this one (wld_annot_scores_merge:
+        counts, scores, partners and tiles add, kernel_ms is the larger);
+        returns self.  ValueError when the shapes or self_term differ."""
+        if self.score.shape != other.score.shape or bool(self.self_term) != bool(other.self_term):
+            raise ValueError("results of different shapes or self_term do not merge")
+        for f in ("pairs", "none_pairs", "nonfinite_pairs", "counted_pairs", "tiles"):
+            setattr(self, f, getattr(self, f) + getattr(other, f))
+        self.score = self.score + other.score
+        self.partners = self.partners + other.partners
+        self.kernel_ms = max(self.kernel_ms, other.kernel_ms)
+        return self
+
+
+def annot_matrix(annot, n_sites=None):
+    """The annotation matrix of Context.run_annot_scores as a C-contiguous
+    float32 [n_sites, n_annot] array, checked before any device call: two
+    dimensions, 1 to ANNOT_MAX columns, n_sites rows where given, every value
+    finite.  float32 input is taken as it is; bool, integer and float64 input
+    only where every value is a float32 (no silent rounding: TypeError
+    otherwise, as for every other dtype).  Shape and value errors raise
+    ValueError."""
+    a = np.asarray(annot)
+    if a.ndim != 2:
+        raise ValueError("annot must be a [n_sites, n_annot] matrix, not %d-dimensional" % a.ndim)
+    if a.shape[1] < 1 or a.shape[1] > ANNOT_MAX:
+        raise ValueError("annot has %d columns; 1 to %d are supported" % (a.shape[1], ANNOT_MAX))
+    if n_sites is not None and a.shape[0] != int(n_sites):
+        raise ValueError("annot has %d rows for %d sites" % (a.shape[0], int(n_sites)))
+    if a.dtype != np.float32:
+        if a.dtype.kind not in "biuf":
+            raise TypeError("annot must be float32 (or exactly convertible numbers), not %s" % a.dtype)
+        with np.errstate(over="ignore", invalid="ignore"):
+            f = a.astype(np.float32)
+        same = (f.astype(a.dtype) == a) | ((a != a) & (f != f)) if a.dtype.kind == "f" else f.astype(np.float64) == a
+        if not bool(np.all(same)):
+            raise TypeError("annot of dtype %s does not convert to float32 exactly; pass float32" % a.dtype)
+        a = f
+    bad = np.argwhere(~np.isfinite(a))
+    if bad.size:
+        raise ValueError("annot[%d, %d] = %r is not finite" % (bad[0][0], bad[0][1], float(a[bad[0][0], bad[0][1]])))
+    return np.ascontiguousarray(a)
 
 
 class LdPartners:
@@ -854,6 +919,32 @@ class Context:
         lib().wld_heatmap_free(ctypes.byref(out))
         return res
 
+    def run_annot_scores(self, annot, self_term=False, chunk_begin=0, chunk_end=0):
+        """wld_run_annot_scores: the partitioned LD scores of every LOADED
+        site — score[i, c] = sum over site i's counted in-window pairs {i, k}
+        of the linear chunk range (end 0 = all) of r2(i, k) annot[k, c] —
+        reduced on the device to an LdAnnotScores; no rows.  annot: a float32
+        [n_sites, n_annot] matrix (annot_matrix checks it before any device
+        call).  self_term: every site with a major and a minor symbol also
+        counts r2(i, i) = 1, as LDSC does."""
+        n = int(lib().wld_loaded_sites(self._h))
+        a = annot_matrix(annot, n if n else None)  # (not loaded: the library refuses the call)
+        flags = ANNOT_SELF if self_term else 0
+        out = AnnotScoresC()
+        check(lib().wld_run_annot_scores(self._h, _p(a, ctypes.c_float), int(a.shape[1]), flags, chunk_begin,
+                                         chunk_end, ctypes.byref(out)), "wld_run_annot_scores")
+        L, C = int(out.n_sites), int(out.n_annot)
+        res = LdAnnotScores(
+            score=(np.ctypeslib.as_array(out.score, shape=(L, C)).astype(np.float64, copy=True) if L
+                   else np.zeros((0, C), dtype=np.float64)),
+            partners=(np.ctypeslib.as_array(out.partners, shape=(L,)).astype(np.uint32, copy=True) if L
+                      else np.zeros(0, dtype=np.uint32)),
+            pairs=int(out.pairs), none_pairs=int(out.none_pairs), nonfinite_pairs=int(out.nonfinite_pairs),
+            counted_pairs=int(out.counted_pairs), self_term=bool(int(out.flags) & ANNOT_SELF), tiles=int(out.tiles),
+            kernel_ms=float(out.kernel_ms))
+        lib().wld_annot_scores_free(ctypes.byref(out))
+        return res
+
     def run_partners(self, k, r2_threshold, chunk_begin=0, chunk_end=0):
         """wld_run_partners: for every LOADED site its best k partners (r2 >
         r2_threshold, r2 descending then partner ascending) among the pairs of
@@ -1157,6 +1248,35 @@ def ld_heatmap(site_set, weights, stat="r2", sites_per_cell=None, cell_width=Non
         ctx.set_window(*before)
     res.cell_start = cell_start
     res.site_cell = site_cell
+    return res
+
+
+def ld_annot_scores(site_set, weights, annot, self_term=False, names=None, max_distance=None, max_sites=None,
+                    ctx=None):
+    """Partitioned LD scores of site_set (not in the reference; LDSC's --l2
+    --annot): checks annot (annot_matrix: a float32 [n_sites, n_annot] matrix
+    indexed by the set's own site index) before any device call, loads the set
+    and runs Context.run_annot_scores under the window max_distance /
+    max_sites (the context's own window is restored afterwards).  names:
+    optional column names, kept on the result.  Returns an LdAnnotScores."""
+    a = annot_matrix(annot, site_set.n_sites())
+    if names is not None:
+        names = [str(x) for x in names]
+        if len(names) != a.shape[1]:
+            raise ValueError("%d names for %d annotation columns" % (len(names), a.shape[1]))
+    w = np.ascontiguousarray(weights, dtype=np.float32)
+    if w.size != site_set.n_seqs():
+        raise ValueError("weights must have n_seqs entries")
+    ctx = ctx or default_context()
+    before = ctx.window()
+    if max_distance is not None or max_sites is not None:
+        ctx.set_window(max_distance, max_sites)
+    try:
+        ctx.load(site_set.buffer, w, site_set.site_map)
+        res = ctx.run_annot_scores(a, self_term)
+    finally:
+        ctx.set_window(*before)
+    res.names = names
     return res
 
 

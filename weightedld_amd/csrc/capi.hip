@@ -26,6 +26,7 @@
 #include "window_plan.hpp"
 #include "summary_plan.hpp"
 #include "heatmap_plan.hpp"
+#include "annot_plan.hpp"
 #include "blocks_plan.hpp"
 #include "partners_plan.hpp"
 #include "prune_plan.hpp"
@@ -239,6 +240,13 @@ struct wld_ctx {
     DevBuf heat_buf, heat_tiles, heat_map;
     hipEvent_t ev_heat[2] = {};
 
+    // wld_run_annot_scores: its accumulators {score[LP][CP], counts[4],
+    // partners[LP]} (zeroed per call), its own tile list, the call's
+    // annotation image with the zero-chunk mask, and the two events around its
+    // launch
+    DevBuf an_buf, an_tiles, an_img;
+    hipEvent_t ev_an[2] = {};
+
     // wld_run_partners: its own tile list, a batch's staging (entries and
     // counts), the batch's CSR, the running lists and the words {classes[3],
     // guard}; its events are created per call
@@ -280,7 +288,7 @@ struct wld_ctx {
         // buffers: it completes before they are freed
         if (stream && stream != own_stream) (void)hipStreamSynchronize(stream);
         DevBuf *all[] = {&keep, &htab, &htab_kept, &site_index, &raw, &wraw, &codes, &w_pad, &wstats, &site_ok, &site_map, &planes, &frag, &rcodes, &rw, &w6, &w4, &f6a, &f6b, &f6marg, &i8a, &i8b, &tiles, &cand, &f6_pairs, &fp6_probe_buf,
-                         &seg_cnt, &seg_off, &chunk_total, &chunk_base, &counters, &chunk_left, &prog_n, &win_hi, &win_pairs, &sum_buf, &heat_buf, &heat_tiles, &heat_map, &pt_tiles, &pt_stage, &pt_cnt, &pt_csr, &pt_run, &pt_words, &blk_brk, &blk_acc, &blk_map, &blk_tiles, &st_a, &st_b, &st_d,
+                         &seg_cnt, &seg_off, &chunk_total, &chunk_base, &counters, &chunk_left, &prog_n, &win_hi, &win_pairs, &sum_buf, &heat_buf, &heat_tiles, &heat_map, &an_buf, &an_tiles, &an_img, &pt_tiles, &pt_stage, &pt_cnt, &pt_csr, &pt_run, &pt_words, &blk_brk, &blk_acc, &blk_map, &blk_tiles, &st_a, &st_b, &st_d,
                          &st_dp, &st_r2, &out_a, &out_b, &out_d, &out_dp, &out_r2};
         for (DevBuf *b : all) release(*b);
         for (DevBuf *b : tg.all()) release(*b);
@@ -291,6 +299,8 @@ struct wld_ctx {
         for (auto &e : ev_sum)
             if (e) (void)hipEventDestroy(e);
         for (auto &e : ev_heat)
+            if (e) (void)hipEventDestroy(e);
+        for (auto &e : ev_an)
             if (e) (void)hipEventDestroy(e);
         for (auto &e : ev_blk)
             if (e) (void)hipEventDestroy(e);
@@ -306,7 +316,7 @@ namespace {
 
 // Every single-device entry point starts here; a device group (wld_create_multi)
 // supports only wld_load, wld_run_host, wld_all_weighted_ld_pairs,
-// wld_run_summary, wld_run_heatmap, wld_run_partners, the LD-block calls and the option/kernel/stats calls,
+// wld_run_summary, wld_run_heatmap, wld_run_annot_scores, wld_run_partners, the LD-block calls and the option/kernel/stats calls,
 // which dispatch to its members.
 int set_dev(wld_ctx *c) {
     if (!c) return fail(WLD_E_ARG, "null context");
@@ -2472,6 +2482,231 @@ void wld_heatmap_free(wld_heatmap *h) {
     free(h->sum);
     free(h->max);
     memset(h, 0, sizeof(*h));
+}
+
+namespace {
+// What wld_run_annot_scores refuses, checked on a loaded single-device context
+// (every member of a group holds the same load).
+int annot_check(wld_ctx *c, const float *annot, uint32_t n_annot, int flags) {
+    if (n_annot == 0) return fail(WLD_E_ARG, "wld_run_annot_scores: n_annot 0");
+    if (n_annot > WLD_ANNOT_MAX)
+        return fail(WLD_E_ARG, "wld_run_annot_scores: n_annot %u exceeds %u", n_annot, (unsigned)WLD_ANNOT_MAX);
+    if (flags & ~WLD_ANNOT_SELF) return fail(WLD_E_ARG, "wld_run_annot_scores: unknown flags 0x%x", (unsigned)flags);
+    if (!annot) return fail(WLD_E_ARG, "wld_run_annot_scores: null annot");
+    if (c->safe)
+        return fail(WLD_E_ARG, "wld_run_annot_scores needs finite weights (this load takes the select loop)");
+    const annot_plan::Check k = annot_plan::validate(annot, c->L, n_annot);
+    if (!k.ok)
+        return fail(WLD_E_ARG, "wld_run_annot_scores: annot[site %llu][column %u] = %g is not finite",
+                    (unsigned long long)k.site, k.column, (double)annot[k.site * n_annot + k.column]);
+    return WLD_OK;
+}
+
+// The partitioned scores of the linear chunks [lb, le) on one device (annot
+// checked; im: its padded image): the range's tile list under the window in a
+// buffer of its own — the row path's cached list, its range and seg_clear are
+// not touched — zeroed accumulators, one launch, one copy back, then the self
+// terms on the host.  Touches no staging, segment count, chunk total, run
+// counter or row-path event.
+int annot_range(wld_ctx *c, const float *annot, const annot_plan::Image &im, uint32_t n_annot, int flags, uint32_t lb,
+                uint32_t le, annot_plan::Scores *out) {
+    WLD_TRY(set_dev(c));
+    if (!c->loaded) return fail(WLD_E_STATE, "wld_run_annot_scores before wld_load");
+    if (c->pend.active) return fail(WLD_E_STATE, "wld_run_annot_scores during a run");
+    const size_t L = c->L, LP = c->LP, CP = im.CP, TB = LP / kTile;
+    *out = annot_plan::Scores{};
+    out->n_sites = L;
+    out->n_annot = n_annot;
+    out->flags = flags;
+    std::vector<double> h_score;
+    std::vector<uint8_t> h_ok;
+    try {
+        out->score.assign(L * n_annot, 0.0);
+        out->partners.assign(L, 0);
+        h_score.resize(LP * CP);
+        h_ok.resize(LP);
+    } catch (const std::bad_alloc &) {
+        return fail(WLD_E_OOM, "host allocation of the scores (%zu sites x %u columns) failed", L, n_annot);
+    }
+    if (lb >= le) return WLD_OK;
+    if (im.values.size() != LP * CP || im.zero.size() != TB * (CP / 16))
+        return fail(WLD_E_STATE, "internal: the annotation image does not fit the load");
+    const bool windowed = window_on(c);
+    if (windowed && c->win_hi_host.size() != L) return fail(WLD_E_STATE, "internal: the window has no plan");
+    const uint32_t T_used = (uint32_t)((L + kTile - 1) / kTile), n = chunk_rows_of(L);
+    std::vector<uint32_t> t =
+        windowed ? window_plan::range_tiles(n, T_used, lb, le, c->win_hi_host) : tile_order::range_tiles(n, T_used, lb, le);
+    out->tiles = t.size();
+    const uint64_t expect = run_pairs(c, lb, le);
+    if (t.empty() && expect)
+        return fail(WLD_E_HIP, "internal: the tile list is empty; the range holds %llu pairs", (unsigned long long)expect);
+    if (!t.empty()) {
+        if (!c->opt_tile_rows && t.size() >= 4096 && T_used < 65535)
+            t = xcd_order(t, tile_order::super_block_side((uint32_t)c->NP));
+        WLD_TRY(ensure_ref_layout(c));
+        for (auto &e : c->ev_an)
+            if (!e) HIP_TRY(hipEventCreate(&e));
+        // {score[LP][CP]} f64 | counts[4] u64 | partners[LP] u32: one memset
+        const size_t bytes = 8 * LP * CP + 8 * 4 + 4 * LP, img_bytes = 4 * LP * CP;
+        WLD_TRY(ensure(c->an_buf, bytes));
+        WLD_TRY(ensure(c->an_tiles, t.size() * sizeof(uint32_t)));
+        WLD_TRY(ensure(c->an_img, img_bytes + im.zero.size()));
+        float *d_img = ptr<float>(c->an_img);
+        uint8_t *d_zero = ptr<uint8_t>(c->an_img) + img_bytes;
+        HIP_TRY(hipMemcpyAsync(d_img, im.values.data(), img_bytes, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_zero, im.zero.data(), im.zero.size(), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->an_tiles.p, t.data(), t.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemsetAsync(c->an_buf.p, 0, bytes, c->stream));
+        double *d_score = ptr<double>(c->an_buf);
+        unsigned long long *d_cnt = reinterpret_cast<unsigned long long *>(d_score + LP * CP);
+        uint32_t *d_part = reinterpret_cast<uint32_t *>(d_cnt + 4);
+        const AnnotArgs aa{d_cnt, d_score, d_part, d_img, d_zero, (uint32_t)CP};
+        ValuLaunch v = ref_valu_launch(c, 0.0f);  // (finite weights: annot_check)
+        v.tiles = ptr<uint32_t>(c->an_tiles);
+        v.n_tiles = (uint32_t)t.size();
+        OrderArgs o{};  // the window only
+        o.L = (uint32_t)L;
+        o.T = (uint32_t)TB;
+        o.win_hi = windowed ? ptr<uint32_t>(c->win_hi) : nullptr;
+        HIP_TRY(hipEventRecord(c->ev_an[0], c->stream));
+        launch_pair_annot(v, o, aa, c->stream);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(c->ev_an[1], c->stream));
+        uint64_t cls[4] = {0, 0, 0, 0};
+        HIP_TRY(hipMemcpyAsync(h_score.data(), d_score, 8 * LP * CP, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(cls, d_cnt, sizeof(cls), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(out->partners.data(), d_part, 4 * L, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));  // (t and the image are read by the copies)
+        out->kernel_ms = event_ms(c->ev_an[0], c->ev_an[1]);
+        out->pairs = cls[0];
+        out->none_pairs = cls[1];
+        out->nonfinite_pairs = cls[2];
+        out->counted_pairs = cls[3];
+        for (size_t i = 0; i < L; ++i)
+            std::copy(h_score.begin() + i * CP, h_score.begin() + i * CP + n_annot, out->score.begin() + i * n_annot);
+        // the kernel's own accounting against the host's plan
+        if (out->pairs != expect || out->pairs != out->none_pairs + out->nonfinite_pairs + out->counted_pairs)
+            return fail(WLD_E_HIP, "internal: annot scores counted %llu pairs (%llu none, %llu nonfinite, %llu counted); "
+                                   "the range holds %llu",
+                        (unsigned long long)out->pairs, (unsigned long long)out->none_pairs,
+                        (unsigned long long)out->nonfinite_pairs, (unsigned long long)out->counted_pairs,
+                        (unsigned long long)expect);
+    }
+    if (flags & WLD_ANNOT_SELF) {
+        // r2(i, i) = 1 for the sites with a major and a minor symbol whose
+        // diagonal chunk the range holds: one more exact term each
+        HIP_TRY(hipMemcpyAsync(h_ok.data(), c->site_ok.p, L, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        for (size_t i = 0; i < L; ++i)
+            if (h_ok[i] && annot_plan::self_in_range(L, i, lb, le))
+                for (uint32_t k = 0; k < n_annot; ++k) out->score[i * n_annot + k] += (double)annot[i * n_annot + k];
+    }
+    return WLD_OK;
+}
+
+// ... on a device group: member k takes its shard of the chunk sequence (as
+// summary_group deals them) cut to [lb, le), on its own host thread; the
+// members' results are added in member order.
+int annot_group(wld_ctx *g, const float *annot, const annot_plan::Image &im, uint32_t n_annot, int flags, uint32_t lb,
+                uint32_t le, annot_plan::Scores *out) {
+    const int G = (int)g->members.size();
+    wld_ctx *c0 = g->members[0];
+    std::vector<uint32_t> sb(G), se(G);
+    for (int k = 0; k < G; ++k) {  // every range before any thread starts
+        if (window_on(c0)) WLD_TRY(wld_shard_chunks_window(c0, G, k, &sb[k], &se[k]));
+        else WLD_TRY(wld_shard_chunks(c0->L, G, k, &sb[k], &se[k]));
+        sb[k] = std::max(sb[k], lb);
+        se[k] = std::max(sb[k], std::min(se[k], le));
+    }
+    std::vector<annot_plan::Scores> part(G);
+    std::vector<int> status(G, WLD_OK);
+    std::vector<std::string> msg(G);
+    std::vector<std::thread> th;
+    for (int k = 0; k < G; ++k)
+        th.emplace_back([&, k] {
+            status[k] = annot_range(g->members[k], annot, im, n_annot, flags, sb[k], se[k], &part[k]);
+            if (status[k] != WLD_OK) msg[k] = wld_last_error();
+        });
+    for (auto &t : th) t.join();
+    for (int k = 0; k < G; ++k)
+        if (status[k] != WLD_OK)
+            return fail(status[k], "device %d (shard %d): %s", g->members[k]->device, k, msg[k].c_str());
+    *out = std::move(part[0]);
+    for (int k = 1; k < G; ++k)
+        if (!annot_plan::merge(*out, part[k])) return fail(WLD_E_STATE, "internal: the members' results differ in shape");
+    return WLD_OK;
+}
+}  // namespace
+
+int wld_run_annot_scores(wld_ctx *c, const float *annot, uint32_t n_annot, int flags, uint32_t chunk_begin,
+                         uint32_t chunk_end, wld_annot_scores *out) {
+    if (!out) return fail(WLD_E_ARG, "null out");
+    memset(out, 0, sizeof(*out));
+    if (!c) return fail(WLD_E_ARG, "null context");
+    wld_ctx *c0 = c->members.empty() ? c : c->members[0];
+    for (wld_ctx *m : c->members.empty() ? std::vector<wld_ctx *>{c} : c->members) {
+        if (!m->loaded) return fail(WLD_E_STATE, "wld_run_annot_scores before wld_load");
+        if (m->pend.active) return fail(WLD_E_STATE, "wld_run_annot_scores during a run");
+    }
+    WLD_TRY(annot_check(c0, annot, n_annot, flags));
+    const uint32_t m = chunks_of(c0->L);
+    if (chunk_end == 0 || chunk_end > m) chunk_end = m;
+    if (chunk_begin > chunk_end) return fail(WLD_E_ARG, "chunk range [%u,%u) invalid", chunk_begin, chunk_end);
+    const size_t L = c0->L;
+    annot_plan::Image im;
+    try {
+        im = annot_plan::build_image(annot, L, n_annot, c0->LP);
+    } catch (const std::bad_alloc &) {
+        return fail(WLD_E_OOM, "host allocation of the annotation image (%zu sites x %u columns) failed", L, n_annot);
+    }
+    annot_plan::Scores s;
+    if (c->members.empty()) WLD_TRY(annot_range(c, annot, im, n_annot, flags, chunk_begin, chunk_end, &s));
+    else WLD_TRY(annot_group(c, annot, im, n_annot, flags, chunk_begin, chunk_end, &s));
+    out->score = (double *)malloc(std::max<size_t>(L * n_annot, 1) * sizeof(double));
+    out->partners = (uint32_t *)malloc(std::max<size_t>(L, 1) * sizeof(uint32_t));
+    if (!out->score || !out->partners) {
+        wld_annot_scores_free(out);
+        return fail(WLD_E_OOM, "host allocation of the scores (%zu sites x %u columns) failed", L, n_annot);
+    }
+    std::copy(s.score.begin(), s.score.end(), out->score);
+    std::copy(s.partners.begin(), s.partners.end(), out->partners);
+    out->n_sites = L;
+    out->n_annot = n_annot;
+    out->flags = flags;
+    out->pairs = s.pairs;
+    out->none_pairs = s.none_pairs;
+    out->nonfinite_pairs = s.nonfinite_pairs;
+    out->counted_pairs = s.counted_pairs;
+    out->tiles = s.tiles;
+    out->kernel_ms = s.kernel_ms;
+    return WLD_OK;
+}
+
+int wld_annot_scores_merge(wld_annot_scores *into, const wld_annot_scores *from) {
+    if (!into || !from) return fail(WLD_E_ARG, "wld_annot_scores_merge: null result");
+    if (into->n_sites != from->n_sites || into->n_annot != from->n_annot || into->flags != from->flags)
+        return fail(WLD_E_ARG, "wld_annot_scores_merge: the results differ in shape (%llu x %u, flags %d; %llu x %u, flags %d)",
+                    (unsigned long long)into->n_sites, into->n_annot, into->flags, (unsigned long long)from->n_sites,
+                    from->n_annot, from->flags);
+    if (into->n_sites && (!into->score || !into->partners || !from->score || !from->partners))
+        return fail(WLD_E_ARG, "wld_annot_scores_merge: a result without arrays");
+    into->pairs += from->pairs;
+    into->none_pairs += from->none_pairs;
+    into->nonfinite_pairs += from->nonfinite_pairs;
+    into->counted_pairs += from->counted_pairs;
+    into->tiles += from->tiles;
+    into->kernel_ms = std::max(into->kernel_ms, from->kernel_ms);
+    const size_t n = (size_t)into->n_sites * into->n_annot;
+    for (size_t i = 0; i < n; ++i) into->score[i] += from->score[i];
+    for (size_t i = 0; i < into->n_sites; ++i) into->partners[i] += from->partners[i];
+    return WLD_OK;
+}
+
+void wld_annot_scores_free(wld_annot_scores *s) {
+    if (!s) return;
+    free(s->score);
+    free(s->partners);
+    memset(s, 0, sizeof(*s));
 }
 
 

@@ -50,6 +50,11 @@
 //                      ascending, one line per (site, rank), rank from 0
 //                      (wld_run_partners; parent indices as in the pair TSV);
 //                      with it --pair-output may be left out
+//   --annot-input FILE       partitioned LD scores (wld_run_annot_scores): FILE is
+//   --annot-score-output FILE  a TSV "site<TAB>name1<TAB>..." of per-site
+//   --annot-self             annotations by parent index; the output has site,
+//                      partners and one <name>_l2 column per annotation;
+//                      --annot-self also counts r2(i, i) = 1
 //   --blocks-output FILE     LD-block TSV (block, first, last, sites, pairs,
 //   --blocks-r2 T            informative, strong, mean, min): maximal runs of
 //   --blocks-dprime T        consecutive sites of interest without a weak pair
@@ -79,6 +84,9 @@
 
 #include "weightedld.h"
 #include "tsv_format.hpp"
+#include "annot_plan.hpp"
+
+namespace annot_plan = wld::annot_plan;
 
 namespace {
 
@@ -264,6 +272,9 @@ struct Opt {
     float blocks_min_value = 0.0f;
     int blocks_rule = WLD_BLOCKS_ALL;
     uint32_t blocks_min_sites = 2;
+    // --annot-input / --annot-score-output / --annot-self: wld_run_annot_scores
+    std::string annot_input, annot_score_output;
+    bool annot_self = false;
 };
 
 void usage(FILE *f) {
@@ -278,6 +289,8 @@ void usage(FILE *f) {
             "        --exact-sums    (addition, not the reference's output) exact masked sums rounded once,\n"
             "                        instead of lib.rs's own f32 summation order; d' and r2 can differ from\n"
             "                        lib.rs's on rare-allele data (the default: output identical to the reference)\n"
+            "        --annot-self    (addition) with --annot-score-output: every site with both symbols also counts\n"
+            "                        r2 = 1 with itself, as LDSC's LD scores do\n"
             "    -V, --version       Prints version information\n\n"
             "OPTIONS:\n"
             "        --fasta-input <fasta-input>          The source file to load\n"
@@ -350,7 +363,17 @@ void usage(FILE *f) {
             "        --blocks-dprime <blocks-dprime>      (addition) a pair is weak when the row's |D'| is below this\n"
             "        --blocks-rule <blocks-rule>          (addition) all: no weak pair in a block; spine: none with its\n"
             "                                             first or last site [default: all]\n"
-            "        --blocks-min-sites <blocks-min-sites>  (addition) smallest block reported, at least 2 [default: 2]\n");
+            "        --blocks-min-sites <blocks-min-sites>  (addition) smallest block reported, at least 2 [default: 2]\n"
+            "        --annot-input <annot-input>          (addition) per-site annotations, Tab Separated: a header\n"
+            "                                             \"site<TAB>name1<TAB>...\" (1 to 128 names), then per site its\n"
+            "                                             parent coordinate (as the pair output's site columns) and\n"
+            "                                             one finite number per name; every site of interest needs a\n"
+            "                                             row, in site order; needs --annot-score-output\n"
+            "        --annot-score-output <annot-score-output>  (addition) Filename to write the partitioned LD scores\n"
+            "                                             to (site, partners, <name>_l2 per annotation: the sum of r2\n"
+            "                                             times the partner's annotation over every in-window partner,\n"
+            "                                             no threshold); needs --annot-input; obeys --max-distance,\n"
+            "                                             --max-sites and --devices; --pair-output may then be left out\n");
 }
 
 [[noreturn]] void arg_error(const char *msg, const char *arg) {
@@ -538,6 +561,12 @@ Opt parse(int argc, char **argv) {
                 arg_error("Invalid value for '--blocks-min-sites' (at least 2):", v.c_str());
             o.blocks_min_sites = (uint32_t)strtoull(v.c_str(), nullptr, 10);
             o.have_blocks_min = true;
+        } else if (a == "--annot-input") {
+            o.annot_input = need("--annot-input");
+        } else if (a == "--annot-score-output") {
+            o.annot_score_output = need("--annot-score-output");
+        } else if (a == "--annot-self") {
+            o.annot_self = true;
         } else if (a == "--kernel") {
             std::string k = need("--kernel");
             o.kernel = k == "valu" ? WLD_KERNEL_VALU : k == "mfma" ? WLD_KERNEL_MFMA : WLD_KERNEL_AUTO;
@@ -573,7 +602,13 @@ Opt parse(int argc, char **argv) {
                   : o.have_blocks_rule   ? "The argument '--blocks-rule' needs"
                                          : "The argument '--blocks-min-sites' needs",
                   "--blocks-output <blocks-output>");
-    if (!have_pair && !ld_sel && o.partners_output.empty() && o.blocks_output.empty())
+    if (!o.annot_input.empty() && o.annot_score_output.empty())
+        arg_error("The argument '--annot-input' needs", "--annot-score-output <annot-score-output>");
+    if (o.annot_input.empty() && !o.annot_score_output.empty())
+        arg_error("The argument '--annot-score-output' needs", "--annot-input <annot-input>");
+    if (o.annot_self && o.annot_score_output.empty())
+        arg_error("The argument '--annot-self' needs", "--annot-input <annot-input> and --annot-score-output <annot-score-output>");
+    if (!have_pair && !ld_sel && o.partners_output.empty() && o.blocks_output.empty() && o.annot_score_output.empty())
         arg_error("The following required arguments were not provided:", "--pair-output <pair-output>");
     if (!o.have_ld_sites_r2) o.ld_sites_r2 = o.r2_threshold;
     if (!o.have_partners_r2) o.partners_r2 = o.r2_threshold;
@@ -1083,6 +1118,73 @@ void log_progress(const ProgressBar &pb) {
            pb.last_position());
 }
 
+// --annot-input: the file, read and checked right after the arguments (before
+// the input set is read and before any device step); a format error ends the
+// run with the line it is on.
+annot_plan::File read_annot_input(const Opt &opt) {
+    annot_plan::File f;
+    if (opt.annot_input.empty()) return f;
+    std::string err;
+    if (!annot_plan::read_file(opt.annot_input.c_str(), f, err)) {
+        fprintf(stderr, "error: --annot-input %s: %s\n", opt.annot_input.c_str(), err.c_str());
+        exit(1);
+    }
+    return f;
+}
+
+// ... joined to the loaded set (parent[i] as in write_summaries): loaded site i
+// takes the first unused row at or after the previous match that carries its
+// parent index.  A site of interest without a row ends the run, before any
+// pair is computed.
+std::vector<float> resolve_annot(const Opt &opt, const annot_plan::File &file, const std::vector<uint64_t> &parent) {
+    std::vector<float> annot;
+    if (opt.annot_score_output.empty()) return annot;
+    std::string err;
+    if (!annot_plan::join(file, parent.data(), parent.size(), annot, err)) {
+        fprintf(stderr, "error: --annot-input %s: %s\n", opt.annot_input.c_str(), err.c_str());
+        quit(1);
+    }
+    return annot;
+}
+
+// --annot-score-output: one pass over every in-window pair of the loaded set
+// (wld_run_annot_scores: the r2 of the pair TSV's rows, no threshold), then the
+// TSV, one line per loaded site.  Doubles print as %.9g.
+void write_annot_scores(const Opt &opt, wld_ctx *ctx, const annot_plan::File &file, const std::vector<float> &annot,
+                        const std::vector<uint64_t> &parent) {
+    if (opt.annot_score_output.empty()) return;
+    using clk = std::chrono::steady_clock;
+    const auto sw = clk::now();
+    const uint32_t C = (uint32_t)file.names.size();
+    wld_annot_scores s;
+    const int st = wld_run_annot_scores(ctx, annot.data(), C, opt.annot_self ? WLD_ANNOT_SELF : 0, 0, 0, &s);
+    if (st != WLD_OK) die(st, "run_annot_scores");
+    INFO("Partitioned the LD scores of %s pairs (%s without a statistic) over %u annotations in %s",
+         human((double)s.pairs).c_str(), human((double)(s.none_pairs + s.nonfinite_pairs)).c_str(), C,
+         fmt_duration(clk::now() - sw).c_str());
+    INFO("Writing output to %s", debug_path(opt.annot_score_output).c_str());
+    std::string out = "site\tpartners";
+    for (const std::string &n : file.names) out += "\t" + n + "_l2";
+    out += "\n";
+    char cell[64];
+    for (uint64_t i = 0; i < s.n_sites && i < parent.size(); ++i) {
+        snprintf(cell, sizeof cell, "%" PRIu64 "\t%u", parent[i], s.partners[i]);
+        out += cell;
+        for (uint32_t k = 0; k < C; ++k) {
+            snprintf(cell, sizeof cell, "\t%.9g", s.score[i * C + k]);
+            out += cell;
+        }
+        out += "\n";
+    }
+    FILE *f = fopen(opt.annot_score_output.c_str(), "wb");
+    const bool ok = f && fwrite(out.data(), 1, out.size(), f) == out.size();
+    if ((f && fclose(f) != 0) || !ok) {
+        fprintf(stderr, "Error: cannot write %s\n", opt.annot_score_output.c_str());
+        quit(1);
+    }
+    wld_annot_scores_free(&s);
+}
+
 // main.rs:186-212 after the pair computation: timing logs, TSV, clean-up.
 int finish(const Opt &opt, wld_ctx *ctx, wld_pairs &pairs, std::chrono::steady_clock::duration dur,
            uint64_t total_pairs) {
@@ -1114,7 +1216,7 @@ int finish(const Opt &opt, wld_ctx *ctx, wld_pairs &pairs, std::chrono::steady_c
 
 // --gpu-prepass: main.rs:139-190 with the site filter and Henikoff weights on
 // the device (wld_load_filtered), then the staged run and a host copy of the rows.
-int run_gpu_prepass(const Opt &opt, wld_siteset *siteset, wld_ctx *ctx) {
+int run_gpu_prepass(const Opt &opt, wld_siteset *siteset, wld_ctx *ctx, const annot_plan::File &annot_file) {
     using clk = std::chrono::steady_clock;
     const size_t L0 = wld_siteset_n_sites(siteset), N = wld_siteset_n_seqs(siteset);
     auto sw = clk::now();
@@ -1138,6 +1240,7 @@ int run_gpu_prepass(const Opt &opt, wld_siteset *siteset, wld_ctx *ctx) {
     if (L && (st = wld_site_map_copy(ctx, parent.data())) != WLD_OK) die(st, "site_map_copy");
     const std::vector<uint32_t> targets = resolve_targets(opt, parent);
     const HeatCells heat_cells = resolve_heat_cells(opt, parent);
+    const std::vector<float> annot = resolve_annot(opt, annot_file, parent);
     if (!opt.pair_output.empty()) INFO("Beginning pairwise weighted LD computation");
     sw = clk::now();
     const uint64_t total_pairs = ((uint64_t)L - 1) * ((uint64_t)L - 2) / 2;  // main.rs:168 (sic, wraps)
@@ -1155,6 +1258,7 @@ int run_gpu_prepass(const Opt &opt, wld_siteset *siteset, wld_ctx *ctx) {
     write_targets(opt, ctx, targets);
     write_partners(opt, ctx, parent);
     write_blocks(opt, ctx, parent);
+    write_annot_scores(opt, ctx, annot_file, annot, parent);
     // (a FASTA set has no site_map: a kept site's parent index is its index in the unfiltered set)
     write_prune(opt, ctx, parent, siteset, std::vector<size_t>(parent.begin(), parent.end()));
     return finish(opt, ctx, pairs, dur, total_pairs);
@@ -1165,6 +1269,7 @@ int run_gpu_prepass(const Opt &opt, wld_siteset *siteset, wld_ctx *ctx) {
 int main(int argc, char **argv) {
     init_logger();
     Opt opt = parse(argc, argv);
+    const annot_plan::File annot_file = read_annot_input(opt);
     using clk = std::chrono::steady_clock;
     if (opt.exact_sums) {
         // not a reference flag (main.rs:14-68 has none like it): printed at any
@@ -1218,7 +1323,7 @@ int main(int argc, char **argv) {
     INFO("Loaded %s file in %s", vcf ? "vcf" : "fasta", fmt_duration(clk::now() - sw).c_str());
     INFO("    %zu sequences, %zu sites", wld_siteset_n_seqs(siteset), wld_siteset_n_sites(siteset));
 
-    if (opt.gpu_prepass && !vcf) return run_gpu_prepass(opt, siteset, get_ctx());
+    if (opt.gpu_prepass && !vcf) return run_gpu_prepass(opt, siteset, get_ctx(), annot_file);
 
     sw = clk::now();
     wld_siteset *filtered = nullptr;
@@ -1254,6 +1359,7 @@ int main(int argc, char **argv) {
     for (size_t i = 0; i < L; ++i) parent[i] = wld_siteset_parent_site_index(filtered, i);
     const std::vector<uint32_t> targets = resolve_targets(opt, parent);
     const HeatCells heat_cells = resolve_heat_cells(opt, parent);
+    const std::vector<float> annot = resolve_annot(opt, annot_file, parent);
     if (!opt.pair_output.empty()) INFO("Beginning pairwise weighted LD computation");
     sw = clk::now();
     const uint64_t total_pairs = ((uint64_t)L - 1) * ((uint64_t)L - 2) / 2;  // main.rs:168 (sic, wraps)
@@ -1275,6 +1381,7 @@ int main(int argc, char **argv) {
     write_targets(opt, ctx, targets);
     write_partners(opt, ctx, parent);
     write_blocks(opt, ctx, parent);
+    write_annot_scores(opt, ctx, annot_file, annot, parent);
     std::vector<size_t> self(L);
     for (size_t i = 0; i < L; ++i) self[i] = i;
     write_prune(opt, ctx, parent, filtered, self);

@@ -194,6 +194,22 @@ struct BlockStatsArgs {
     float strong_min;
 };
 
+// The accumulators and operands of a partitioned-score run (pair_annot.hip;
+// wld_run_annot_scores; annot_plan.hpp builds the image and the mask).
+// counts = {pairs, none, nonfinite, counted}, score [LP][CP] and partners [LP]
+// are zero before the launch; a tile adds to a destination with at most one
+// atomic.  annot: the padded image [LP][CP] (CP a multiple of 16; zero past the
+// loaded sites and the caller's columns); zero: per (64-site tile, 16-column
+// chunk) [tile * (CP / 16) + chunk], 1 where the image holds only zeros.
+struct AnnotArgs {
+    unsigned long long *counts;
+    double *score;
+    uint32_t *partners;
+    const float *annot;
+    const uint8_t *zero;
+    uint32_t CP;
+};
+
 // The staging of one batch of a best-partner run (pair_partners.hip;
 // wld_run_partners; layout in partners_plan.hpp).  Tile position p of the
 // launch's list (p < n_tiles, the workgroup id) owns the parts (2 p + side) *
@@ -307,6 +323,12 @@ void launch_pair_summary(const ValuLaunch &v, const OrderArgs &o, const SummaryA
 // The same sums over v's list (the heat map's own filtered tile list), every
 // considered pair reduced into its cell of h; o gives the window only.
 void launch_pair_heatmap(const ValuLaunch &v, const OrderArgs &o, const HeatmapArgs &h, hipStream_t st);
+
+// pair_annot.hip
+// The same sums over v's list (the call's own tile list of the range and
+// window); every tile's counted r2 multiplied into a's score rows; o gives the
+// window only.
+void launch_pair_annot(const ValuLaunch &v, const OrderArgs &o, const AnnotArgs &a, hipStream_t st);
 
 // pair_blocks.hip
 // The same sums over v's list: pass 1 (every tile of the range and window)
