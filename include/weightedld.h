@@ -272,6 +272,19 @@ int wld_set_kernel(wld_ctx *ctx, int kernel);
  *                      tile-pair fp6 screen runs; 0: always four.  A pair the
  *                      three sums reject is rejected on four: same candidate
  *                      tiles, sub-blocks and rows.
+ *   WLD_OPT_FP6_QUICK  1 (default, auto): where the fp6 screen runs on three
+ *                      sums (WLD_OPT_FP6_THREE) and its sample run found it
+ *                      worthwhile at this threshold or a lower one, each wave
+ *                      first tries to reject a lane's 16 pairs of a row block
+ *                      together, from one numerator maximum and marginal
+ *                      bounds shared by the lane, at half the vector
+ *                      operations per pair; a row block where some lane
+ *                      cannot (at most a quarter of the sampled ones, else
+ *                      off) takes the per-pair test as before.  Lists that
+ *                      are not sampled stay off.  2: wherever the three-sum
+ *                      kernel runs; 0: never.  A row block the quick test
+ *                      rejects holds no pair the per-pair test keeps: same
+ *                      second passes, candidate tiles, sub-blocks and rows.
  *   WLD_OPT_TARGET_BATCH_SLOTS  wld_run_targets: the pair slots (16 x target
  *                      blocks x padded site count, three floats each) of the
  *                      dense staging one batch may use (default 2^26: 768 MiB;
@@ -309,6 +322,7 @@ int wld_set_kernel(wld_ctx *ctx, int kernel);
 #define WLD_OPT_FP6_SHARED 19
 #define WLD_OPT_PARTNERS_BATCH_BYTES 20
 #define WLD_OPT_FP6_THREE 21
+#define WLD_OPT_FP6_QUICK 22
 int wld_set_option(wld_ctx *ctx, int option, int64_t value);
 int wld_get_option(wld_ctx *ctx, int option, int64_t *value);
 
@@ -550,6 +564,10 @@ typedef struct {
                                 (WLD_OPT_FP6_THREE), the fourth only for the entries counted below */
     uint64_t fp6_rechecked;  /* fp6_three == 1: the screen's entries (tile pairs or single tiles) that ran the
                                 second pass for the fourth sum; else 0 */
+    int fp6_quick;           /* 1: the three-sum screen (fp6_three == 1) ran the lane-shared quick test in front of
+                                its per-pair test (WLD_OPT_FP6_QUICK) */
+    uint64_t fp6_quick_full; /* fp6_quick == 1: the screen's row blocks (16 sites x a 64-site tile, four per tile)
+                                that the quick test did not reject and the per-pair test looked at; else 0 */
 } wld_run_stats;
 int wld_last_stats(wld_ctx *ctx, wld_run_stats *out);
 /* The fp6 screen's weight codes of the loaded set (tests, diagnostics): the

@@ -27,7 +27,8 @@ KERNEL_AUTO, KERNEL_VALU, KERNEL_MFMA = 0, 1, 2
 OPTIONS = {"prefilter": 1, "screen": 2, "tile_order": 3, "all_planes": 4, "mfma_layout": 5, "valu_plain": 6,
            "staging_rows": 7, "host_batch_pairs": 8, "ref_sums": 11, "fused_scan": 12, "screen_fp6": 13,
            "test_guard": 14, "fp6_pairs_min_tiles": 15, "i8_pairs": 16, "fp6_a4": 17,
-           "target_batch_slots": 18, "fp6_shared": 19, "partners_batch_bytes": 20, "fp6_three": 21}
+           "target_batch_slots": 18, "fp6_shared": 19, "partners_batch_bytes": 20, "fp6_three": 21,
+           "fp6_quick": 22}
 
 
 class WldError(RuntimeError):
@@ -73,6 +74,8 @@ class RunStats(ctypes.Structure):
         ("fp6_shared", ctypes.c_int),
         ("fp6_three", ctypes.c_int),
         ("fp6_rechecked", ctypes.c_uint64),
+        ("fp6_quick", ctypes.c_int),
+        ("fp6_quick_full", ctypes.c_uint64),
     ]
 
 

@@ -122,7 +122,7 @@ struct wld_ctx {
     int opt_screen = 1;  // WLD_OPT_SCREEN: 0 never, 1 auto (default), 2 always, 3 two-plane, 4 exact candidate pairs
     screen_policy::Learned learned;  // auto: the thresholds the passes so far have taught (screen_policy.hpp)
     screen_policy::Plan pass;        // the last row pass's plan (its route as launched)
-    DevBuf fp6_probe_buf;  // the sample run's three counts
+    DevBuf fp6_probe_buf;  // the sample run's four counts
     bool opt_site_major = false, opt_valu_plain = false;
     bool opt_fused_scan = true;  // WLD_OPT_FUSED_SCAN: the chunk scan in the candidate launch's last workgroup
     int opt_test_guard = 0;      // WLD_OPT_TEST_GUARD (tests: a bucket count corrupted before the candidate launch)
@@ -137,6 +137,7 @@ struct wld_ctx {
     bool opt_i8_pairs = true;    // WLD_OPT_I8_PAIRS: the i8 screen on tile pairs (pre-multiplied images)
     int opt_fp6 = 1;             // WLD_OPT_SCREEN_FP6: 0 off, 1 auto, 2 whenever it applies, 3 auto without the sample run
     bool opt_fp6_a4 = true;      // WLD_OPT_FP6_A4: the fp6 screen's A image as fp4 where the weight codes fit e2m1
+    int opt_fp6_quick = 1;  // WLD_OPT_FP6_QUICK: the lane-shared quick test in front of the three-sum test (0 never, 1 auto: after a sample run, 2 always)
     int opt_fp6_three = 1;  // WLD_OPT_FP6_THREE: the tile-pair fp6 screen on three sums (0 never, 1 auto: after a sample run, 2 always)
     bool opt_fp6_shared = true;  // WLD_OPT_FP6_SHARED: no A image where the weight codes are all one code (the B image serves both operands)
     bool opt_ref_sums = true;  // WLD_OPT_REF_SUMS: lib.rs's own f32 summation order (default)
@@ -830,7 +831,8 @@ struct PolicyInputs {
     screen_policy::PassFacts pass;
 };
 PolicyInputs policy_inputs(const wld_ctx *c, float thr, bool dense) {
-    return {{c->opt_screen, c->opt_fp6, c->opt_ref_sums, c->opt_prefilter, c->opt_i8_pairs, c->opt_fp6_three},
+    return {{c->opt_screen, c->opt_fp6, c->opt_ref_sums, c->opt_prefilter, c->opt_i8_pairs, c->opt_fp6_three,
+             c->opt_fp6_quick},
             {c->kernel == WLD_KERNEL_MFMA, c->use_frag, c->wst.nonneg != 0, c->NP, c->plane_mask, c->fp6_ok,
              c->fp6_better},
             {c->f6_n_pairs != 0, c->n_tiles, thr, dense, c->prog_pass, c->pend.count_out != nullptr}};
@@ -905,6 +907,7 @@ int launch_pairs(wld_ctx *c, float thr, const OrderArgs &o, const DenseArgs *den
         m.bound_test = plan.bound_test;
         m.fp6_bail = plan.fp6_bail;
         m.fp6_three = plan.fp6_three;
+        m.fp6_quick = plan.fp6_quick;
         m.f6_rechecked = reinterpret_cast<unsigned *>(ptr<unsigned long long>(c->counters) + kF6Rechecked);
         m.i8img = &c->i8s;
         for (int t = 0; t < 3; ++t) m.resid[t] = c->wst.resid[t];
@@ -1087,6 +1090,11 @@ int wld_set_option(wld_ctx *c, int option, int64_t value) {
             c->opt_fp6_three = (int)value;
             c->learned.reset();  // (what a sample run counts depends on it)
             break;
+        case WLD_OPT_FP6_QUICK:
+            if (value < 0 || value > 2) return fail(WLD_E_ARG, "WLD_OPT_FP6_QUICK takes 0 to 2");
+            c->opt_fp6_quick = (int)value;
+            c->learned.reset();  // (what a sample run counts depends on it)
+            break;
         default: return fail(WLD_E_ARG, "unknown option %d", option);
     }
     return WLD_OK;
@@ -1203,6 +1211,7 @@ int wld_get_option(wld_ctx *c, int option, int64_t *value) {
         case WLD_OPT_FP6_A4: *value = c->opt_fp6_a4; break;
         case WLD_OPT_FP6_SHARED: *value = c->opt_fp6_shared; break;
         case WLD_OPT_FP6_THREE: *value = c->opt_fp6_three; break;
+        case WLD_OPT_FP6_QUICK: *value = c->opt_fp6_quick; break;
         default: return fail(WLD_E_ARG, "unknown option %d", option);
     }
     return WLD_OK;
@@ -1526,21 +1535,24 @@ int fp6_sample(wld_ctx *c, float thr, bool operands_fresh) {
     const PolicyInputs in = policy_inputs(c, thr, false);
     if (!screen_policy::wants_sample(in.opt, in.load, in.pass, c->learned)) return WLD_OK;
     const hipStream_t s = !operands_fresh && c->own_stream ? c->own_stream : c->stream;
-    WLD_TRY(ensure(c->fp6_probe_buf, 3 * sizeof(unsigned)));
+    WLD_TRY(ensure(c->fp6_probe_buf, 4 * sizeof(unsigned)));
     MfmaLaunch m = mfma_base(c, thr);
     // on three sums where the pass might be (the same candidate counts: the
     // fourth sum is formed wherever a verdict needs it), so that the sample
     // also tells how often the second pass runs
     m.fp6_three = c->opt_fp6_three != 0 && m.f6_pairs != nullptr;
+    // ... and with the quick test where the pass might be, to count the row
+    // blocks that fall through it
+    m.fp6_quick = m.fp6_three && c->opt_fp6_quick != 0;
     const uint32_t entries = m.f6_pairs ? m.f6_n_pairs : m.n_tiles;
     const uint32_t stride = std::max<uint32_t>(1, std::min<uint32_t>(64, entries / 256));
     launch_fp6_probe(m, ptr<unsigned>(c->fp6_probe_buf), stride, s);
     HIP_TRY(hipGetLastError());
-    unsigned h[3] = {0, 0, 0};
+    unsigned h[4] = {0, 0, 0, 0};
     HIP_TRY(hipMemcpyAsync(h, c->fp6_probe_buf.p, sizeof(h), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     c->fp6_sampled = true;
-    screen_policy::learn(c->learned, screen_policy::Sample{thr, h[0], h[1], m.fp6_three, h[2]});
+    screen_policy::learn(c->learned, screen_policy::Sample{thr, h[0], h[1], m.fp6_three, h[2], m.fp6_quick, h[3]});
     return WLD_OK;
 }
 
@@ -1748,7 +1760,11 @@ int run_complete(wld_ctx *c, uint64_t *n_rows) {
     c->stats.fp6_a4 = c->stats.screen_fp6 == 1 && c->f6.a4 ? 1 : 0;
     c->stats.fp6_shared = c->stats.screen_fp6 == 1 && c->f6.shared ? 1 : 0;
     c->stats.fp6_three = c->stats.screen_fp6 == 1 ? screen_policy::stat_fp6_three(c->pass) : 0;
-    c->stats.fp6_rechecked = c->stats.fp6_three ? __atomic_load_n(&c->h_cnt[5], __ATOMIC_ACQUIRE) : 0;
+    // (h_cnt[5]: the entries rechecked, and above them the quick test's row blocks)
+    const unsigned long long f6_counts = __atomic_load_n(&c->h_cnt[5], __ATOMIC_ACQUIRE);
+    c->stats.fp6_rechecked = c->stats.fp6_three ? (f6_counts & 0xFFFFFFFFull) : 0;
+    c->stats.fp6_quick = c->stats.screen_fp6 == 1 ? screen_policy::stat_fp6_quick(c->pass) : 0;
+    c->stats.fp6_quick_full = c->stats.fp6_quick ? (f6_counts >> 32) : 0;
     c->stats.candidate_pairs = cand_pairs ? h[0] : 0;
     // auto: what this pass's counts teach the policy (screen_policy.hpp: the break-evens)
     screen_policy::learn(c->learned, screen_policy::Outcome{route, r.thr, false, h[2], c->n_tiles, h[0], r.pairs});

@@ -82,7 +82,7 @@ __device__ inline bool tile_in_range(uint32_t tile, uint32_t L) {
 // *count_out (may be null) and host_out[1], the staging cursor into
 // host_out[0], the candidate-tile count cand_count[0] into host_out[2] and
 // their computed 16x16 sub-blocks cand_count[1] into host_out[3], *rechecked
-// into host_out[5] (host_out: mapped pinned memory, may be null); cursor, the chunk totals and both
+// (with rechecked[1] in the upper half) into host_out[5] (host_out: mapped pinned memory, may be null); cursor, the chunk totals and both
 // candidate counts are left at 0 for the next run.  With ticket set, the last
 // workgroup of the candidate launch after a screen runs it (scan_tail,
 // pair_common.hpp) instead of a launch of its own.
@@ -101,14 +101,17 @@ struct ScanArgs {
     unsigned *cand_buckets_reset;
     unsigned *ticket;  // 0 between launches; null: the scan is launched on its own
     // the fp6 screen's count of entries that formed the fourth sum (may be
-    // null): into host_out[5], and back to 0 for the next pass
+    // null) and, in the word after it, of the row blocks its quick test did
+    // not reject: into host_out[5] (lower and upper half), and back to 0 for
+    // the next pass
     unsigned *rechecked = nullptr;
 };
 
 // 64-bit words of a context's run counters (capi.hip enqueue_pass):
 // {cursor, total, {ticket, work}, set 0: {candidates, sub-blocks} + 16 bucket
 // counts (9 words), set 1: the same, the cursor the scan saw, the fp6
-// screen's entries that formed the fourth sum}
+// screen's entries that formed the fourth sum (lower half) and row blocks
+// its quick test did not reject (upper half)}
 constexpr uint32_t kCounterWords = 23;
 constexpr uint32_t kCursorSeen = 21;
 constexpr uint32_t kF6Rechecked = 22;
@@ -508,14 +511,19 @@ struct MfmaLaunch {
     // *f6_rechecked (0 before the launch: the scan resets it)
     bool fp6_three = false;
     unsigned *f6_rechecked = nullptr;
+    // ... with the lane-shared quick test in front of the three-sum test
+    // (WLD_OPT_FP6_QUICK), which counts the row blocks that fell through to it
+    // into f6_rechecked[1]
+    bool fp6_quick = false;
     // I8PairScreen: the pre-multiplied operands of the top active plane
     const I8Screen *i8img = nullptr;
 };
 // The fp6 screen's sample run over every stride-th entry of its list: probe[0]
 // = the sampled tiles holding a pair its bound cannot reject, probe[1] = the
 // sampled tiles, probe[2] = with m.fp6_three (tile pairs) the sampled entries
-// that formed the fourth sum, else 0 (m as for the pass; nothing else is
-// written)
+// that formed the fourth sum, else 0, probe[3] = with m.fp6_quick the row
+// blocks (four per tile) the quick test did not reject, else 0 (m as for the
+// pass; nothing else is written)
 void launch_fp6_probe(const MfmaLaunch &m, unsigned *probe, uint32_t stride, hipStream_t s);
 // Enqueues the MFMA pair kernel(s) of one pass by m.route; where a screen runs
 // (screen_policy::ran_screen; never for dense stats or site-major, which the

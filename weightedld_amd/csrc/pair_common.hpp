@@ -390,6 +390,87 @@ __host__ __device__ __forceinline__ float r2_screen_terms_f6t(float p, float s, 
     const float nub = fmaf(2.0f, nt, E);
     return fmaf(nub, nub, -(thr_c * ((m1 * m2) * (m3 * m4))));
 }
+// The quick test in front of r2_screen_terms_f6t (WLD_OPT_FP6_QUICK; pair_mfma.hip
+// f6t_quick_skip): a lane's 16 pairs of a row block, 4 row sites e by 4 column
+// sites n, rejected together.  Per pair only the numerator is formed, with
+// the operations of r2_screen_terms_f6t on the same values (d, q, X0lo, cap2
+// and the two fmaf: so the pair's nt is that function's bit for bit), and
+// three maxima are kept: nt, d = 2 P10 and p = P01 (f6q_pair, 15 operations
+// where the full test takes 30).  Once per lane and row block (f6q_lane_terms)
+// the marginals are bounded from the sites' terms alone,
+//   m1' = min_e c1 - dmax              m2' = min_e rA2 + min_n cB2
+//   m3' = min_e rA + min_n cB3         m4' = min_n c4 - 2 pmax,
+// and t1' = fma(nub', nub', -fl(thr_c P')) with nub' = fl(2 nt + E) and P' the
+// product of the primed marginals, rounded as r2_screen_terms_f6t rounds its
+// own.  Quick skip iff t1' <= 0 and mlo' >= mloc.
+// It is implied-conservative: where it skips, r2_screen_terms_f6t skips every
+// one of the 16 pairs (t1 <= 0 and mlo >= mloc), in f32 as written, so a row
+// block it rejects has no pair in doubt and the three-sum kernel's verdicts
+// are unchanged.
+//   * Marginals.  Every operand is on the 1/16 grid below 2^20 (the argument
+//     above), and so are the minima and maxima of such values: each primed
+//     marginal is exact.  d = 2 P10 >= 0 and p = P01 >= 0 are weight sums, so
+//     for every pair (e, n) m1' <= c1(e) - d = m1, m2' <= (rA2(e) + cB2(n)) +
+//     d = m2, m3' <= 2 p + (rA(e) + cB3(n)) = m3 and m4' <= c4(n) - 2 p = m4:
+//     mlo' <= mlo, and mlo' >= mloc implies the pair's mlo >= mloc.
+//   * Product.  A skip has mlo' >= mloc >= 0, so the primed marginals and the
+//     pair's above them are nonnegative.  A rounded f32 product of nonnegative
+//     factors is nondecreasing in each (rounding is monotone): fl(m1' m2'),
+//     fl(m3' m4'), their rounded product and its rounded product with thr_c >=
+//     0 are each <= the pair's: P' <= P.
+//   * Numerator.  nt' is the maximum of the 16 pairs' own nt, so nub' = fl(2
+//     nt' + E) >= fl(2 nt + E) = nub >= 0 (one fmaf each, monotone; E >= 0).
+//   * Hence nub'^2 - P' >= nub^2 - P exactly, and t1' = fl(nub'^2 - P') >=
+//     fl(nub^2 - P) = t1 (one rounding of a monotone exact value): t1' <= 0
+//     implies t1 <= 0.  No slack term anywhere.
+// A NaN (there is none: every input is finite and far from overflow) would
+// fail both comparisons and send the lane to the full test.
+// tests/cpp/f6_quick_check.cpp checks the implication and the nt bits on lanes
+// built from small alignments.
+struct F6qAcc {  // a lane's maxima over a row block's 16 pairs (all >= 0)
+    float dmax = 0.0f, pmax = 0.0f, nt = 0.0f;
+};
+struct F6qRowMin {  // minima over the lane's 4 row sites
+    float c1, rA2, rA;
+};
+struct F6qColMin {  // minima over the lane's 4 column sites
+    float cB2, cB3, c4;
+};
+// (start from INFINITY; one row site at a time)
+__host__ __device__ __forceinline__ void f6q_row_min(F6qRowMin &m, const F6tRow &a) {
+    m.c1 = fminf(m.c1, a.c1);
+    m.rA2 = fminf(m.rA2, a.rA2);
+    m.rA = fminf(m.rA, a.rA);
+}
+__host__ __device__ __forceinline__ F6qColMin f6q_col_min(const F6tCol (&b)[4]) {
+    return F6qColMin{fminf(fminf(b[0].cB2, b[1].cB2), fminf(b[2].cB2, b[3].cB2)),
+                     fminf(fminf(b[0].cB3, b[1].cB3), fminf(b[2].cB3, b[3].cB3)),
+                     fminf(fminf(b[0].c4, b[1].c4), fminf(b[2].c4, b[3].c4))};
+}
+// one pair into the lane's maxima; returns the pair's nt (r2_screen_terms_f6t's)
+__host__ __device__ __forceinline__ float f6q_pair(float p, float s, float t, const F6tRow &a, const F6tCol &b,
+                                                   F6qAcc &acc) {
+    const float d = s - t;
+    acc.dmax = fmaxf(acc.dmax, d);
+    acc.pmax = fmaxf(acc.pmax, p);
+    const float q = -((a.ma2 - s) * (b.mb - p));
+    const float X0lo = p + (a.row + b.col);
+    const float cap2 = fminf(fmaf(-2.0f, p, a.Ma2), b.Mb2 - d);
+    const float nt = fmaxf(fabsf(fmaf(X0lo, t, q)), fabsf(fmaf(X0lo + cap2, t, q)));
+    acc.nt = fmaxf(acc.nt, nt);
+    return nt;
+}
+// t1' of the lane and row block, mlo its smallest primed marginal
+__host__ __device__ __forceinline__ float f6q_lane_terms(const F6qAcc &acc, const F6qRowMin &a, const F6qColMin &b,
+                                                         float thr_c, float E, float &mlo) {
+    const float m1 = a.c1 - acc.dmax, m2 = a.rA2 + b.cB2;
+    const float m3 = a.rA + b.cB3, m4 = fmaf(-2.0f, acc.pmax, b.c4);
+    mlo = fminf(fminf(m1, m2), fminf(m3, m4));
+    const float nub = fmaf(2.0f, acc.nt, E);
+    return fmaf(nub, nub, -(thr_c * ((m1 * m2) * (m3 * m4))));
+}
+// (written so that a NaN does not skip)
+__host__ __device__ __forceinline__ bool f6q_skip(float t1, float mlo, float mloc) { return t1 <= 0.0f && mlo >= mloc; }
 __host__ __device__ __forceinline__ float r2_screen_violation(float T, float A, float B, float AB, float R,
                                                               float thr_c) {
     float E, mloc, t2;
@@ -551,12 +632,13 @@ __device__ inline void chunk_scan_block(const ScanArgs &a) {
             a.host_out[1] = run;
             a.host_out[2] = cand;
             a.host_out[3] = blocks;
-            if (a.rechecked) a.host_out[5] = ld32(a.rechecked);  // ([4]: the guard word)
+            if (a.rechecked)  // ([4]: the guard word)
+                a.host_out[5] = (unsigned long long)ld32(a.rechecked) | (unsigned long long)ld32(a.rechecked + 1) << 32;
             __threadfence_system();
         }
         // (every screen workgroup that counted has finished: the scan runs
         // in a launch behind the screen's)
-        if (a.rechecked) *a.rechecked = 0;
+        if (a.rechecked) a.rechecked[0] = a.rechecked[1] = 0;
     }
     __syncthreads();
     unsigned long long base = sw[wv] + v - s;

@@ -411,7 +411,9 @@ struct ScreenArgs {
     unsigned *probe;
     uint32_t probe_stride;
     // the fp6 tile-pair screen on three sums: the entries that formed the
-    // fourth sum are counted here (a pass) or in probe[2] (the sample run)
+    // fourth sum are counted here (a pass) or in probe[2] (the sample run);
+    // with the quick test, the row blocks it did not reject in rechecked[1]
+    // (the 64-bit counter word's second half) or probe[3]
     unsigned *rechecked;
 };
 
@@ -1269,6 +1271,82 @@ __device__ __forceinline__ bool f6t_any_doubt(const v4f (&acc)[4][2][2], const F
     }
     return doubt;
 }
+// The quick test in front of f6t_any_doubt (WLD_OPT_FP6_QUICK; pair_common.hpp
+// f6q_pair / f6q_lane_terms): does every lane of the wave reject its 16 pairs
+// of this row block together, from one numerator maximum and marginal bounds
+// taken over the lane?  Then no pair of the row block is in doubt.  cb / cm:
+// the lane's column terms and their minima, formed once for the wave's two
+// row blocks.  Padded and filtered pairs are tested as the others: one that
+// fails only sends the wave to f6t_any_doubt, which masks it (diagonal tiles
+// do not come here: f6t_wave_doubt).  The result is wave-uniform (one ballot).
+template <bool kShared>
+__device__ __forceinline__ bool f6t_quick_skip(const v4f (&acc)[4][2][2], const F6Epi &ep, const float2 *sA,
+                                               const F6tCol (&cb)[4], const F6qColMin &cm, float W6, float wv) {
+    F6qRowMin rm{INFINITY, INFINITY, INFINITY};
+    F6qAcc q;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const float2 a = sA[16 * ep.wq + 4 * (ep.lane >> 4) + e];
+        const F6tRow ra = f6t_row(W6, a.x, a.y, ep.R2);
+        f6q_row_min(rm, ra);
+#pragma unroll
+        for (int n = 0; n < 4; ++n) {
+            float p = acc[n][0][1][e], s = acc[n][1][0][e], t = acc[n][1][1][e];
+            if constexpr (kShared) p *= 0.5f * wv, s *= wv, t *= wv;
+            f6q_pair(p, s, t, ra, cb[n], q);
+            // (one pair at a time: left to itself the scheduler interleaves
+            // the 32 pairs' chains, and the accumulators spill)
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+    float mlo;
+    const float t1 = f6q_lane_terms(q, rm, cm, ep.thr_c, ep.E, mlo);
+    return __ballot(!f6q_skip(t1, mlo, ep.mloc)) == 0;
+}
+// Is any pair of the wave's two row blocks in doubt on three sums?  kQuick: a
+// row block that f6t_quick_skip rejects is not looked at again; the others,
+// counted into *full (an LDS word, one atomic per wave that has any), run
+// f6t_any_doubt as without it.  Both quick tests come first, so the count does
+// not depend on which row block's doubt is found first.  A diagonal tile goes
+// straight to f6t_any_doubt, uncounted: each of its row blocks holds 16 pairs
+// of a site with itself (r2 = 1), which no bound over a lane can reject.
+// What the quick test leaves behind is kept from f6t_any_doubt: it reads its
+// site terms again, forms its lane indices, rescales the shared image's sums
+// and takes every pair's d = s - t anew (wv, the lane and the t sums pass
+// through empty statements, in place and at no instruction).  Values the
+// compiler keeps live across the quick test for it cost the registers the
+// accumulators need: they spill.
+template <bool kShared, bool kQuick>
+__device__ __forceinline__ bool f6t_wave_doubt(v4f (&acc)[2][4][2][2], const F6Epi &ep0, const F6Epi &ep1,
+                                               const float2 *sA, const float2 *sB, float W6, float wv, uint32_t *full) {
+    if constexpr (kQuick) {
+        bool full0 = true, full1 = true;  // (uniform)
+        if (ep0.ta != ep0.tb) {
+            F6tCol cb[4];
+#pragma unroll
+            for (int n = 0; n < 4; ++n) {
+                const float2 b = sB[(ep0.lane & 15) + 16 * n];
+                cb[n] = f6t_col(b.x, b.y, ep0.R2);
+            }
+            const F6qColMin cm = f6q_col_min(cb);
+            full0 = !f6t_quick_skip<kShared>(acc[0], ep0, sA, cb, cm, W6, wv);
+            full1 = !f6t_quick_skip<kShared>(acc[1], ep1, sA, cb, cm, W6, wv);
+            if ((full0 || full1) && ep0.lane == 0) atomicAdd(full, (uint32_t)full0 + (uint32_t)full1);
+        }
+        uint32_t lane = ep0.lane;
+        asm volatile("" : "+v"(lane), "+s"(wv)::"memory");
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int n = 0; n < 4; ++n) asm volatile("" : "+v"(acc[j][n][1][1]));
+        F6Epi e0 = ep0, e1 = ep1;
+        e0.lane = e1.lane = lane;
+        return (full0 && f6t_any_doubt<kShared>(acc[0], e0, sA, sB, W6, wv)) ||
+               (full1 && f6t_any_doubt<kShared>(acc[1], e1, sA, sB, W6, wv));
+    }
+    return f6t_any_doubt<kShared>(acc[0], ep0, sA, sB, W6, wv) ||
+           f6t_any_doubt<kShared>(acc[1], ep1, sA, sB, W6, wv);
+}
 }  // namespace
 
 // one 64x64 tile per 4-wave workgroup, four per CU (tile lists past 2^15
@@ -1431,7 +1509,13 @@ extern "C" int wld_debug_f6_clock(unsigned long long *out) {
 // every wave's last LDS read of the first pass: the second pass's first copy
 // is issued behind it, and no wave skips a barrier another reaches.  On C4
 // 5 of 24,649 entries take the second pass.
-template <int kFmt, bool kThree = false>
+// kQuick (with kThree; WLD_OPT_FP6_QUICK): each wave first tries to reject a
+// row block's pairs lane by lane on shared bounds (f6t_quick_skip), at half
+// the vector operations per pair, and runs the full three-sum test only for
+// the row blocks where some lane cannot (counted in sQuickFull, then by one
+// atomic per workgroup that has any).  The branch is wave-uniform and lies
+// between the same barriers.
+template <int kFmt, bool kThree = false, bool kQuick = false>
 __global__ __launch_bounds__(256, 3) void pair_fp6_screen2w_kernel(
     const uint8_t *__restrict__ a6, const uint8_t *__restrict__ b6, const float2 *__restrict__ marg, float W6,
     const uint64_t *__restrict__ ok_bits,
@@ -1444,6 +1528,8 @@ __global__ __launch_bounds__(256, 3) void pair_fp6_screen2w_kernel(
     __shared__ unsigned long long sMask[2];
     __shared__ uint32_t sBail, sCand[2];
     __shared__ uint32_t sDoubt[2];  // kThree: some pair of the half's tile is in doubt on three sums
+    __shared__ uint32_t sQuickFull;  // kQuick: the workgroup's row blocks that the quick test did not reject
+    static_assert(kThree || !kQuick, "the quick test stands in front of the three-sum test");
     if (!sc.probe && blockIdx.x == 0 && threadIdx.x == 0) *sc.cand_work = 0u;  // for the launch after it
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const uint32_t half = wave >> 1, rp = wave & 1, ltid = tid & 127;
@@ -1504,6 +1590,8 @@ __global__ __launch_bounds__(256, 3) void pair_fp6_screen2w_kernel(
         }
         if constexpr (kThree)
             if (tid < 2) sDoubt[tid] = 0u;  // (published by the first stage barrier, set after the loop)
+        if constexpr (kQuick)
+            if (tid == 2) sQuickFull = 0u;  // (likewise)
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         const uint64_t okA = ok_bits[ta], okB = ok_bits[tb];
         v4f acc[2][4][2][2];  // [row block 2 rp + j][b block n][channel_a][X, Y]
@@ -1584,12 +1672,17 @@ __global__ __launch_bounds__(256, 3) void pair_fp6_screen2w_kernel(
         const F6Epi ep1{ta, tb, 2 * rp + 1, lane, okA, okB, 2.0f * sc.Rf, thr * (1.0f - 0x1p-7f), sc.E, sc.mloc};
         if constexpr (kThree) {
             const float2 *sB = sMarg + kTile * (1 + half);
-            const bool doubt = !idle && (f6t_any_doubt<F::kShared>(acc[0], ep0, sMarg, sB, W6, wv) ||
-                                         f6t_any_doubt<F::kShared>(acc[1], ep1, sMarg, sB, W6, wv));
+            const bool doubt =
+                !idle && f6t_wave_doubt<F::kShared, kQuick>(acc, ep0, ep1, sMarg, sB, W6, wv, &sQuickFull);
             if (doubt) sDoubt[half] = 1u;  // (benign race: every writer stores 1)
             // every wave's LDS reads of the first pass lie before this barrier
             // (the last stage's wait, the marginals just read)
             __syncthreads();
+            if constexpr (kQuick) {
+                // (the second half of the rechecked word / the probe's fourth count)
+                unsigned *const cnt = sc.probe ? sc.probe + 3 : sc.rechecked ? sc.rechecked + 1 : nullptr;
+                if (tid == 0 && cnt && sQuickFull) atomicAdd(cnt, sQuickFull);
+            }
 #ifdef WLD_EXP_ZERO_IMG  // (every zero-image pair is in doubt: keep the reject path's work)
             const bool again = (sDoubt[0] | sDoubt[1]) == 0x5EEDu;
 #else
@@ -2007,7 +2100,13 @@ void fp6_screen_args(const MfmaLaunch &m, ScreenArgs &sc) {
 template <int kFmt>
 void launch_fp6_screen_fmt(const MfmaLaunch &m, const uint64_t *ok_bits, const OrderArgs &o, const ScreenArgs &sc,
                            uint32_t stride, hipStream_t s) {
-    if (m.f6_pairs && m.fp6_three) {
+    if (m.f6_pairs && m.fp6_three && m.fp6_quick) {
+        // (three sums per pair behind the lane-shared quick test)
+        hipLaunchKernelGGL((pair_fp6_screen2w_kernel<kFmt, true, true>), dim3((m.f6_n_pairs + stride - 1) / stride),
+                           dim3(256), 0, s, m.fp6->a6, m.fp6->b6, reinterpret_cast<const float2 *>(m.fp6->marg),
+                           m.fp6->W6, ok_bits, m.f6_pairs, m.f6_n_pairs, m.fp6->NK, m.L, m.n_chunk_rows, m.thr, o, sc,
+                           m.fp6->wv);
+    } else if (m.f6_pairs && m.fp6_three) {
         // (three sums per pair, the fourth where an entry needs it)
         hipLaunchKernelGGL((pair_fp6_screen2w_kernel<kFmt, true>), dim3((m.f6_n_pairs + stride - 1) / stride),
                            dim3(256), 0, s, m.fp6->a6, m.fp6->b6, reinterpret_cast<const float2 *>(m.fp6->marg),
@@ -2045,7 +2144,7 @@ void launch_fp6_probe(const MfmaLaunch &m, unsigned *probe, uint32_t stride, hip
     fp6_screen_args(m, sc);
     sc.probe = probe;
     sc.probe_stride = std::max<uint32_t>(stride, 1);
-    (void)hipMemsetAsync(probe, 0, 3 * sizeof(unsigned), s);
+    (void)hipMemsetAsync(probe, 0, 4 * sizeof(unsigned), s);
     launch_fp6_screen(m, ok_bits, OrderArgs{}, sc, sc.probe_stride, s);
 }
 

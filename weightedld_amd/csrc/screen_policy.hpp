@@ -63,6 +63,14 @@ constexpr uint32_t kSampleMinTiles = 2048;
 // it only where the sample run found the second pass on at most an eighth of
 // its entries: a cap well inside the break-even, not a tuned value.
 constexpr uint64_t kFp6ThreeKeep = 8;
+// The three-sum screen's quick test rejects a lane's 16 pairs of a row block
+// together at about half the full test's vector operations; a row block where
+// some lane cannot be rejected pays the quick test on top of the full one.  By
+// operation count it breaks even near 0.4 of the row blocks falling through;
+// auto takes it only where the sample run found at most a quarter.
+constexpr uint64_t kFp6QuickKeep = 4;
+// (a 64 x 64 tile is four row blocks of 16 sites)
+constexpr uint64_t kFp6RowBlocksPerTile = 4;
 
 // What the auto policy has learned on this load, window and option set.
 struct Learned {
@@ -84,6 +92,11 @@ struct Learned {
     // above the screen runs on three sums: a higher threshold leaves fewer
     // pairs in doubt)
     float fp6_three_good = INFINITY;
+    // the smallest threshold at which the sample run, on three sums with the
+    // quick test, found at most a quarter of its row blocks falling through to
+    // the full test (there and above the quick test runs: a higher threshold
+    // lets it reject more)
+    float fp6_quick_good = INFINITY;
 
     void reset() { *this = Learned{}; }
 };
@@ -95,6 +108,9 @@ struct Options {
     // WLD_OPT_FP6_THREE: 0 four sums, 1 auto (where a sample run allowed it),
     // 2 three sums wherever the tile-pair fp6 screen runs
     int fp6_three = 1;
+    // WLD_OPT_FP6_QUICK: 0 off, 1 auto (where a sample run allowed it), 2
+    // wherever the three-sum kernel runs
+    int fp6_quick = 1;
 };
 struct LoadFacts {
     bool mfma;            // the load runs on the integer kernel (WLD_KERNEL_MFMA)
@@ -125,6 +141,9 @@ struct Plan {
     // Fp6Screen on the tile-pair list: three masked sums per pair, the fourth
     // only for entries with a pair in doubt (the same candidates either way)
     bool fp6_three = false;
+    // ... with the lane-shared quick test in front of the three-sum test (the
+    // same verdicts either way)
+    bool fp6_quick = false;
 };
 
 // Whether a tile-pair fp6 screen at thr runs on three sums.  Auto needs a
@@ -134,6 +153,12 @@ struct Plan {
 static inline bool fp6_three(const Options &o, const PassFacts &p, const Learned &s) {
     if (!p.have_pairs) return false;
     return o.fp6_three == 2 || (o.fp6_three == 1 && p.thr >= s.fp6_three_good);
+}
+
+// Whether a screen on three sums runs the quick test first.  Auto needs a
+// sample run's word, as fp6_three: lists that are not sampled stay off.
+static inline bool fp6_quick(const Options &o, const PassFacts &p, const Learned &s) {
+    return o.fp6_quick == 2 || (o.fp6_quick == 1 && p.thr >= s.fp6_quick_good);
 }
 
 static inline Plan decide(const Options &o, const LoadFacts &l, const PassFacts &p, const Learned &s) {
@@ -169,6 +194,7 @@ static inline Plan decide(const Options &o, const LoadFacts &l, const PassFacts 
         if (l.fp6_ok && (o.fp6 == 2 || (fp6_auto && l.fp6_better && thr > s.fp6_bad))) {
             plan.route = Route::Fp6Screen;
             plan.fp6_three = fp6_three(o, p, s);
+            plan.fp6_quick = plan.fp6_three && fp6_quick(o, p, s);
             // auto: past a sixteenth of the tiles as candidates the fp6 screen
             // gives the pass up and the pass is re-run on the i8 screen (not
             // with per-chunk progress, which a re-run does not report again,
@@ -228,11 +254,15 @@ static inline bool wants_sample(Options o, const LoadFacts &l, PassFacts p, cons
 // not 0) and `rechecked` of its entries took the second pass.  An entry holds
 // at most two tiles, so (sampled + 1) / 2 is a lower bound of the sampled
 // entries: the eighth is taken of that.
+// quick: the sample ran the quick test as well (WLD_OPT_FP6_QUICK not 0) and
+// `quick_full` of its 4 x sampled row blocks fell through to the full test.
 struct Sample {
     float thr;
     uint64_t candidates, sampled;
     bool three = false;
     uint64_t rechecked = 0;
+    bool quick = false;
+    uint64_t quick_full = 0;
 };
 static inline void learn(Learned &s, const Sample &r) {
     if (r.candidates * kFp6Keep > r.sampled) {
@@ -242,6 +272,8 @@ static inline void learn(Learned &s, const Sample &r) {
     s.fp6_good = std::min(s.fp6_good, r.thr);
     if (r.three && r.sampled && r.rechecked * kFp6ThreeKeep <= (r.sampled + 1) / 2)
         s.fp6_three_good = std::min(s.fp6_three_good, r.thr);
+    if (r.three && r.quick && r.sampled && r.quick_full * kFp6QuickKeep <= r.sampled * kFp6RowBlocksPerTile)
+        s.fp6_quick_good = std::min(s.fp6_quick_good, r.thr);
 }
 
 // A completed pass.
@@ -287,6 +319,8 @@ static inline int stat_screened(Route r) {
 static inline int stat_screen_fp6(Route r) { return r == Route::Fp6Screen ? 1 : 0; }
 // wld_run_stats.fp6_three of a pass that was not given up
 static inline int stat_fp6_three(const Plan &p) { return p.route == Route::Fp6Screen && p.fp6_three ? 1 : 0; }
+// wld_run_stats.fp6_quick of a pass that was not given up
+static inline int stat_fp6_quick(const Plan &p) { return stat_fp6_three(p) && p.fp6_quick ? 1 : 0; }
 // wld_run_stats.pair_kernel_launches of a pass with tiles (exact candidate
 // pairs: the i8 pass, ref_sums_kernel, ref_compact_kernel)
 static inline int stat_launches(Route r) { return r == Route::CandidatePairs ? 3 : ran_screen(r) ? 2 : 1; }
