@@ -295,6 +295,10 @@ int wld_set_kernel(wld_ctx *ctx, int kernel);
  *                      one batch may use (default 2^30; a batch always holds at
  *                      least one tile).  Changes no bit of a result; it exists
  *                      to bound memory and so tests can force several batches.
+ *   WLD_OPT_MATRIX_BATCH_BYTES  wld_run_matrix: the bytes of the device buffer
+ *                      one band of whole rows may use (default 2^30; a band
+ *                      always holds at least 64 rows).  Changes no byte of a
+ *                      result; it bounds memory and lets tests force bands.
  *   WLD_OPT_TEST_GUARD 0 (default); 1 (tests only): before each candidate
  *                      launch the last candidate bucket's count is set one
  *                      past its capacity, so the launch meets an entry outside
@@ -323,6 +327,7 @@ int wld_set_kernel(wld_ctx *ctx, int kernel);
 #define WLD_OPT_PARTNERS_BATCH_BYTES 20
 #define WLD_OPT_FP6_THREE 21
 #define WLD_OPT_FP6_QUICK 22
+#define WLD_OPT_MATRIX_BATCH_BYTES 23
 int wld_set_option(wld_ctx *ctx, int option, int64_t value);
 int wld_get_option(wld_ctx *ctx, int option, int64_t *value);
 
@@ -809,6 +814,86 @@ int wld_run_annot_scores(wld_ctx *ctx, const float *annot /* n_sites*n_annot, ro
                          int flags, uint32_t chunk_begin, uint32_t chunk_end, wld_annot_scores *out);
 int wld_annot_scores_merge(wld_annot_scores *into, const wld_annot_scores *from);
 void wld_annot_scores_free(wld_annot_scores *s);
+
+/* ---- LD matrix: dense r, r2, D or D' of a site rectangle (not in the
+ * reference; PLINK's --r square / --r2 square, LDstore, LDlink's LDmatrix: what
+ * fine-mapping, summary-statistic imputation, conditional analysis and PRS
+ * samplers start from) ----
+ *
+ * Rectangle.  Rows [row_begin,row_end) and columns [col_begin,col_end) are
+ * LOADED site indices (wld_loaded_sites); an end of 0 means the loaded site
+ * count.  Entry (i, j) is dst[i * ld + j] (ld in elements, >= the width) and
+ * belongs to the sites u = row_begin + i, v = col_begin + j.  The rectangle may
+ * lie above, below or across the diagonal and need not be aligned to anything.
+ *
+ * Off the diagonal, with a = min(u, v), b = max(u, v):
+ *   * pair (a, b) in the context's window (wld_set_window; none: every pair):
+ *     the value is computed from the f32 d, d', r2 that the default row path
+ *     (WLD_OPT_REF_SUMS 1) puts in the row of pair (a, b), bit for bit.  Pair
+ *     (b, a) is never evaluated (the row path's f32 values are not symmetric
+ *     in their arguments): entries (u, v) and (v, u) hold the same bits.
+ *       WLD_MATRIX_R2, _D, _DPRIME   that r2, d, d';
+ *       WLD_MATRIX_R   s = sqrtf(r2), correctly rounded, r = (d > 0) ? -s : s.
+ *     d carries the REFERENCE's sign, expected minus observed (lib.rs:502),
+ *     the opposite of the textbook D; WLD_MATRIX_R undoes that: r is the
+ *     weighted Pearson correlation of the two sites' major-allele indicators
+ *     over the sequences in the pair's mask (both sites major or minor).
+ *     WLD_MATRIX_D and _DPRIME keep the reference's sign.  r2 is not clamped:
+ *     rounding can leave it a few ulps above 1 (1.0000001), and r with it.
+ *   * a none pair (a site without a major or a minor symbol): NaN;
+ *   * a nonfinite pair: what the arithmetic gave (NaN or +-inf);
+ *   * out of the window: +0.0 (the matrix is banded).
+ * On the diagonal: 1.0 for _R2 and _R where the site has a major and a minor
+ * symbol, NaN otherwise; NaN for _D and _DPRIME.
+ * WLD_MATRIX_ZERO_MISSING (flags): every entry that would be NaN or +-inf
+ * becomes +0.0, except the _R / _R2 diagonal, which becomes 1.0.
+ * WLD_MATRIX_F16: the f32 value rounded to nearest-even to IEEE binary16,
+ * subnormal results kept (numpy's astype(float16)).
+ *
+ * Info.  pairs, none_pairs, nonfinite_pairs, counted_pairs: the distinct pairs
+ * a < b in the window with an entry in the rectangle — a pair with both
+ * orientations inside counts once — classified as wld_run_summary classifies
+ * them (by r2); for the full square they equal the summary's for the same
+ * window.  tiles: the 64x64 tiles launched.  kernel_ms: HIP-event time of the
+ * fill and pair launches (wld_run_matrix: summed over its bands).
+ *
+ * Every element inside the rectangle is written; nothing outside it is
+ * touched, the ld - width elements between rows included.  No value goes
+ * through an atomic: two calls give identical bytes.
+ *
+ * wld_run_matrix_device: d_dst is device memory of the context's device (a
+ * torch tensor's, say); the call returns after its work has completed.
+ * wld_run_matrix: h_dst is host memory, written through bands of whole rows
+ * from a device buffer the call owns, at most WLD_OPT_MATRIX_BATCH_BYTES
+ * (tiles whose two images fall into different bands are computed once per
+ * band).  WLD_OPT_REF_SUMS, the kernel choice and the screen options do not
+ * apply.
+ *
+ * WLD_E_ARG: an empty or out-of-range rectangle; an unknown stat, dtype or
+ * flag bit; ld below the width; a null destination; non-finite weights (a load
+ * that takes the row path's select loop).  WLD_E_STATE: before a load, while a
+ * run is in flight, on a device group.  WLD_E_OOM leaves the context usable.
+ * The calls keep their tile lists, counters and events to themselves:
+ * wld_last_stats, the last run's rows and the row path's cached tile list stay
+ * as they were. */
+#define WLD_MATRIX_R2 0
+#define WLD_MATRIX_R 1 /* signed */
+#define WLD_MATRIX_D 2
+#define WLD_MATRIX_DPRIME 3
+#define WLD_MATRIX_F32 0
+#define WLD_MATRIX_F16 1
+#define WLD_MATRIX_ZERO_MISSING 1 /* flags */
+typedef struct {
+    uint32_t row_begin, row_end, col_begin, col_end; /* as resolved */
+    int stat, dtype, flags;
+    uint64_t pairs, none_pairs, nonfinite_pairs, counted_pairs;
+    uint64_t tiles;   /* 64x64 tiles launched */
+    double kernel_ms; /* HIP-event time of the launches */
+} wld_matrix_info;
+int wld_run_matrix_device(wld_ctx *ctx, uint32_t row_begin, uint32_t row_end, uint32_t col_begin, uint32_t col_end,
+                          int stat, int dtype, int flags, void *d_dst, size_t ld /* elements */, wld_matrix_info *out);
+int wld_run_matrix(wld_ctx *ctx, uint32_t row_begin, uint32_t row_end, uint32_t col_begin, uint32_t col_end, int stat,
+                   int dtype, int flags, void *h_dst, size_t ld /* elements */, wld_matrix_info *out);
 
 /* ---- LD pruning: a greedy r2-independent site set with tags (not in the
  * reference; PLINK's --indep-pairwise, bcftools +prune) ----

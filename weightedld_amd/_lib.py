@@ -28,7 +28,7 @@ OPTIONS = {"prefilter": 1, "screen": 2, "tile_order": 3, "all_planes": 4, "mfma_
            "staging_rows": 7, "host_batch_pairs": 8, "ref_sums": 11, "fused_scan": 12, "screen_fp6": 13,
            "test_guard": 14, "fp6_pairs_min_tiles": 15, "i8_pairs": 16, "fp6_a4": 17,
            "target_batch_slots": 18, "fp6_shared": 19, "partners_batch_bytes": 20, "fp6_three": 21,
-           "fp6_quick": 22}
+           "fp6_quick": 22, "matrix_batch_bytes": 23}
 
 
 class WldError(RuntimeError):
@@ -130,6 +130,28 @@ class AnnotScoresC(ctypes.Structure):
         ("counted_pairs", ctypes.c_uint64),
         ("score", ctypes.POINTER(ctypes.c_double)),
         ("partners", ctypes.POINTER(ctypes.c_uint32)),
+        ("tiles", ctypes.c_uint64),
+        ("kernel_ms", ctypes.c_double),
+    ]
+
+
+MATRIX_STATS = {"r2": 0, "r": 1, "d": 2, "dprime": 3}  # WLD_MATRIX_*
+MATRIX_F32, MATRIX_F16, MATRIX_ZERO_MISSING = 0, 1, 1
+
+
+class MatrixInfoC(ctypes.Structure):
+    _fields_ = [
+        ("row_begin", ctypes.c_uint32),
+        ("row_end", ctypes.c_uint32),
+        ("col_begin", ctypes.c_uint32),
+        ("col_end", ctypes.c_uint32),
+        ("stat", ctypes.c_int),
+        ("dtype", ctypes.c_int),
+        ("flags", ctypes.c_int),
+        ("pairs", ctypes.c_uint64),
+        ("none_pairs", ctypes.c_uint64),
+        ("nonfinite_pairs", ctypes.c_uint64),
+        ("counted_pairs", ctypes.c_uint64),
         ("tiles", ctypes.c_uint64),
         ("kernel_ms", ctypes.c_double),
     ]
@@ -318,6 +340,10 @@ SIGNATURES = {
                                     ctypes.c_uint32, ctypes.POINTER(AnnotScoresC)]),
     "wld_annot_scores_merge": (_int, [ctypes.POINTER(AnnotScoresC), ctypes.POINTER(AnnotScoresC)]),
     "wld_annot_scores_free": (None, [ctypes.POINTER(AnnotScoresC)]),
+    "wld_run_matrix_device": (_int, [_vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _int, _int,
+                                     _int, _vp, _sz, ctypes.POINTER(MatrixInfoC)]),
+    "wld_run_matrix": (_int, [_vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _int, _int, _int,
+                              _vp, _sz, ctypes.POINTER(MatrixInfoC)]),
     "wld_run_prune": (_int, [_vp, ctypes.c_float, _f32p, ctypes.POINTER(Prune)]),
     "wld_prune_free": (None, [ctypes.POINTER(Prune)]),
     "wld_loaded_sites": (_sz, [_vp]),

@@ -14,14 +14,15 @@ from collections import namedtuple
 import numpy as np
 
 from ._lib import (ANNOT_MAX, ANNOT_SELF, AnnotScoresC, BLOCKS_ABS_DPRIME, BLOCKS_ALL, BLOCKS_NONE, BLOCKS_R2, BLOCKS_SPINE, BlockBreaksC, BlocksC,
-                   HEAT_ABS_DPRIME, HEAT_MAX_CELLS, HEAT_R2, KERNEL_AUTO, KERNEL_MFMA, KERNEL_VALU, OPTIONS,
+                   HEAT_ABS_DPRIME, HEAT_MAX_CELLS, HEAT_R2, KERNEL_AUTO, KERNEL_MFMA, KERNEL_VALU, MATRIX_F16, MATRIX_F32,
+                   MATRIX_STATS, MATRIX_ZERO_MISSING, MatrixInfoC, OPTIONS,
                    PARTNERS_MAX_K, PARTNERS_NONE, PROGRESS_FN, Heatmap, Pairs, PartnersC, Prune, RunStats, Summary,
                    TargetRowsC, WldError, check, lib)
 
 __all__ = [
     "Symbol", "SymbolHistogram", "SiteSet", "LdStats", "PairStore", "read_fasta", "read_vcf",
     "is_site_of_interest", "henikoff_weights", "single_weighted_ld_pair", "all_weighted_ld_pairs",
-    "ld_summary", "LdSummary", "ld_heatmap", "LdHeatmap", "heatmap_cells", "ld_annot_scores", "LdAnnotScores", "annot_matrix", "ANNOT_MAX", "ld_prune", "LdPrune", "maf_priority", "ld_targets", "TargetRows", "ld_partners", "LdPartners", "PARTNERS_MAX_K", "PARTNERS_NONE", "ld_blocks", "LdBlocks", "LdBlockBreaks", "BLOCKS_NONE", "Context", "default_context", "KERNEL_AUTO", "KERNEL_VALU", "KERNEL_MFMA", "OPTIONS", "WldError",
+    "ld_summary", "LdSummary", "ld_heatmap", "LdHeatmap", "heatmap_cells", "ld_annot_scores", "LdAnnotScores", "annot_matrix", "ANNOT_MAX", "ld_matrix", "LdMatrixInfo", "matrix_args", "matrix_region", "ld_prune", "LdPrune", "maf_priority", "ld_targets", "TargetRows", "ld_partners", "LdPartners", "PARTNERS_MAX_K", "PARTNERS_NONE", "ld_blocks", "LdBlocks", "LdBlockBreaks", "BLOCKS_NONE", "Context", "default_context", "KERNEL_AUTO", "KERNEL_VALU", "KERNEL_MFMA", "OPTIONS", "WldError",
 ]
 
 
@@ -285,6 +286,88 @@ class LdAnnotScores:
         self.partners = self.partners + other.partners
         self.kernel_ms = max(self.kernel_ms, other.kernel_ms)
         return self
+
+
+LdMatrixInfo = namedtuple("LdMatrixInfo", ["rows", "cols", "stat", "dtype", "zero_missing", "pairs", "none_pairs",
+                                           "nonfinite_pairs", "counted_pairs", "tiles", "kernel_ms"])
+LdMatrixInfo.__doc__ = """wld_matrix_info (Context.run_matrix, ld_matrix): rows and cols, the (begin, end)
+loaded-site ranges of the rectangle as resolved; stat ("r2", "r", "d", "dprime"), dtype ("float32", "float16"),
+zero_missing; the class counts of the distinct in-window pairs with an entry in the rectangle; the 64x64 tiles
+launched and kernel_ms.  From ld_matrix also sites, the parent coordinates of the rows."""
+
+_MATRIX_DTYPES = {"float32": MATRIX_F32, "float16": MATRIX_F16}
+
+
+def _site_range(x, n_sites, what):
+    if x is None:
+        return 0, int(n_sites)
+    try:
+        b, e = int(x[0]), int(x[1])
+    except (TypeError, IndexError, ValueError):
+        raise ValueError("%s must be None or a (begin, end) pair of loaded site indices" % what)
+    if len(x) != 2 or b < 0 or e <= b or e > int(n_sites):
+        raise ValueError("%s [%d, %d) must be a non-empty range within the %d loaded sites" % (what, b, e, int(n_sites)))
+    return b, e
+
+
+def matrix_args(n_sites, rows=None, cols=None, stat="r", dtype="float32", out=None):
+    """Context.run_matrix's arguments checked before any device call: returns
+    (rows, cols, stat id, dtype id, kind, ld) with rows / cols resolved (begin,
+    end) pairs, kind None (no out), "numpy" or "device", and ld the row stride
+    of out in elements (the width without out).  ValueError on anything the
+    call would refuse: a range outside the n_sites loaded sites, an unknown
+    stat or dtype, an out of the wrong shape, dtype, strides or device kind."""
+    rows, cols = _site_range(rows, n_sites, "rows"), _site_range(cols, n_sites, "cols")
+    if stat not in MATRIX_STATS:
+        raise ValueError("stat must be one of %s" % ", ".join('"%s"' % k for k in MATRIX_STATS))
+    name = np.dtype(dtype).name if not isinstance(dtype, str) else dtype
+    if name not in _MATRIX_DTYPES:
+        raise ValueError('dtype must be "float32" or "float16"')
+    shape = (rows[1] - rows[0], cols[1] - cols[0])
+    if out is None:
+        return rows, cols, MATRIX_STATS[stat], _MATRIX_DTYPES[name], None, shape[1]
+    if isinstance(out, np.ndarray):
+        kind, oname, strides = "numpy", out.dtype.name, tuple(x // out.itemsize if x % out.itemsize == 0 else -1
+                                                               for x in out.strides)
+        if not out.flags.writeable:
+            raise ValueError("out is read-only")
+    elif all(hasattr(out, a) for a in ("data_ptr", "stride", "dtype", "shape", "device")):
+        kind, oname, strides = "device", str(out.dtype).replace("torch.", ""), tuple(int(x) for x in out.stride())
+        if getattr(out.device, "type", "") != "cuda":
+            raise ValueError("a tensor out must be on the context's GPU, not on %s" % (out.device,))
+    else:
+        raise ValueError("out must be a numpy array or a device tensor (data_ptr, stride, dtype, shape, device)")
+    if tuple(int(x) for x in out.shape) != shape:
+        raise ValueError("out has shape %s; the rectangle is %s" % (tuple(out.shape), shape))
+    if oname != name:
+        raise ValueError("out has dtype %s; dtype is %s" % (oname, name))
+    if strides[1] != 1 and shape[1] > 1:
+        raise ValueError("out must have contiguous rows (last stride 1)")
+    if strides[0] < shape[1] and shape[0] > 1:
+        raise ValueError("out's row stride %d is below the width %d" % (strides[0], shape[1]))
+    return rows, cols, MATRIX_STATS[stat], _MATRIX_DTYPES[name], kind, max(strides[0], shape[1])
+
+
+def matrix_region(site_map, n_sites, region):
+    """The loaded-site range [begin, end) of region = (start, stop), parent
+    coordinates, start <= pos < stop (heatmap_cells' rule; site_map None:
+    coordinate = site index).  ValueError: a malformed or empty region, or a
+    site_map that descends (the region's sites would not be one range)."""
+    pos = np.arange(int(n_sites), dtype=np.int64) if site_map is None else np.asarray(site_map).astype(np.int64).reshape(-1)
+    if pos.size != int(n_sites):
+        raise ValueError("site_map has %d entries for %d sites" % (pos.size, int(n_sites)))
+    try:
+        start, stop = int(region[0]), int(region[1])
+    except (TypeError, IndexError, ValueError):
+        raise ValueError("region must be (start, stop)")
+    if len(region) != 2 or start < 0 or stop < start:
+        raise ValueError("region must be (start, stop) with 0 <= start <= stop")
+    if np.any(np.diff(pos) < 0):
+        raise ValueError("a region needs a non-decreasing site_map")
+    b, e = int(np.searchsorted(pos, start, side="left")), int(np.searchsorted(pos, stop, side="left"))
+    if e <= b:
+        raise ValueError("no site lies in the region [%d, %d)" % (start, stop))
+    return b, e
 
 
 def annot_matrix(annot, n_sites=None):
@@ -945,6 +1028,47 @@ class Context:
         lib().wld_annot_scores_free(ctypes.byref(out))
         return res
 
+    def run_matrix(self, rows=None, cols=None, stat="r", dtype="float32", zero_missing=False, out=None):
+        """wld_run_matrix / wld_run_matrix_device: the dense LD matrix of the
+        loaded-site rectangle rows x cols ((begin, end) pairs; None: every
+        site) under the context's window: stat "r" (signed: the weighted
+        correlation of the major-allele indicators), "r2", "d" or "dprime" (the
+        reference's sign), float32 or float16, symmetric bit for bit, +0.0 out
+        of the window, NaN for pairs without a value (zero_missing: 0.0, and
+        1.0 on the r / r2 diagonal).  Without out: returns (numpy array,
+        LdMatrixInfo).  out a numpy array (C-contiguous rows; a row stride is
+        kept): filled through the host call.  out a device tensor (data_ptr,
+        stride, dtype, shape, device — a torch tensor on the context's GPU,
+        last stride 1): filled in place on the device; its pending work is
+        synchronised first.  With out: returns (out, LdMatrixInfo).  Shape,
+        dtype and range mismatches raise ValueError before any device call."""
+        n = int(lib().wld_loaded_sites(self._h))
+        if not n:
+            check(lib().wld_run_matrix(self._h, 0, 0, 0, 0, 0, 0, 0, None, 0, ctypes.byref(MatrixInfoC())),
+                  "wld_run_matrix")  # (not loaded: the library's own refusal)
+        rows, cols, st, dt, kind, ld = matrix_args(n, rows, cols, stat, dtype, out)
+        flags = MATRIX_ZERO_MISSING if zero_missing else 0
+        info = MatrixInfoC()
+        if kind is None:
+            out = np.empty((rows[1] - rows[0], cols[1] - cols[0]), dtype=np.float16 if dt == MATRIX_F16 else np.float32)
+            kind = "numpy"
+        if kind == "numpy":
+            check(lib().wld_run_matrix(self._h, rows[0], rows[1], cols[0], cols[1], st, dt, flags,
+                                       ctypes.c_void_p(out.ctypes.data), ld, ctypes.byref(info)), "wld_run_matrix")
+        else:
+            import torch  # (only here: a device tensor was passed)
+            if out.device.index is not None and out.device.index != self.device:
+                raise ValueError("out is on device %d; the context runs on %d" % (out.device.index, self.device))
+            torch.cuda.synchronize(out.device)
+            check(lib().wld_run_matrix_device(self._h, rows[0], rows[1], cols[0], cols[1], st, dt, flags,
+                                              ctypes.c_void_p(int(out.data_ptr())), ld, ctypes.byref(info)),
+                  "wld_run_matrix_device")
+        return out, LdMatrixInfo(rows=(int(info.row_begin), int(info.row_end)), cols=(int(info.col_begin), int(info.col_end)),
+                                 stat=stat, dtype="float16" if dt == MATRIX_F16 else "float32",
+                                 zero_missing=bool(zero_missing), pairs=int(info.pairs), none_pairs=int(info.none_pairs),
+                                 nonfinite_pairs=int(info.nonfinite_pairs), counted_pairs=int(info.counted_pairs),
+                                 tiles=int(info.tiles), kernel_ms=float(info.kernel_ms))
+
     def run_partners(self, k, r2_threshold, chunk_begin=0, chunk_end=0):
         """wld_run_partners: for every LOADED site its best k partners (r2 >
         r2_threshold, r2 descending then partner ascending) among the pairs of
@@ -1278,6 +1402,36 @@ def ld_annot_scores(site_set, weights, annot, self_term=False, names=None, max_d
         ctx.set_window(*before)
     res.names = names
     return res
+
+
+def ld_matrix(site_set, weights, region=None, stat="r", dtype="float32", zero_missing=False, max_distance=None,
+              max_sites=None, out=None, ctx=None):
+    """The LD matrix of site_set (not in the reference; PLINK's --r square,
+    LDstore, LDlink's LDmatrix): loads the set and runs Context.run_matrix on
+    the square of the sites in region = (start, stop), parent coordinates,
+    start <= pos < stop (None: every site), under the window max_distance /
+    max_sites (the context's own window is restored afterwards).  Returns
+    (matrix, info, sites): the matrix (or out), its LdMatrixInfo and the parent
+    coordinates of its rows and columns."""
+    w = np.ascontiguousarray(weights, dtype=np.float32)
+    if w.size != site_set.n_seqs():
+        raise ValueError("weights must have n_seqs entries")
+    n = site_set.n_sites()
+    sq = (0, n) if region is None else matrix_region(site_set.site_map, n, region)
+    matrix_args(n, sq, sq, stat, dtype, out)  # (every refusal before the load)
+    ctx = ctx or default_context()
+    before = ctx.window()
+    if max_distance is not None or max_sites is not None:
+        ctx.set_window(max_distance, max_sites)
+    try:
+        ctx.load(site_set.buffer, w, site_set.site_map)
+        m, info = ctx.run_matrix(sq, sq, stat, dtype, zero_missing, out)
+    finally:
+        ctx.set_window(*before)
+    sm = site_set.site_map
+    sites = (np.arange(sq[0], sq[1], dtype=np.uint64) if sm is None
+             else np.asarray(sm, dtype=np.uint64)[sq[0]:sq[1]].copy())
+    return m, info, sites
 
 
 def ld_prune(site_set, weights, r2_threshold, priority=None, max_distance=None, max_sites=None, ctx=None):

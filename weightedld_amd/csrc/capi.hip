@@ -27,6 +27,7 @@
 #include "summary_plan.hpp"
 #include "heatmap_plan.hpp"
 #include "annot_plan.hpp"
+#include "matrix_plan.hpp"
 #include "blocks_plan.hpp"
 #include "partners_plan.hpp"
 #include "prune_plan.hpp"
@@ -144,6 +145,7 @@ struct wld_ctx {
     uint64_t opt_staging_rows = 1ull << 25, opt_host_batch_pairs = 1ull << 31;
     uint64_t opt_target_slots = targets_plan::kDefaultBatchSlots;  // WLD_OPT_TARGET_BATCH_SLOTS
     uint64_t opt_partners_bytes = partners_plan::kDefaultBatchBytes;  // WLD_OPT_PARTNERS_BATCH_BYTES
+    uint64_t opt_matrix_bytes = matrix_plan::kDefaultBatchBytes;      // WLD_OPT_MATRIX_BATCH_BYTES
 
     // loaded SiteSet
     bool loaded = false;
@@ -248,6 +250,12 @@ struct wld_ctx {
     DevBuf an_buf, an_tiles, an_img;
     hipEvent_t ev_an[2] = {};
 
+    // wld_run_matrix_device / wld_run_matrix: the tile list and fill list of
+    // a band, the four class counts, and the two events around a band's
+    // launches (the host call's band buffer lives for the call only)
+    DevBuf mx_lists, mx_cnt;
+    hipEvent_t ev_mx[2] = {};
+
     // wld_run_partners: its own tile list, a batch's staging (entries and
     // counts), the batch's CSR, the running lists and the words {classes[3],
     // guard}; its events are created per call
@@ -289,7 +297,7 @@ struct wld_ctx {
         // buffers: it completes before they are freed
         if (stream && stream != own_stream) (void)hipStreamSynchronize(stream);
         DevBuf *all[] = {&keep, &htab, &htab_kept, &site_index, &raw, &wraw, &codes, &w_pad, &wstats, &site_ok, &site_map, &planes, &frag, &rcodes, &rw, &w6, &w4, &f6a, &f6b, &f6marg, &i8a, &i8b, &tiles, &cand, &f6_pairs, &fp6_probe_buf,
-                         &seg_cnt, &seg_off, &chunk_total, &chunk_base, &counters, &chunk_left, &prog_n, &win_hi, &win_pairs, &sum_buf, &heat_buf, &heat_tiles, &heat_map, &an_buf, &an_tiles, &an_img, &pt_tiles, &pt_stage, &pt_cnt, &pt_csr, &pt_run, &pt_words, &blk_brk, &blk_acc, &blk_map, &blk_tiles, &st_a, &st_b, &st_d,
+                         &seg_cnt, &seg_off, &chunk_total, &chunk_base, &counters, &chunk_left, &prog_n, &win_hi, &win_pairs, &sum_buf, &heat_buf, &heat_tiles, &heat_map, &an_buf, &an_tiles, &an_img, &mx_lists, &mx_cnt, &pt_tiles, &pt_stage, &pt_cnt, &pt_csr, &pt_run, &pt_words, &blk_brk, &blk_acc, &blk_map, &blk_tiles, &st_a, &st_b, &st_d,
                          &st_dp, &st_r2, &out_a, &out_b, &out_d, &out_dp, &out_r2};
         for (DevBuf *b : all) release(*b);
         for (DevBuf *b : tg.all()) release(*b);
@@ -302,6 +310,8 @@ struct wld_ctx {
         for (auto &e : ev_heat)
             if (e) (void)hipEventDestroy(e);
         for (auto &e : ev_an)
+            if (e) (void)hipEventDestroy(e);
+        for (auto &e : ev_mx)
             if (e) (void)hipEventDestroy(e);
         for (auto &e : ev_blk)
             if (e) (void)hipEventDestroy(e);
@@ -1062,6 +1072,10 @@ int wld_set_option(wld_ctx *c, int option, int64_t value) {
             if (value < 1) return fail(WLD_E_ARG, "WLD_OPT_PARTNERS_BATCH_BYTES must be >= 1");
             c->opt_partners_bytes = (uint64_t)value;
             break;
+        case WLD_OPT_MATRIX_BATCH_BYTES:
+            if (value < 1) return fail(WLD_E_ARG, "WLD_OPT_MATRIX_BATCH_BYTES must be >= 1");
+            c->opt_matrix_bytes = (uint64_t)value;
+            break;
         case WLD_OPT_FUSED_SCAN: c->opt_fused_scan = value != 0; break;
         case WLD_OPT_I8_PAIRS: c->opt_i8_pairs = value != 0; break;
         case WLD_OPT_TEST_GUARD: c->opt_test_guard = value != 0; break;
@@ -1203,6 +1217,7 @@ int wld_get_option(wld_ctx *c, int option, int64_t *value) {
         case WLD_OPT_HOST_BATCH_PAIRS: *value = (int64_t)c->opt_host_batch_pairs; break;
         case WLD_OPT_TARGET_BATCH_SLOTS: *value = (int64_t)c->opt_target_slots; break;
         case WLD_OPT_PARTNERS_BATCH_BYTES: *value = (int64_t)c->opt_partners_bytes; break;
+        case WLD_OPT_MATRIX_BATCH_BYTES: *value = (int64_t)c->opt_matrix_bytes; break;
         case WLD_OPT_FUSED_SCAN: *value = c->opt_fused_scan; break;
         case WLD_OPT_TEST_GUARD: *value = c->opt_test_guard; break;
         case WLD_OPT_FP6_PAIRS_MIN_TILES: *value = c->opt_fp6_pairs_min; break;
@@ -2725,6 +2740,158 @@ void wld_annot_scores_free(wld_annot_scores *s) {
     memset(s, 0, sizeof(*s));
 }
 
+
+namespace {
+static_assert(WLD_MATRIX_R2 == matrix_plan::kStatR2 && WLD_MATRIX_R == matrix_plan::kStatR &&
+                  WLD_MATRIX_D == matrix_plan::kStatD && WLD_MATRIX_DPRIME == matrix_plan::kStatDPrime &&
+                  WLD_MATRIX_F32 == matrix_plan::kF32 && WLD_MATRIX_F16 == matrix_plan::kF16 &&
+                  WLD_MATRIX_ZERO_MISSING == matrix_plan::kZeroMissing,
+              "matrix_plan.hpp restates the header's constants");
+
+// What the matrix calls refuse, in the contract's order: the state, then the
+// arguments (matrix_plan::validate), then the load's weights.  *q: the
+// rectangle with its ends resolved.
+int matrix_check(wld_ctx *c, const char *who, uint32_t rb, uint32_t re, uint32_t cb, uint32_t ce, int stat, int dtype,
+                 int flags, const void *dst, size_t ld, matrix_plan::Rect *q) {
+    WLD_TRY(set_dev(c));
+    if (!c->loaded) return fail(WLD_E_STATE, "%s before wld_load", who);
+    if (c->pend.active) return fail(WLD_E_STATE, "%s during a run", who);
+    switch (matrix_plan::validate(c->L, rb, re, cb, ce, stat, dtype, flags, ld, dst != nullptr, q)) {
+        case matrix_plan::kOk: break;
+        case matrix_plan::kStat: return fail(WLD_E_ARG, "%s: unknown stat %d", who, stat);
+        case matrix_plan::kDtype: return fail(WLD_E_ARG, "%s: unknown dtype %d", who, dtype);
+        case matrix_plan::kFlags: return fail(WLD_E_ARG, "%s: unknown flags 0x%x", who, (unsigned)flags);
+        case matrix_plan::kNull: return fail(WLD_E_ARG, "%s: null destination", who);
+        case matrix_plan::kRange:
+            return fail(WLD_E_ARG, "%s: rows [%u,%u) x columns [%u,%u) exceed the %zu loaded sites", who, rb, re, cb, ce,
+                        c->L);
+        case matrix_plan::kEmpty:
+            return fail(WLD_E_ARG, "%s: rows [%u,%u) x columns [%u,%u) hold no entry", who, rb, re, cb, ce);
+        case matrix_plan::kLd:
+            return fail(WLD_E_ARG, "%s: ld %zu is below the rectangle's width %u", who, ld, q->c1 - q->c0);
+    }
+    if (c->safe) return fail(WLD_E_ARG, "%s needs finite weights (this load takes the select loop)", who);
+    if (window_on(c) && c->win_hi_host.size() != c->L) return fail(WLD_E_STATE, "internal: the window has no plan");
+    return WLD_OK;
+}
+
+void matrix_info_init(wld_matrix_info *out, const matrix_plan::Rect &q, int stat, int dtype, int flags) {
+    memset(out, 0, sizeof(*out));
+    out->row_begin = q.r0, out->row_end = q.r1, out->col_begin = q.c0, out->col_end = q.c1;
+    out->stat = stat, out->dtype = dtype, out->flags = flags;
+}
+
+// One band of the call's rectangle into device memory (d_dst: the element of
+// entry (band.r0, band.c0)): the band's tile and fill lists in buffers of the
+// matrix calls' own, zeroed class counts, the fill and pair launches, the
+// counts back; returns after the work has completed, its counts, tiles and
+// time added to *out.  Touches no staging, segment count, chunk total, run
+// counter, cached tile list or row-path event.
+int matrix_band(wld_ctx *c, const matrix_plan::Rect &full, const matrix_plan::Rect &band, int stat, int dtype,
+                int flags, void *d_dst, size_t ld, wld_matrix_info *out) {
+    const size_t L = c->L, LP = c->LP;
+    const bool windowed = window_on(c);
+    matrix_plan::Plan p;
+    try {
+        p = matrix_plan::plan((uint32_t)L, windowed ? c->win_hi_host.data() : nullptr, band);
+        const uint32_t T_used = (uint32_t)((L + kTile - 1) / kTile);
+        out->tiles += p.tiles.size();
+        if (!c->opt_tile_rows && p.tiles.size() >= 4096 && T_used < 65535)
+            p.tiles = xcd_order(p.tiles, tile_order::super_block_side((uint32_t)c->NP));
+    } catch (const std::bad_alloc &) {
+        return fail(WLD_E_OOM, "host allocation of the matrix's tile list failed");
+    }
+    const size_t nt = p.tiles.size(), nf = p.fill.size();
+    if (nt) WLD_TRY(ensure_ref_layout(c));
+    for (auto &e : c->ev_mx)
+        if (!e) HIP_TRY(hipEventCreate(&e));
+    WLD_TRY(ensure(c->mx_lists, (nt + nf) * sizeof(uint32_t)));
+    WLD_TRY(ensure(c->mx_cnt, 4 * sizeof(unsigned long long)));
+    uint32_t *d_tiles = ptr<uint32_t>(c->mx_lists), *d_fill = d_tiles + nt;
+    if (nt) HIP_TRY(hipMemcpyAsync(d_tiles, p.tiles.data(), nt * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    if (nf) HIP_TRY(hipMemcpyAsync(d_fill, p.fill.data(), nf * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(c->mx_cnt.p, 0, 4 * sizeof(unsigned long long), c->stream));
+    const MatrixArgs ma{d_dst, ld, full, band, stat, dtype == WLD_MATRIX_F16, (flags & WLD_MATRIX_ZERO_MISSING) != 0,
+                        ptr<unsigned long long>(c->mx_cnt)};
+    ValuLaunch v = ref_valu_launch(c, 0.0f);  // (finite weights: matrix_check)
+    v.tiles = d_tiles;
+    v.n_tiles = (uint32_t)nt;
+    OrderArgs o{};  // the window only
+    o.L = (uint32_t)L;
+    o.T = (uint32_t)(LP / kTile);
+    o.win_hi = windowed ? ptr<uint32_t>(c->win_hi) : nullptr;
+    HIP_TRY(hipEventRecord(c->ev_mx[0], c->stream));
+    launch_matrix_fill(d_fill, (uint32_t)nf, ptr<uint8_t>(c->site_ok), ma, c->stream);
+    launch_pair_matrix(v, o, ma, c->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c->ev_mx[1], c->stream));
+    uint64_t cls[4] = {0, 0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(cls, c->mx_cnt.p, sizeof(cls), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));  // (the lists are read by the copies)
+    out->kernel_ms += event_ms(c->ev_mx[0], c->ev_mx[1]);
+    out->pairs += cls[0];
+    out->none_pairs += cls[1];
+    out->nonfinite_pairs += cls[2];
+    out->counted_pairs += cls[3];
+    return WLD_OK;
+}
+
+// the kernels' own accounting against the host's plan
+int matrix_account(wld_ctx *c, const matrix_plan::Rect &q, const wld_matrix_info *out) {
+    const uint64_t expect =
+        matrix_plan::count_pairs((uint32_t)c->L, window_on(c) ? c->win_hi_host.data() : nullptr, q);
+    if (out->pairs != expect || out->pairs != out->none_pairs + out->nonfinite_pairs + out->counted_pairs)
+        return fail(WLD_E_HIP, "internal: the matrix counted %llu pairs (%llu none, %llu nonfinite, %llu counted); "
+                               "the rectangle holds %llu",
+                    (unsigned long long)out->pairs, (unsigned long long)out->none_pairs,
+                    (unsigned long long)out->nonfinite_pairs, (unsigned long long)out->counted_pairs,
+                    (unsigned long long)expect);
+    return WLD_OK;
+}
+}  // namespace
+
+int wld_run_matrix_device(wld_ctx *c, uint32_t row_begin, uint32_t row_end, uint32_t col_begin, uint32_t col_end,
+                          int stat, int dtype, int flags, void *d_dst, size_t ld, wld_matrix_info *out) {
+    if (!out) return fail(WLD_E_ARG, "null out");
+    memset(out, 0, sizeof(*out));
+    if (!c) return fail(WLD_E_ARG, "null context");
+    matrix_plan::Rect q{};
+    WLD_TRY(matrix_check(c, "wld_run_matrix_device", row_begin, row_end, col_begin, col_end, stat, dtype, flags, d_dst,
+                         ld, &q));
+    matrix_info_init(out, q, stat, dtype, flags);
+    WLD_TRY(matrix_band(c, q, q, stat, dtype, flags, d_dst, ld, out));
+    return matrix_account(c, q, out);
+}
+
+int wld_run_matrix(wld_ctx *c, uint32_t row_begin, uint32_t row_end, uint32_t col_begin, uint32_t col_end, int stat,
+                   int dtype, int flags, void *h_dst, size_t ld, wld_matrix_info *out) {
+    if (!out) return fail(WLD_E_ARG, "null out");
+    memset(out, 0, sizeof(*out));
+    if (!c) return fail(WLD_E_ARG, "null context");
+    matrix_plan::Rect q{};
+    WLD_TRY(matrix_check(c, "wld_run_matrix", row_begin, row_end, col_begin, col_end, stat, dtype, flags, h_dst, ld, &q));
+    matrix_info_init(out, q, stat, dtype, flags);
+    const size_t eb = dtype == WLD_MATRIX_F16 ? 2 : 4, width = q.c1 - q.c0;
+    std::vector<matrix_plan::Rect> bands;
+    try {
+        bands = matrix_plan::bands(q, eb, c->opt_matrix_bytes);
+    } catch (const std::bad_alloc &) {
+        return fail(WLD_E_OOM, "host allocation of the matrix's bands failed");
+    }
+    DevBuf buf;  // the call's own: released before it returns
+    int st = ensure(buf, (size_t)(bands[0].r1 - bands[0].r0) * width * eb);
+    for (size_t k = 0; k < bands.size() && st == WLD_OK; ++k) {
+        const matrix_plan::Rect &b = bands[k];
+        st = matrix_band(c, q, b, stat, dtype, flags, buf.p, width, out);
+        if (st != WLD_OK) break;
+        const hipError_t e = hipMemcpy2D(static_cast<char *>(h_dst) + (size_t)(b.r0 - q.r0) * ld * eb, ld * eb, buf.p,
+                                         width * eb, width * eb, b.r1 - b.r0, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) st = fail(WLD_E_HIP, "wld_run_matrix copy: %s", hipGetErrorString(e));
+    }
+    release(buf);
+    WLD_TRY(st);
+    return matrix_account(c, q, out);
+}
 
 namespace {
 // What wld_run_partners refuses, checked on a loaded single-device context

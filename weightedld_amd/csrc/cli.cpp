@@ -50,6 +50,14 @@
 //                      ascending, one line per (site, rank), rank from 0
 //                      (wld_run_partners; parent indices as in the pair TSV);
 //                      with it --pair-output may be left out
+//   --matrix-output FILE     dense LD matrix (wld_run_matrix) of the sites of
+//   --matrix-stat STAT       interest, or of those inside --matrix-region
+//   --matrix-region A:B      START:END (parent coordinates): r (default), r2, d
+//   --matrix-format FMT      or dprime; tsv (header row and first column =
+//   --matrix-zero-missing    parent site indices, values %.9g) or npy (v1.0
+//                      <f4, C order; the indices in FILE.sites); NaN entries
+//                      become 0 (1 on the r / r2 diagonal) with
+//                      --matrix-zero-missing; obeys --max-distance/--max-sites
 //   --annot-input FILE       partitioned LD scores (wld_run_annot_scores): FILE is
 //   --annot-score-output FILE  a TSV "site<TAB>name1<TAB>..." of per-site
 //   --annot-self             annotations by parent index; the output has site,
@@ -272,6 +280,12 @@ struct Opt {
     float blocks_min_value = 0.0f;
     int blocks_rule = WLD_BLOCKS_ALL;
     uint32_t blocks_min_sites = 2;
+    // --matrix-output / --matrix-stat / --matrix-region / --matrix-format / --matrix-zero-missing: wld_run_matrix
+    std::string matrix_output;
+    int matrix_stat = WLD_MATRIX_R;
+    uint64_t matrix_lo = 0, matrix_hi = 0;
+    bool have_matrix_stat = false, have_matrix_region = false, have_matrix_format = false, matrix_npy = false,
+         matrix_zero_missing = false;
     // --annot-input / --annot-score-output / --annot-self: wld_run_annot_scores
     std::string annot_input, annot_score_output;
     bool annot_self = false;
@@ -364,6 +378,17 @@ void usage(FILE *f) {
             "        --blocks-rule <blocks-rule>          (addition) all: no weak pair in a block; spine: none with its\n"
             "                                             first or last site [default: all]\n"
             "        --blocks-min-sites <blocks-min-sites>  (addition) smallest block reported, at least 2 [default: 2]\n"
+            "        --matrix-output <matrix-output>      (addition) Filename to write the dense LD matrix of the sites\n"
+            "                                             of interest to (symmetric; 0 outside the window; nan where a\n"
+            "                                             pair has no value); obeys --max-distance, --max-sites\n"
+            "        --matrix-stat <matrix-stat>          (addition) r (signed correlation) | r2 | d | dprime [default: r]\n"
+            "        --matrix-region <matrix-region>      (addition) \"START:END\": only the sites with START <=\n"
+            "                                             parent index < END\n"
+            "        --matrix-format <matrix-format>      (addition) tsv (a header row and a first column of parent\n"
+            "                                             site indices) | npy (float32; the indices go to\n"
+            "                                             <matrix-output>.sites) [default: tsv]\n"
+            "        --matrix-zero-missing                (addition) entries without a value become 0 (1 on the r / r2\n"
+            "                                             diagonal)\n"
             "        --annot-input <annot-input>          (addition) per-site annotations, Tab Separated: a header\n"
             "                                             \"site<TAB>name1<TAB>...\" (1 to 128 names), then per site its\n"
             "                                             parent coordinate (as the pair output's site columns) and\n"
@@ -561,6 +586,32 @@ Opt parse(int argc, char **argv) {
                 arg_error("Invalid value for '--blocks-min-sites' (at least 2):", v.c_str());
             o.blocks_min_sites = (uint32_t)strtoull(v.c_str(), nullptr, 10);
             o.have_blocks_min = true;
+        } else if (a == "--matrix-output") {
+            o.matrix_output = need("--matrix-output");
+        } else if (a == "--matrix-stat") {
+            const std::string k = need("--matrix-stat");
+            if (k != "r" && k != "r2" && k != "d" && k != "dprime") arg_error("Invalid value for '--matrix-stat':", k.c_str());
+            o.matrix_stat = k == "r" ? WLD_MATRIX_R : k == "r2" ? WLD_MATRIX_R2 : k == "d" ? WLD_MATRIX_D : WLD_MATRIX_DPRIME;
+            o.have_matrix_stat = true;
+        } else if (a == "--matrix-region") {
+            const std::string v = need("--matrix-region");
+            const size_t c = v.find(':');
+            const std::string lo = v.substr(0, std::min(c, v.size())), hi = c == std::string::npos ? "" : v.substr(c + 1);
+            auto bad = [](const std::string &t) {
+                return t.empty() || t.find_first_not_of("0123456789") != std::string::npos || t.size() > 19;
+            };
+            if (bad(lo) || bad(hi) || strtoull(lo.c_str(), nullptr, 10) > strtoull(hi.c_str(), nullptr, 10))
+                arg_error("Invalid value for '--matrix-region' (START:END):", v.c_str());
+            o.matrix_lo = strtoull(lo.c_str(), nullptr, 10);
+            o.matrix_hi = strtoull(hi.c_str(), nullptr, 10);
+            o.have_matrix_region = true;
+        } else if (a == "--matrix-format") {
+            const std::string k = need("--matrix-format");
+            if (k != "tsv" && k != "npy") arg_error("Invalid value for '--matrix-format':", k.c_str());
+            o.matrix_npy = k == "npy";
+            o.have_matrix_format = true;
+        } else if (a == "--matrix-zero-missing") {
+            o.matrix_zero_missing = true;
         } else if (a == "--annot-input") {
             o.annot_input = need("--annot-input");
         } else if (a == "--annot-score-output") {
@@ -608,7 +659,17 @@ Opt parse(int argc, char **argv) {
         arg_error("The argument '--annot-score-output' needs", "--annot-input <annot-input>");
     if (o.annot_self && o.annot_score_output.empty())
         arg_error("The argument '--annot-self' needs", "--annot-input <annot-input> and --annot-score-output <annot-score-output>");
-    if (!have_pair && !ld_sel && o.partners_output.empty() && o.blocks_output.empty() && o.annot_score_output.empty())
+    if (o.matrix_output.empty() &&
+        (o.have_matrix_stat || o.have_matrix_region || o.have_matrix_format || o.matrix_zero_missing))
+        arg_error(o.have_matrix_stat     ? "The argument '--matrix-stat' needs"
+                  : o.have_matrix_region ? "The argument '--matrix-region' needs"
+                  : o.have_matrix_format ? "The argument '--matrix-format' needs"
+                                         : "The argument '--matrix-zero-missing' needs",
+                  "--matrix-output <matrix-output>");
+    if (!o.matrix_output.empty() && o.devices.size() > 1)
+        arg_error("The argument '--matrix-output' cannot be used with", "--devices (the LD matrix runs on one device)");
+    if (!have_pair && !ld_sel && o.partners_output.empty() && o.blocks_output.empty() && o.annot_score_output.empty() &&
+        o.matrix_output.empty())
         arg_error("The following required arguments were not provided:", "--pair-output <pair-output>");
     if (!o.have_ld_sites_r2) o.ld_sites_r2 = o.r2_threshold;
     if (!o.have_partners_r2) o.partners_r2 = o.r2_threshold;
@@ -1185,6 +1246,94 @@ void write_annot_scores(const Opt &opt, wld_ctx *ctx, const annot_plan::File &fi
     wld_annot_scores_free(&s);
 }
 
+// --matrix-output: the loaded-site range of --matrix-region (parent[i] as in
+// write_summaries; START <= parent < END, --heatmap-region's rule), one matrix
+// call to the host (wld_run_matrix: the values of the pair TSV's rows, no
+// threshold), then the TSV (%.9g: an f32 round-trips) or the npy file with the
+// parent indices beside it.
+void write_matrix(const Opt &opt, wld_ctx *ctx, const std::vector<uint64_t> &parent) {
+    if (opt.matrix_output.empty()) return;
+    using clk = std::chrono::steady_clock;
+    const auto sw = clk::now();
+    size_t b = 0, e = parent.size();
+    if (opt.have_matrix_region) {
+        if (!std::is_sorted(parent.begin(), parent.end())) {
+            fprintf(stderr, "error: --matrix-region needs sites in ascending parent order\n");
+            quit(1);
+        }
+        b = std::lower_bound(parent.begin(), parent.end(), opt.matrix_lo) - parent.begin();
+        e = std::lower_bound(parent.begin(), parent.end(), opt.matrix_hi) - parent.begin();
+    }
+    if (e <= b) {
+        fprintf(stderr, "error: --matrix-output: no site of interest lies in the region\n");
+        quit(1);
+    }
+    const size_t n = e - b;
+    std::vector<float> m;
+    try {
+        m.resize(n * n);
+    } catch (const std::bad_alloc &) {
+        fprintf(stderr, "error: --matrix-output: a %zu x %zu matrix does not fit in memory (use --matrix-region)\n", n, n);
+        quit(1);
+    }
+    wld_matrix_info info;
+    const int st = wld_run_matrix(ctx, (uint32_t)b, (uint32_t)e, (uint32_t)b, (uint32_t)e, opt.matrix_stat, WLD_MATRIX_F32,
+                                  opt.matrix_zero_missing ? WLD_MATRIX_ZERO_MISSING : 0, m.data(), n, &info);
+    if (st != WLD_OK) die(st, "run_matrix");
+    INFO("Computed the %zu x %zu LD matrix from %s pairs (%s without a statistic) in %s", n, n,
+         human((double)info.pairs).c_str(), human((double)(info.none_pairs + info.nonfinite_pairs)).c_str(),
+         fmt_duration(clk::now() - sw).c_str());
+    INFO("Writing output to %s", debug_path(opt.matrix_output).c_str());
+    auto write_all = [&](const std::string &path, const std::string &head, const void *body, size_t bytes) {
+        FILE *f = fopen(path.c_str(), "wb");
+        const bool ok = f && fwrite(head.data(), 1, head.size(), f) == head.size() &&
+                        (!bytes || fwrite(body, 1, bytes, f) == bytes);
+        if ((f && fclose(f) != 0) || !ok) {
+            fprintf(stderr, "Error: cannot write %s\n", path.c_str());
+            quit(1);
+        }
+    };
+    char cell[64];
+    if (opt.matrix_npy) {
+        // npy 1.0: magic, version, u16 header length, a dict padded with spaces
+        // to a multiple of 64 bytes in all, newline-terminated
+        std::string dict = "{'descr': '<f4', 'fortran_order': False, 'shape': (" + std::to_string(n) + ", " +
+                           std::to_string(n) + "), }";
+        while ((10 + dict.size() + 1) % 64) dict += ' ';
+        dict += '\n';
+        std::string head("\x93NUMPY\x01\x00", 8);
+        head += (char)(dict.size() & 0xFF);
+        head += (char)(dict.size() >> 8);
+        head += dict;
+        write_all(opt.matrix_output, head, m.data(), m.size() * sizeof(float));
+        std::string sites;
+        for (size_t i = b; i < e; ++i) {
+            snprintf(cell, sizeof cell, "%" PRIu64 "\n", parent[i]);
+            sites += cell;
+        }
+        write_all(opt.matrix_output + ".sites", sites, nullptr, 0);
+        return;
+    }
+    std::string out = "site";
+    for (size_t i = b; i < e; ++i) {
+        snprintf(cell, sizeof cell, "\t%" PRIu64, parent[i]);
+        out += cell;
+    }
+    out += "\n";
+    for (size_t i = 0; i < n; ++i) {
+        snprintf(cell, sizeof cell, "%" PRIu64, parent[b + i]);
+        out += cell;
+        for (size_t j = 0; j < n; ++j) {
+            const float x = m[i * n + j];
+            if (x != x) snprintf(cell, sizeof cell, "\tnan");
+            else snprintf(cell, sizeof cell, "\t%.9g", (double)x);
+            out += cell;
+        }
+        out += "\n";
+    }
+    write_all(opt.matrix_output, out, nullptr, 0);
+}
+
 // main.rs:186-212 after the pair computation: timing logs, TSV, clean-up.
 int finish(const Opt &opt, wld_ctx *ctx, wld_pairs &pairs, std::chrono::steady_clock::duration dur,
            uint64_t total_pairs) {
@@ -1259,6 +1408,7 @@ int run_gpu_prepass(const Opt &opt, wld_siteset *siteset, wld_ctx *ctx, const an
     write_partners(opt, ctx, parent);
     write_blocks(opt, ctx, parent);
     write_annot_scores(opt, ctx, annot_file, annot, parent);
+    write_matrix(opt, ctx, parent);
     // (a FASTA set has no site_map: a kept site's parent index is its index in the unfiltered set)
     write_prune(opt, ctx, parent, siteset, std::vector<size_t>(parent.begin(), parent.end()));
     return finish(opt, ctx, pairs, dur, total_pairs);
@@ -1382,6 +1532,7 @@ int main(int argc, char **argv) {
     write_partners(opt, ctx, parent);
     write_blocks(opt, ctx, parent);
     write_annot_scores(opt, ctx, annot_file, annot, parent);
+    write_matrix(opt, ctx, parent);
     std::vector<size_t> self(L);
     for (size_t i = 0; i < L; ++i) self[i] = i;
     write_prune(opt, ctx, parent, filtered, self);

@@ -6,6 +6,7 @@
 #include <cstdint>
 #include <vector>
 
+#include "matrix_plan.hpp"
 #include "screen_policy.hpp"
 
 namespace wld {
@@ -213,6 +214,23 @@ struct AnnotArgs {
     uint32_t CP;
 };
 
+// The destination of a dense LD matrix launch (pair_matrix.hip;
+// wld_run_matrix_device / wld_run_matrix; matrix_plan.hpp lists the tiles and
+// the fill blocks).  dst: the element of entry (band.r0, band.c0), ld elements
+// per row, float (f16 false) or IEEE binary16; only entries inside band are
+// written, by plain stores.  full: the call's rectangle, of which band is a
+// range of whole rows (the counting rule, matrix_plan::counts_here).  counts =
+// {pairs, none, nonfinite, counted}, zero before the launch, one atomic each
+// per tile.  stat: WLD_MATRIX_*; zero_missing: WLD_MATRIX_ZERO_MISSING.
+struct MatrixArgs {
+    void *dst;
+    size_t ld;
+    matrix_plan::Rect full, band;
+    int stat;
+    bool f16, zero_missing;
+    unsigned long long *counts;
+};
+
 // The staging of one batch of a best-partner run (pair_partners.hip;
 // wld_run_partners; layout in partners_plan.hpp).  Tile position p of the
 // launch's list (p < n_tiles, the workgroup id) owns the parts (2 p + side) *
@@ -332,6 +350,16 @@ void launch_pair_heatmap(const ValuLaunch &v, const OrderArgs &o, const HeatmapA
 // window); every tile's counted r2 multiplied into a's score rows; o gives the
 // window only.
 void launch_pair_annot(const ValuLaunch &v, const OrderArgs &o, const AnnotArgs &a, hipStream_t st);
+
+// pair_matrix.hip
+// The same sums over v's list (the call's own list of the band's tiles); every
+// tile's values staged in LDS and stored into m.dst directly and transposed
+// (matrix_plan::images); o gives the window only.  launch_matrix_fill writes
+// the n_blocks listed 64x64 blocks (bi << 16 | bj) no tile of the list covers:
+// +0.0, and the diagonal rule where a block holds the diagonal.
+void launch_pair_matrix(const ValuLaunch &v, const OrderArgs &o, const MatrixArgs &m, hipStream_t st);
+void launch_matrix_fill(const uint32_t *blocks, uint32_t n_blocks, const uint8_t *site_ok, const MatrixArgs &m,
+                        hipStream_t st);
 
 // pair_blocks.hip
 // The same sums over v's list: pass 1 (every tile of the range and window)

@@ -46,7 +46,7 @@
 //
 // The kernel template lives in this header so that pair_valu.hip (the row
 // kernels), pair_summary.hip, pair_heatmap.hip, pair_partners.hip,
-// pair_blocks.hip and pair_annot.hip (REDUCE: the same operands, sums and
+// pair_blocks.hip, pair_annot.hip and pair_matrix.hip (REDUCE: the same operands, sums and
 // ld_epilogue, each tile reduced on chip instead of compacted into rows)
 // instantiate one body: there is no second copy of the sum stages to drift.
 #pragma once
@@ -89,11 +89,13 @@ typedef float v4f __attribute__((ext_vector_type(4)));
 // pairs' per-site break arrays, and the statistics of the pairs inside a
 // block; kReduceAnnot (pair_annot.hip, annot_epilogue): the tile's counted r2
 // times the annotation tiles of its column and row sites, per site and
-// annotation column.  The kernel then takes SummaryArgs / HeatmapArgs /
-// PartnersArgs / BlockBreakArgs / BlockStatsArgs / AnnotArgs where the row
-// kernels take DenseArgs; o gives it the window only.
+// annotation column; kReduceMatrix (pair_matrix.hip, matrix_epilogue): nothing
+// reduced but the class counts — the tile's r2, r, d or d' stored into a
+// caller's matrix, directly and transposed.  The kernel then takes SummaryArgs
+// / HeatmapArgs / PartnersArgs / BlockBreakArgs / BlockStatsArgs / AnnotArgs /
+// MatrixArgs where the row kernels take DenseArgs; o gives it the window only.
 constexpr int kReduceNone = 0, kReduceSummary = 1, kReduceHeatmap = 2, kReducePartners = 3;
-constexpr int kReduceBreaks = 4, kReduceBlockStats = 5, kReduceAnnot = 6;
+constexpr int kReduceBreaks = 4, kReduceBlockStats = 5, kReduceAnnot = 6, kReduceMatrix = 7;
 template <int REDUCE>
 struct ReduceArgsOf { using type = DenseArgs; };
 template <> struct ReduceArgsOf<kReduceSummary> { using type = SummaryArgs; };
@@ -102,6 +104,7 @@ template <> struct ReduceArgsOf<kReducePartners> { using type = PartnersArgs; };
 template <> struct ReduceArgsOf<kReduceBreaks> { using type = BlockBreakArgs; };
 template <> struct ReduceArgsOf<kReduceBlockStats> { using type = BlockStatsArgs; };
 template <> struct ReduceArgsOf<kReduceAnnot> { using type = AnnotArgs; };
+template <> struct ReduceArgsOf<kReduceMatrix> { using type = MatrixArgs; };
 __device__ __attribute__((always_inline)) void summary_epilogue(const SummaryArgs &s, const OrderArgs &o,
                                                                 const uint8_t *site_ok, uint32_t L, uint32_t a0,
                                                                 uint32_t b0, uint32_t tid,
@@ -126,6 +129,10 @@ __device__ __attribute__((always_inline)) void annot_epilogue(const AnnotArgs &k
                                                               const uint8_t *site_ok, uint32_t L, uint32_t a0,
                                                               uint32_t b0, uint32_t tid,
                                                               const float (&tot)[4][4][4]);
+__device__ __attribute__((always_inline)) void matrix_epilogue(const MatrixArgs &m, const OrderArgs &o,
+                                                               const uint8_t *site_ok, uint32_t L, uint32_t a0,
+                                                               uint32_t b0, uint32_t tid,
+                                                               const float (&tot)[4][4][4]);
 template <bool DENSE, bool SAFE, bool MF, bool REF, bool LOOP, int REDUCE = kReduceNone>
 __global__ __launch_bounds__(256, MF ? (REF ? WLD_VALU_REF_WG : WLD_VALU_MF_WG) : 2) void pair_valu_kernel(
     const uint8_t *__restrict__ codes, const float *__restrict__ w, const uint8_t *__restrict__ site_ok,
@@ -446,7 +453,8 @@ __global__ __launch_bounds__(256, MF ? (REF ? WLD_VALU_REF_WG : WLD_VALU_MF_WG) 
             else if constexpr (REDUCE == kReducePartners) partners_epilogue(dn, o, site_ok, L, a0, b0, tid, thr, tot);
             else if constexpr (REDUCE == kReduceBreaks) blocks_break_epilogue(dn, o, site_ok, L, a0, b0, tid, tot);
             else if constexpr (REDUCE == kReduceBlockStats) blocks_stats_epilogue(dn, o, site_ok, L, a0, b0, tid, tot);
-            else annot_epilogue(dn, o, site_ok, L, a0, b0, tid, tot);
+            else if constexpr (REDUCE == kReduceAnnot) annot_epilogue(dn, o, site_ok, L, a0, b0, tid, tot);
+            else matrix_epilogue(dn, o, site_ok, L, a0, b0, tid, tot);
             return;
         }
         // ---- epilogue ------------------------------------------------------
