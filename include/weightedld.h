@@ -895,6 +895,100 @@ int wld_run_matrix_device(wld_ctx *ctx, uint32_t row_begin, uint32_t row_end, ui
 int wld_run_matrix(wld_ctx *ctx, uint32_t row_begin, uint32_t row_end, uint32_t col_begin, uint32_t col_end, int stat,
                    int dtype, int flags, void *h_dst, size_t ld /* elements */, wld_matrix_info *out);
 
+/* ---- Banded LD matrix: band storage of a windowed matrix, and its product
+ * with a block of vectors (not in the reference; LAPACK's upper band storage
+ * by rows: what fine-mapping, imputation and PRS sweeps multiply with, at the
+ * band's size instead of the square's) ----
+ *
+ * Layout.  Rows [row_begin,row_end) are LOADED site indices (an end of 0 means
+ * the loaded site count) and K = bandwidth.  For u in the rows and k = 0..K,
+ * dst[(u - row_begin) * ld + k] (ld in elements, >= K + 1) is entry (u, u + k)
+ * of the matrix wld_run_matrix_device defines under the context's current
+ * window: the same stat (WLD_MATRIX_R2 / _R / _D / _DPRIME, the same signed-r
+ * rule), at k = 0 the same diagonal rule, NaN for a none pair, +0.0 out of the
+ * window, WLD_MATRIX_ZERO_MISSING and the WLD_MATRIX_F32 / _F16 rounding, bit
+ * for bit.  Elements with u + k >= the loaded site count are +0.0.  Pair
+ * (a, b), a < b, is evaluated once, as (a, b), and stored once, in row a; no
+ * value goes through an atomic: two calls give identical bytes.  Every element
+ * of the [rows] x [K + 1] block is written and nothing else is touched, the
+ * ld - (K + 1) elements between rows included.
+ *
+ * Width.  wld_matrix_banded_width gives K_needed = max over a of hi[a] - a for
+ * the window's limits hi (wld_window_limits_copy's; a max_distance-only window
+ * too); without a window, the loaded site count - 1.  bandwidth < K_needed is
+ * refused (WLD_E_ARG, the message names the width needed): a band that drops
+ * in-window pairs is never produced.  bandwidth > K_needed is allowed; the
+ * surplus is +0.0.
+ *
+ * Info.  pairs, none_pairs, nonfinite_pairs, counted_pairs: the in-window
+ * pairs a < b with a in [row_begin,row_end), classified as wld_run_summary
+ * classifies them; for all rows they equal the summary's for the same window.
+ * tiles: the 64x64 tiles launched.  kernel_ms: HIP-event time of the fill and
+ * pair launches (wld_run_matrix_banded: summed over its strips).
+ *
+ * wld_run_matrix_banded_device: d_dst is device memory of the context's
+ * device; the call returns after its work has completed.
+ * wld_run_matrix_banded: h_dst is host memory, written through strips of
+ * whole rows from a device buffer the call owns, at most
+ * WLD_OPT_MATRIX_BATCH_BYTES (64 rows at least); a pair belongs to the strip of
+ * its row a, so a tile is computed once per strip it meets.
+ *
+ * Tile indices are 16-bit: more than 4,194,304 loaded sites are refused.
+ * Refusals and state rules are wld_run_matrix_device's (WLD_E_ARG: an empty or
+ * out-of-range row range, an unknown stat, dtype or flag bit, ld < K + 1, a
+ * null destination, a short bandwidth, non-finite weights; WLD_E_STATE: before
+ * a load, while a run is in flight, on a device group).  The calls keep their
+ * lists, counters and events to themselves: wld_last_stats, the last run's
+ * rows and the row path's cached tile list stay as they were. */
+typedef struct {
+    uint32_t row_begin, row_end; /* as resolved */
+    uint32_t bandwidth;
+    int stat, dtype, flags;
+    uint64_t pairs, none_pairs, nonfinite_pairs, counted_pairs;
+    uint64_t tiles;   /* 64x64 tiles launched */
+    double kernel_ms; /* HIP-event time of the launches */
+} wld_matrix_banded_info;
+int wld_matrix_banded_width(wld_ctx *ctx, uint32_t *bandwidth_needed);
+int wld_run_matrix_banded_device(wld_ctx *ctx, uint32_t row_begin, uint32_t row_end, uint32_t bandwidth, int stat,
+                                 int dtype, int flags, void *d_dst, size_t ld /* elements */,
+                                 wld_matrix_banded_info *out);
+int wld_run_matrix_banded(wld_ctx *ctx, uint32_t row_begin, uint32_t row_end, uint32_t bandwidth, int stat, int dtype,
+                          int flags, void *h_dst, size_t ld /* elements */, wld_matrix_banded_info *out);
+
+/* Band product.  Y = S X for the symmetric n_sites x n_sites matrix S whose
+ * upper band is d_band in the layout above with ALL rows present (row_begin
+ * 0, row_end n_sites): for every site i and column c,
+ *
+ *   Y[i][c] = sum_{k=0..K, i+k<n} B[i][k] X[i+k][c]
+ *           + sum_{k=1..min(K,i)}  B[i-k][k] X[i-k][c]
+ *
+ * d_band: WLD_MATRIX_F32 or _F16 (band_dtype), ld >= K + 1 elements per row.
+ * d_x: WLD_APPLY_X_F32 or _F64 (x_dtype), row-major [n_sites][ldx], ldx >=
+ * n_cols.  d_y: double, [n_sites][ldy], ldy >= n_cols, overwritten (only its
+ * n_cols columns).  n_cols >= 1 with no upper limit.  All three are device
+ * memory of the context's device and must not overlap; the context supplies
+ * the device and the stream only: no load is needed and n_sites is the
+ * caller's.  The call returns after its work has completed.
+ *
+ * Deterministic: every Y element is summed by one owner in a fixed order, in
+ * f64, without atomics; two calls give identical bytes.  With float X every
+ * product is exact and |Y - exact| <= n 2^-52 sum|term| (n the element's term
+ * count); with double X each product is rounded once.
+ * Band elements with i + k >= n_sites are never read.  The device data is not
+ * validated: a non-finite band value propagates by IEEE rules to the rows i
+ * and i + k it belongs to (WLD_MATRIX_ZERO_MISSING avoids them), and X must be
+ * finite: the product runs on 64x64 blocks padded with zeros, so a non-finite
+ * X entry can reach any output within 64 + K sites of it.
+ *
+ * WLD_E_ARG: a null pointer, n_sites or n_cols 0, ld < K + 1, ldx or ldy <
+ * n_cols, an unknown dtype.  WLD_E_STATE: while a run is in flight, on a device
+ * group. */
+#define WLD_APPLY_X_F32 0
+#define WLD_APPLY_X_F64 1
+int wld_banded_apply_device(wld_ctx *ctx, const void *d_band, int band_dtype, size_t ld, uint32_t n_sites,
+                            uint32_t bandwidth, const void *d_x, int x_dtype, size_t ldx, uint32_t n_cols, double *d_y,
+                            size_t ldy);
+
 /* ---- LD pruning: a greedy r2-independent site set with tags (not in the
  * reference; PLINK's --indep-pairwise, bcftools +prune) ----
  *

@@ -157,6 +157,26 @@ class MatrixInfoC(ctypes.Structure):
     ]
 
 
+APPLY_X_F32, APPLY_X_F64 = 0, 1  # WLD_APPLY_X_*
+
+
+class MatrixBandedInfoC(ctypes.Structure):
+    _fields_ = [
+        ("row_begin", ctypes.c_uint32),
+        ("row_end", ctypes.c_uint32),
+        ("bandwidth", ctypes.c_uint32),
+        ("stat", ctypes.c_int),
+        ("dtype", ctypes.c_int),
+        ("flags", ctypes.c_int),
+        ("pairs", ctypes.c_uint64),
+        ("none_pairs", ctypes.c_uint64),
+        ("nonfinite_pairs", ctypes.c_uint64),
+        ("counted_pairs", ctypes.c_uint64),
+        ("tiles", ctypes.c_uint64),
+        ("kernel_ms", ctypes.c_double),
+    ]
+
+
 BLOCKS_R2, BLOCKS_ABS_DPRIME, BLOCKS_ALL, BLOCKS_SPINE, BLOCKS_NONE = 0, 1, 0, 1, 0xFFFFFFFF
 
 
@@ -344,6 +364,13 @@ SIGNATURES = {
                                      _int, _vp, _sz, ctypes.POINTER(MatrixInfoC)]),
     "wld_run_matrix": (_int, [_vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _int, _int, _int,
                               _vp, _sz, ctypes.POINTER(MatrixInfoC)]),
+    "wld_matrix_banded_width": (_int, [_vp, ctypes.POINTER(ctypes.c_uint32)]),
+    "wld_run_matrix_banded_device": (_int, [_vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _int, _int, _int,
+                                            _vp, _sz, ctypes.POINTER(MatrixBandedInfoC)]),
+    "wld_run_matrix_banded": (_int, [_vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _int, _int, _int, _vp, _sz,
+                                     ctypes.POINTER(MatrixBandedInfoC)]),
+    "wld_banded_apply_device": (_int, [_vp, _vp, _int, _sz, ctypes.c_uint32, ctypes.c_uint32, _vp, _int, _sz,
+                                       ctypes.c_uint32, _vp, _sz]),
     "wld_run_prune": (_int, [_vp, ctypes.c_float, _f32p, ctypes.POINTER(Prune)]),
     "wld_prune_free": (None, [ctypes.POINTER(Prune)]),
     "wld_loaded_sites": (_sz, [_vp]),

@@ -15,14 +15,14 @@ import numpy as np
 
 from ._lib import (ANNOT_MAX, ANNOT_SELF, AnnotScoresC, BLOCKS_ABS_DPRIME, BLOCKS_ALL, BLOCKS_NONE, BLOCKS_R2, BLOCKS_SPINE, BlockBreaksC, BlocksC,
                    HEAT_ABS_DPRIME, HEAT_MAX_CELLS, HEAT_R2, KERNEL_AUTO, KERNEL_MFMA, KERNEL_VALU, MATRIX_F16, MATRIX_F32,
-                   MATRIX_STATS, MATRIX_ZERO_MISSING, MatrixInfoC, OPTIONS,
+                   MATRIX_STATS, MATRIX_ZERO_MISSING, APPLY_X_F32, APPLY_X_F64, MatrixBandedInfoC, MatrixInfoC, OPTIONS,
                    PARTNERS_MAX_K, PARTNERS_NONE, PROGRESS_FN, Heatmap, Pairs, PartnersC, Prune, RunStats, Summary,
                    TargetRowsC, WldError, check, lib)
 
 __all__ = [
     "Symbol", "SymbolHistogram", "SiteSet", "LdStats", "PairStore", "read_fasta", "read_vcf",
     "is_site_of_interest", "henikoff_weights", "single_weighted_ld_pair", "all_weighted_ld_pairs",
-    "ld_summary", "LdSummary", "ld_heatmap", "LdHeatmap", "heatmap_cells", "ld_annot_scores", "LdAnnotScores", "annot_matrix", "ANNOT_MAX", "ld_matrix", "LdMatrixInfo", "matrix_args", "matrix_region", "ld_prune", "LdPrune", "maf_priority", "ld_targets", "TargetRows", "ld_partners", "LdPartners", "PARTNERS_MAX_K", "PARTNERS_NONE", "ld_blocks", "LdBlocks", "LdBlockBreaks", "BLOCKS_NONE", "Context", "default_context", "KERNEL_AUTO", "KERNEL_VALU", "KERNEL_MFMA", "OPTIONS", "WldError",
+    "ld_summary", "LdSummary", "ld_heatmap", "LdHeatmap", "heatmap_cells", "ld_annot_scores", "LdAnnotScores", "annot_matrix", "ANNOT_MAX", "ld_matrix", "LdMatrixInfo", "matrix_args", "matrix_region", "ld_banded", "LdBandedInfo", "banded_args", "banded_from_dense", "banded_to_dense", "banded_matmul_host", "banded_cg_solve", "ld_prune", "LdPrune", "maf_priority", "ld_targets", "TargetRows", "ld_partners", "LdPartners", "PARTNERS_MAX_K", "PARTNERS_NONE", "ld_blocks", "LdBlocks", "LdBlockBreaks", "BLOCKS_NONE", "Context", "default_context", "KERNEL_AUTO", "KERNEL_VALU", "KERNEL_MFMA", "OPTIONS", "WldError",
 ]
 
 
@@ -368,6 +368,190 @@ def matrix_region(site_map, n_sites, region):
     if e <= b:
         raise ValueError("no site lies in the region [%d, %d)" % (start, stop))
     return b, e
+
+
+LdBandedInfo = namedtuple("LdBandedInfo", ["rows", "bandwidth", "stat", "dtype", "zero_missing", "pairs", "none_pairs",
+                                           "nonfinite_pairs", "counted_pairs", "tiles", "kernel_ms"])
+LdBandedInfo.__doc__ = """wld_matrix_banded_info (Context.run_matrix_banded, ld_banded): rows, the (begin, end)
+loaded-site range as resolved; bandwidth K (the band has K + 1 columns); stat, dtype, zero_missing; the class counts of
+the in-window pairs a < b with a in rows; the 64x64 tiles launched and kernel_ms."""
+
+
+def _out_layout(out, shape, name):
+    """(kind, row stride in elements) of an out array of Context.run_matrix's kinds, checked against shape and
+    the dtype name; ValueError otherwise."""
+    if isinstance(out, np.ndarray):
+        kind, oname, strides = "numpy", out.dtype.name, tuple(x // out.itemsize if x % out.itemsize == 0 else -1
+                                                               for x in out.strides)
+        if not out.flags.writeable:
+            raise ValueError("out is read-only")
+    elif all(hasattr(out, a) for a in ("data_ptr", "stride", "dtype", "shape", "device")):
+        kind, oname, strides = "device", str(out.dtype).replace("torch.", ""), tuple(int(x) for x in out.stride())
+        if getattr(out.device, "type", "") != "cuda":
+            raise ValueError("a tensor out must be on the context's GPU, not on %s" % (out.device,))
+    else:
+        raise ValueError("out must be a numpy array or a device tensor (data_ptr, stride, dtype, shape, device)")
+    if tuple(int(x) for x in out.shape) != tuple(shape):
+        raise ValueError("out has shape %s; the call writes %s" % (tuple(out.shape), tuple(shape)))
+    if oname != name:
+        raise ValueError("out has dtype %s; dtype is %s" % (oname, name))
+    if strides[1] != 1 and shape[1] > 1:
+        raise ValueError("out must have contiguous rows (last stride 1)")
+    if strides[0] < shape[1] and shape[0] > 1:
+        raise ValueError("out's row stride %d is below the width %d" % (strides[0], shape[1]))
+    return kind, max(strides[0], shape[1])
+
+
+def banded_args(n_sites, needed, rows=None, bandwidth=None, stat="r", dtype="float32", out=None):
+    """Context.run_matrix_banded's arguments checked before any device call:
+    returns (rows, bandwidth, stat id, dtype id, kind, ld) with rows a resolved
+    (begin, end) pair, bandwidth resolved (None: needed, the width the window
+    needs — Context.matrix_banded_width), kind None (no out), "numpy" or
+    "device", and ld the row stride of out in elements (bandwidth + 1 without
+    out).  ValueError on anything the call would refuse: a range outside the
+    n_sites loaded sites, a bandwidth below needed, an unknown stat or dtype, an
+    out of the wrong shape ([rows, bandwidth + 1]), dtype, strides or kind."""
+    rows = _site_range(rows, n_sites, "rows")
+    if stat not in MATRIX_STATS:
+        raise ValueError("stat must be one of %s" % ", ".join('"%s"' % k for k in MATRIX_STATS))
+    name = np.dtype(dtype).name if not isinstance(dtype, str) else dtype
+    if name not in _MATRIX_DTYPES:
+        raise ValueError('dtype must be "float32" or "float16"')
+    needed = int(needed)
+    if bandwidth is None:
+        bandwidth = needed
+    try:
+        K = int(bandwidth)
+    except (TypeError, ValueError):
+        raise ValueError("bandwidth must be None or an integer")
+    if K != bandwidth or K < 0 or K > 0xFFFFFFFF:
+        raise ValueError("bandwidth must be None or an integer in [0, 2^32)")
+    if K < needed:
+        raise ValueError("bandwidth %d would drop in-window pairs; the window needs bandwidth %d" % (K, needed))
+    shape = (rows[1] - rows[0], K + 1)
+    if out is None:
+        return rows, K, MATRIX_STATS[stat], _MATRIX_DTYPES[name], None, shape[1]
+    kind, ld = _out_layout(out, shape, name)
+    return rows, K, MATRIX_STATS[stat], _MATRIX_DTYPES[name], kind, ld
+
+
+def banded_from_dense(M, K):
+    """The upper band of the square matrix M in the banded layout: B[i, k] =
+    M[i, i + k] for k = 0..K, 0 where i + k >= n.  numpy, M's dtype."""
+    M = np.asarray(M)
+    if M.ndim != 2 or M.shape[0] != M.shape[1]:
+        raise ValueError("M must be a square matrix")
+    K = int(K)
+    if K < 0:
+        raise ValueError("K must be >= 0")
+    n = M.shape[0]
+    B = np.zeros((n, K + 1), dtype=M.dtype)
+    for k in range(min(K, n - 1) + 1):
+        B[:n - k, k] = M.diagonal(k)
+    return B
+
+
+def banded_to_dense(B, n=None):
+    """The symmetric n x n matrix of the band B ([n, K + 1]; n None: B's rows):
+    D[i, i + k] = D[i + k, i] = B[i, k] for i + k < n, 0 beyond the band.
+    Elements with i + k >= n are not read.  numpy, B's dtype."""
+    B = np.asarray(B)
+    if B.ndim != 2 or B.shape[1] < 1:
+        raise ValueError("B must be a [n, K + 1] band")
+    n = B.shape[0] if n is None else int(n)
+    if n != B.shape[0]:
+        raise ValueError("B has %d rows for %d sites" % (B.shape[0], n))
+    D = np.zeros((n, n), dtype=B.dtype)
+    i = np.arange(n)
+    for k in range(min(B.shape[1], n)):
+        D[i[:n - k], i[:n - k] + k] = B[:n - k, k]
+        D[i[:n - k] + k, i[:n - k]] = B[:n - k, k]
+    return D
+
+
+def banded_matmul_host(B, X):
+    """The f64 reference of Context.banded_apply on the host: Y = S X for the
+    symmetric matrix S of the band B ([n, K + 1]) and X ([n] or [n, n_cols]),
+    in float64: Y[i] = sum_k B[i, k] X[i + k] + sum_{k >= 1} B[i - k, k] X[i - k].
+    Elements with i + k >= n are not read.  numpy."""
+    B = np.asarray(B)
+    X = np.asarray(X)
+    if B.ndim != 2 or B.shape[1] < 1:
+        raise ValueError("B must be a [n, K + 1] band")
+    n = B.shape[0]
+    if X.ndim not in (1, 2) or X.shape[0] != n:
+        raise ValueError("X must be [n] or [n, n_cols] with n = %d" % n)
+    Bd = B.astype(np.float64)
+    Xd = X.astype(np.float64).reshape(n, -1)
+    Y = np.zeros_like(Xd)
+    for k in range(min(B.shape[1], n)):
+        b = Bd[:n - k, k:k + 1]
+        Y[:n - k] += b * Xd[k:]
+        if k:
+            Y[k:] += b * Xd[:n - k]
+    return Y.reshape(X.shape)
+
+
+def banded_cg_solve(apply, B, b, ridge=0.0, tol=1e-8, max_iter=None):
+    """Plain conjugate gradients for (S + ridge I) x = b, S the symmetric
+    matrix of the band B and apply(B, v) its product with a vector (on whatever
+    array type apply takes: Context.banded_apply on device tensors,
+    banded_matmul_host on numpy arrays).  b is one right-hand side ([n] or
+    [n, 1]).  Returns (x, iterations, relative residual |b - A x| / |b|,
+    converged): converged is True once the residual, recomputed from x, is <=
+    tol within max_iter iterations (None: 10 n).
+
+    The band of a weighted, pairwise-masked correlation matrix need NOT be
+    positive definite (every pair has its own mask, and a window cuts the
+    matrix): where the curvature p.A p of a search direction is not positive
+    the iteration stops with converged False and the best x so far; a ridge
+    makes the system definite."""
+    def f64(a):
+        return a.double() if hasattr(a, "double") else np.asarray(a, dtype=np.float64)
+
+    def dot(u, v):
+        return float((u * v).sum())
+
+    b = f64(b)
+    if len(b.shape) not in (1, 2) or (len(b.shape) == 2 and b.shape[1] != 1):
+        raise ValueError("b must be one right-hand side, [n] or [n, 1]")
+    n = int(b.shape[0])
+    if not (tol > 0):
+        raise ValueError("tol must be > 0")
+    max_iter = 10 * n if max_iter is None else int(max_iter)
+    ridge = float(ridge)
+
+    def A(v):
+        return f64(apply(B, v)) + ridge * v
+
+    x = b.new_zeros(b.shape) if hasattr(b, "new_zeros") else np.zeros_like(b)
+    bnorm = dot(b, b) ** 0.5
+    if bnorm == 0.0:
+        return x, 0, 0.0, True
+    r = b + 0.0
+    p = r
+    rs = dot(r, r)
+    it = 0
+    while it < max_iter:
+        Ap = A(p)
+        curv = dot(p, Ap)
+        if not curv > 0.0:  # (also NaN)
+            return x, it, rs ** 0.5 / bnorm, False
+        it += 1
+        alpha = rs / curv
+        x = x + alpha * p
+        r = r - alpha * Ap
+        rs_new = dot(r, r)
+        if rs_new ** 0.5 <= tol * bnorm:
+            r = b - A(x)  # the residual itself, not its recurrence
+            rs_new = dot(r, r)
+            if rs_new ** 0.5 <= tol * bnorm:
+                return x, it, rs_new ** 0.5 / bnorm, True
+            p, rs = r, rs_new  # restart from it
+            continue
+        p = r + (rs_new / rs) * p
+        rs = rs_new
+    return x, it, rs ** 0.5 / bnorm, False
 
 
 def annot_matrix(annot, n_sites=None):
@@ -1069,6 +1253,111 @@ class Context:
                                  nonfinite_pairs=int(info.nonfinite_pairs), counted_pairs=int(info.counted_pairs),
                                  tiles=int(info.tiles), kernel_ms=float(info.kernel_ms))
 
+    def matrix_banded_width(self):
+        """wld_matrix_banded_width: the bandwidth the context's window needs,
+        max over a of hi[a] - a for the window's limits (no window: the loaded
+        site count - 1).  run_matrix_banded refuses a smaller bandwidth."""
+        k = ctypes.c_uint32(0)
+        check(lib().wld_matrix_banded_width(self._h, ctypes.byref(k)), "wld_matrix_banded_width")
+        return int(k.value)
+
+    def run_matrix_banded(self, rows=None, bandwidth=None, stat="r", dtype="float32", zero_missing=False, out=None):
+        """wld_run_matrix_banded / wld_run_matrix_banded_device: the LD matrix
+        of run_matrix under the context's window in band storage: a
+        [rows, bandwidth + 1] array whose element [u - rows[0], k] is entry
+        (u, u + k) — the same bits as run_matrix's, +0.0 where u + k is past
+        the last site.  rows: a (begin, end) pair of loaded sites (None: every
+        site); bandwidth None: the width the window needs
+        (matrix_banded_width), a smaller one is refused, a larger one pads
+        with +0.0.  out as in run_matrix (a numpy array through the host call,
+        a device tensor in place).  Returns (array, LdBandedInfo).  Argument
+        errors raise ValueError before any device call."""
+        n = int(lib().wld_loaded_sites(self._h))
+        if not n:
+            check(lib().wld_run_matrix_banded(self._h, 0, 0, 0, 0, 0, 0, None, 0, ctypes.byref(MatrixBandedInfoC())),
+                  "wld_run_matrix_banded")  # (not loaded: the library's own refusal)
+        rows, K, st, dt, kind, ld = banded_args(n, self.matrix_banded_width(), rows, bandwidth, stat, dtype, out)
+        flags = MATRIX_ZERO_MISSING if zero_missing else 0
+        info = MatrixBandedInfoC()
+        if kind is None:
+            out = np.empty((rows[1] - rows[0], K + 1), dtype=np.float16 if dt == MATRIX_F16 else np.float32)
+            kind = "numpy"
+        if kind == "numpy":
+            check(lib().wld_run_matrix_banded(self._h, rows[0], rows[1], K, st, dt, flags,
+                                              ctypes.c_void_p(out.ctypes.data), ld, ctypes.byref(info)),
+                  "wld_run_matrix_banded")
+        else:
+            import torch  # (only here: a device tensor was passed)
+            if out.device.index is not None and out.device.index != self.device:
+                raise ValueError("out is on device %d; the context runs on %d" % (out.device.index, self.device))
+            torch.cuda.synchronize(out.device)
+            check(lib().wld_run_matrix_banded_device(self._h, rows[0], rows[1], K, st, dt, flags,
+                                                     ctypes.c_void_p(int(out.data_ptr())), ld, ctypes.byref(info)),
+                  "wld_run_matrix_banded_device")
+        return out, LdBandedInfo(rows=(int(info.row_begin), int(info.row_end)), bandwidth=int(info.bandwidth), stat=stat,
+                                 dtype="float16" if dt == MATRIX_F16 else "float32", zero_missing=bool(zero_missing),
+                                 pairs=int(info.pairs), none_pairs=int(info.none_pairs),
+                                 nonfinite_pairs=int(info.nonfinite_pairs), counted_pairs=int(info.counted_pairs),
+                                 tiles=int(info.tiles), kernel_ms=float(info.kernel_ms))
+
+    def banded_apply(self, band, X, out=None, bandwidth=None):
+        """wld_banded_apply_device: Y = S X on the device for the symmetric
+        matrix S whose upper band is `band` — a [n, W] float32 or float16
+        device tensor in run_matrix_banded's layout with every row present
+        (last stride 1; bandwidth None: W - 1, else the first bandwidth + 1
+        columns) — and X a [n] or [n, n_cols] float32 or float64 device tensor
+        (last stride 1).  Returns a float64 tensor of X's shape (out: such a
+        tensor, overwritten).  Every element is summed by one owner in a fixed
+        order in f64: two calls give identical bytes.  Band elements past the
+        last site (i + k >= n) are never read; X must be finite.  The tensors'
+        pending work is synchronised first; needs no load."""
+        import torch
+
+        def dev(t, what, dtypes):
+            if not all(hasattr(t, a) for a in ("data_ptr", "stride", "dtype", "shape", "device")):
+                raise ValueError("%s must be a device tensor" % what)
+            if getattr(t.device, "type", "") != "cuda":
+                raise ValueError("%s must be on the context's GPU, not on %s" % (what, t.device))
+            if t.device.index is not None and t.device.index != self.device:
+                raise ValueError("%s is on device %d; the context runs on %d" % (what, t.device.index, self.device))
+            if t.dtype not in dtypes:
+                raise ValueError("%s has dtype %s; it must be one of %s" % (what, t.dtype, ", ".join(map(str, dtypes))))
+
+        def stride_of(t, width, what):
+            # rows `ld` elements apart, contiguous inside a row
+            if t.dim() == 2 and t.shape[1] > 1 and t.stride(1) != 1:
+                raise ValueError("%s must have contiguous rows (last stride 1)" % what)
+            ld = int(t.stride(0)) if t.shape[0] > 1 else width
+            if ld < width:
+                raise ValueError("%s's row stride %d is below its width %d" % (what, ld, width))
+            return ld
+
+        dev(band, "band", (torch.float32, torch.float16))
+        dev(X, "X", (torch.float32, torch.float64))
+        if band.dim() != 2 or band.shape[0] < 1 or band.shape[1] < 1:
+            raise ValueError("band must be a [n, bandwidth + 1] tensor")
+        n = int(band.shape[0])
+        K = int(band.shape[1]) - 1 if bandwidth is None else int(bandwidth)
+        if K < 0 or K > int(band.shape[1]) - 1:
+            raise ValueError("bandwidth %d does not fit the band's %d columns" % (K, int(band.shape[1])))
+        if X.dim() not in (1, 2) or int(X.shape[0]) != n or (X.dim() == 2 and X.shape[1] < 1):
+            raise ValueError("X must be [n] or [n, n_cols] with n = %d, not %s" % (n, tuple(X.shape)))
+        n_cols = 1 if X.dim() == 1 else int(X.shape[1])
+        if out is None:
+            out = torch.empty(tuple(X.shape), dtype=torch.float64, device=X.device)
+        else:
+            dev(out, "out", (torch.float64,))
+            if tuple(out.shape) != tuple(X.shape):
+                raise ValueError("out has shape %s; X has %s" % (tuple(out.shape), tuple(X.shape)))
+        ld = stride_of(band, int(band.shape[1]), "band")
+        ldx, ldy = stride_of(X, n_cols, "X"), stride_of(out, n_cols, "out")
+        torch.cuda.synchronize(X.device)
+        check(lib().wld_banded_apply_device(
+            self._h, ctypes.c_void_p(int(band.data_ptr())), MATRIX_F16 if band.dtype == torch.float16 else MATRIX_F32, ld,
+            n, K, ctypes.c_void_p(int(X.data_ptr())), APPLY_X_F64 if X.dtype == torch.float64 else APPLY_X_F32, ldx,
+            n_cols, ctypes.c_void_p(int(out.data_ptr())), ldy), "wld_banded_apply_device")
+        return out
+
     def run_partners(self, k, r2_threshold, chunk_begin=0, chunk_end=0):
         """wld_run_partners: for every LOADED site its best k partners (r2 >
         r2_threshold, r2 descending then partner ascending) among the pairs of
@@ -1431,6 +1720,35 @@ def ld_matrix(site_set, weights, region=None, stat="r", dtype="float32", zero_mi
     sm = site_set.site_map
     sites = (np.arange(sq[0], sq[1], dtype=np.uint64) if sm is None
              else np.asarray(sm, dtype=np.uint64)[sq[0]:sq[1]].copy())
+    return m, info, sites
+
+
+def ld_banded(site_set, weights, bandwidth=None, stat="r", dtype="float32", zero_missing=False, max_distance=None,
+              max_sites=None, out=None, ctx=None):
+    """The LD matrix of site_set in band storage (ld_matrix's matrix at the
+    band's size: what a windowed matrix needs at chromosome scale): loads the
+    set and runs Context.run_matrix_banded on every site under the window
+    max_distance / max_sites (the context's own window is restored
+    afterwards).  bandwidth None: the width the window needs.  Returns (band,
+    info, sites): the [n_sites, bandwidth + 1] band (or out), its LdBandedInfo
+    and the parent coordinates of its rows."""
+    w = np.ascontiguousarray(weights, dtype=np.float32)
+    if w.size != site_set.n_seqs():
+        raise ValueError("weights must have n_seqs entries")
+    n = site_set.n_sites()
+    banded_args(n, 0, None, None if bandwidth is None else bandwidth, stat, dtype,
+                None if bandwidth is None else out)  # (what can be refused before the load)
+    ctx = ctx or default_context()
+    before = ctx.window()
+    if max_distance is not None or max_sites is not None:
+        ctx.set_window(max_distance, max_sites)
+    try:
+        ctx.load(site_set.buffer, w, site_set.site_map)
+        m, info = ctx.run_matrix_banded(None, bandwidth, stat, dtype, zero_missing, out)
+    finally:
+        ctx.set_window(*before)
+    sm = site_set.site_map
+    sites = np.arange(n, dtype=np.uint64) if sm is None else np.asarray(sm, dtype=np.uint64).copy()
     return m, info, sites
 
 

@@ -2894,6 +2894,200 @@ int wld_run_matrix(wld_ctx *c, uint32_t row_begin, uint32_t row_end, uint32_t co
 }
 
 namespace {
+namespace mbp = matrix_banded_plan;
+
+// the window's limits on the host (null: no window), as matrix_check left them
+const uint32_t *banded_limits(wld_ctx *c) { return window_on(c) ? c->win_hi_host.data() : nullptr; }
+
+// What the banded matrix calls refuse, in wld_run_matrix_device's order: the
+// state, then the arguments (matrix_banded_plan::validate), then the load's
+// weights.  *q: the rows with their end resolved.
+int banded_check(wld_ctx *c, const char *who, uint32_t rb, uint32_t re, uint32_t K, int stat, int dtype, int flags,
+                 const void *dst, size_t ld, mbp::Rows *q) {
+    WLD_TRY(set_dev(c));
+    if (!c->loaded) return fail(WLD_E_STATE, "%s before wld_load", who);
+    if (c->pend.active) return fail(WLD_E_STATE, "%s during a run", who);
+    if (window_on(c) && c->win_hi_host.size() != c->L) return fail(WLD_E_STATE, "internal: the window has no plan");
+    const uint32_t needed = mbp::width((uint32_t)std::min<size_t>(c->L, mbp::kMaxSites), banded_limits(c));
+    switch (mbp::validate(c->L, rb, re, K, needed, stat, dtype, flags, ld, dst != nullptr, q)) {
+        case mbp::kOk: break;
+        case mbp::kStat: return fail(WLD_E_ARG, "%s: unknown stat %d", who, stat);
+        case mbp::kDtype: return fail(WLD_E_ARG, "%s: unknown dtype %d", who, dtype);
+        case mbp::kFlags: return fail(WLD_E_ARG, "%s: unknown flags 0x%x", who, (unsigned)flags);
+        case mbp::kNull: return fail(WLD_E_ARG, "%s: null destination", who);
+        case mbp::kSites:
+            return fail(WLD_E_ARG, "%s: %zu loaded sites exceed the %llu that 16-bit tile indices address", who, c->L,
+                        (unsigned long long)mbp::kMaxSites);
+        case mbp::kRange: return fail(WLD_E_ARG, "%s: rows [%u,%u) exceed the %zu loaded sites", who, rb, re, c->L);
+        case mbp::kEmpty: return fail(WLD_E_ARG, "%s: rows [%u,%u) hold no site", who, rb, re);
+        case mbp::kWidth:
+            return fail(WLD_E_ARG, "%s: bandwidth %u would drop in-window pairs; the window needs bandwidth %u", who, K,
+                        needed);
+        case mbp::kLd: return fail(WLD_E_ARG, "%s: ld %zu is below bandwidth + 1 = %llu", who, ld, (unsigned long long)K + 1);
+    }
+    if (c->safe) return fail(WLD_E_ARG, "%s needs finite weights (this load takes the select loop)", who);
+    return WLD_OK;
+}
+
+void banded_info_init(wld_matrix_banded_info *out, const mbp::Rows &q, uint32_t K, int stat, int dtype, int flags) {
+    memset(out, 0, sizeof(*out));
+    out->row_begin = q.r0, out->row_end = q.r1, out->bandwidth = K;
+    out->stat = stat, out->dtype = dtype, out->flags = flags;
+}
+
+// One strip of rows into device memory (d_dst: element k = 0 of row strip.r0):
+// the strip's tile and fill lists in the matrix calls' own buffers, zeroed
+// class counts, the fill and pair launches, the counts back; returns after the
+// work has completed, its counts, tiles and time added to *out.  Touches no
+// staging, segment count, chunk total, run counter, cached tile list or
+// row-path event.
+int banded_strip(wld_ctx *c, const mbp::Rows &strip, uint32_t K, int stat, int dtype, int flags, void *d_dst, size_t ld,
+                 wld_matrix_banded_info *out) {
+    const size_t L = c->L, LP = c->LP;
+    const bool windowed = window_on(c);
+    mbp::Plan p;
+    try {
+        p = mbp::plan((uint32_t)L, banded_limits(c), strip, K);
+        const uint32_t T_used = (uint32_t)((L + kTile - 1) / kTile);
+        out->tiles += p.tiles.size();
+        if (!c->opt_tile_rows && p.tiles.size() >= 4096 && T_used < 65535)
+            p.tiles = xcd_order(p.tiles, tile_order::super_block_side((uint32_t)c->NP));
+    } catch (const std::bad_alloc &) {
+        return fail(WLD_E_OOM, "host allocation of the banded matrix's tile list failed");
+    }
+    const size_t nt = p.tiles.size(), nf = p.fill.size();
+    if (nf > 0xFFFFFFFFull) return fail(WLD_E_ARG, "the banded matrix's fill list exceeds a launch");
+    if (nt) WLD_TRY(ensure_ref_layout(c));
+    for (auto &e : c->ev_mx)
+        if (!e) HIP_TRY(hipEventCreate(&e));
+    WLD_TRY(ensure(c->mx_lists, nt * sizeof(uint32_t) + nf * sizeof(mbp::FillBlock)));
+    WLD_TRY(ensure(c->mx_cnt, 4 * sizeof(unsigned long long)));
+    uint32_t *d_tiles = ptr<uint32_t>(c->mx_lists);
+    mbp::FillBlock *d_fill = reinterpret_cast<mbp::FillBlock *>(d_tiles + nt);
+    if (nt) HIP_TRY(hipMemcpyAsync(d_tiles, p.tiles.data(), nt * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    if (nf) HIP_TRY(hipMemcpyAsync(d_fill, p.fill.data(), nf * sizeof(mbp::FillBlock), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(c->mx_cnt.p, 0, 4 * sizeof(unsigned long long), c->stream));
+    const MatrixBandedArgs ma{d_dst, ld, strip.r0, strip.r1, K, stat, dtype == WLD_MATRIX_F16,
+                              (flags & WLD_MATRIX_ZERO_MISSING) != 0, ptr<unsigned long long>(c->mx_cnt)};
+    ValuLaunch v = ref_valu_launch(c, 0.0f);  // (finite weights: banded_check)
+    v.tiles = d_tiles;
+    v.n_tiles = (uint32_t)nt;
+    OrderArgs o{};  // the window only
+    o.L = (uint32_t)L;
+    o.T = (uint32_t)(LP / kTile);
+    o.win_hi = windowed ? ptr<uint32_t>(c->win_hi) : nullptr;
+    HIP_TRY(hipEventRecord(c->ev_mx[0], c->stream));
+    launch_matrix_banded_fill(d_fill, (uint32_t)nf, ptr<uint8_t>(c->site_ok), ma, c->stream);
+    launch_pair_matrix_banded(v, o, ma, c->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c->ev_mx[1], c->stream));
+    uint64_t cls[4] = {0, 0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(cls, c->mx_cnt.p, sizeof(cls), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));  // (the lists are read by the copies)
+    out->kernel_ms += event_ms(c->ev_mx[0], c->ev_mx[1]);
+    out->pairs += cls[0];
+    out->none_pairs += cls[1];
+    out->nonfinite_pairs += cls[2];
+    out->counted_pairs += cls[3];
+    return WLD_OK;
+}
+
+// the kernels' own accounting against the host's plan
+int banded_account(wld_ctx *c, const mbp::Rows &q, const wld_matrix_banded_info *out) {
+    const uint64_t expect = mbp::count_pairs((uint32_t)c->L, banded_limits(c), q);
+    if (out->pairs != expect || out->pairs != out->none_pairs + out->nonfinite_pairs + out->counted_pairs)
+        return fail(WLD_E_HIP, "internal: the banded matrix counted %llu pairs (%llu none, %llu nonfinite, %llu "
+                               "counted); the rows hold %llu",
+                    (unsigned long long)out->pairs, (unsigned long long)out->none_pairs,
+                    (unsigned long long)out->nonfinite_pairs, (unsigned long long)out->counted_pairs,
+                    (unsigned long long)expect);
+    return WLD_OK;
+}
+}  // namespace
+
+int wld_matrix_banded_width(wld_ctx *c, uint32_t *bandwidth_needed) {
+    if (!c) return fail(WLD_E_ARG, "null context");
+    if (!bandwidth_needed) return fail(WLD_E_ARG, "wld_matrix_banded_width: null output");
+    WLD_TRY(set_dev(c));
+    if (!c->loaded) return fail(WLD_E_STATE, "wld_matrix_banded_width before wld_load");
+    if (window_on(c) && c->win_hi_host.size() != c->L) return fail(WLD_E_STATE, "internal: the window has no plan");
+    if (c->L > mbp::kMaxSites)
+        return fail(WLD_E_ARG, "wld_matrix_banded_width: %zu loaded sites exceed the %llu that 16-bit tile indices address",
+                    c->L, (unsigned long long)mbp::kMaxSites);
+    *bandwidth_needed = mbp::width((uint32_t)c->L, banded_limits(c));
+    return WLD_OK;
+}
+
+int wld_run_matrix_banded_device(wld_ctx *c, uint32_t row_begin, uint32_t row_end, uint32_t bandwidth, int stat,
+                                 int dtype, int flags, void *d_dst, size_t ld, wld_matrix_banded_info *out) {
+    if (!out) return fail(WLD_E_ARG, "null out");
+    memset(out, 0, sizeof(*out));
+    if (!c) return fail(WLD_E_ARG, "null context");
+    mbp::Rows q{};
+    WLD_TRY(banded_check(c, "wld_run_matrix_banded_device", row_begin, row_end, bandwidth, stat, dtype, flags, d_dst, ld,
+                         &q));
+    banded_info_init(out, q, bandwidth, stat, dtype, flags);
+    WLD_TRY(banded_strip(c, q, bandwidth, stat, dtype, flags, d_dst, ld, out));
+    return banded_account(c, q, out);
+}
+
+int wld_run_matrix_banded(wld_ctx *c, uint32_t row_begin, uint32_t row_end, uint32_t bandwidth, int stat, int dtype,
+                          int flags, void *h_dst, size_t ld, wld_matrix_banded_info *out) {
+    if (!out) return fail(WLD_E_ARG, "null out");
+    memset(out, 0, sizeof(*out));
+    if (!c) return fail(WLD_E_ARG, "null context");
+    mbp::Rows q{};
+    WLD_TRY(banded_check(c, "wld_run_matrix_banded", row_begin, row_end, bandwidth, stat, dtype, flags, h_dst, ld, &q));
+    banded_info_init(out, q, bandwidth, stat, dtype, flags);
+    const size_t eb = dtype == WLD_MATRIX_F16 ? 2 : 4, width = (size_t)bandwidth + 1;
+    std::vector<mbp::Rows> strips;
+    try {
+        strips = mbp::strips(q, bandwidth, eb, c->opt_matrix_bytes);
+    } catch (const std::bad_alloc &) {
+        return fail(WLD_E_OOM, "host allocation of the banded matrix's strips failed");
+    }
+    DevBuf buf;  // the call's own: released before it returns
+    int st = ensure(buf, (size_t)(strips[0].r1 - strips[0].r0) * width * eb);
+    for (size_t k = 0; k < strips.size() && st == WLD_OK; ++k) {
+        const mbp::Rows &s = strips[k];
+        st = banded_strip(c, s, bandwidth, stat, dtype, flags, buf.p, width, out);
+        if (st != WLD_OK) break;
+        const hipError_t e = hipMemcpy2D(static_cast<char *>(h_dst) + (size_t)(s.r0 - q.r0) * ld * eb, ld * eb, buf.p,
+                                         width * eb, width * eb, s.r1 - s.r0, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) st = fail(WLD_E_HIP, "wld_run_matrix_banded copy: %s", hipGetErrorString(e));
+    }
+    release(buf);
+    WLD_TRY(st);
+    return banded_account(c, q, out);
+}
+
+int wld_banded_apply_device(wld_ctx *c, const void *d_band, int band_dtype, size_t ld, uint32_t n_sites,
+                            uint32_t bandwidth, const void *d_x, int x_dtype, size_t ldx, uint32_t n_cols, double *d_y,
+                            size_t ldy) {
+    const char *who = "wld_banded_apply_device";
+    if (!c) return fail(WLD_E_ARG, "null context");
+    WLD_TRY(set_dev(c));
+    if (c->pend.active) return fail(WLD_E_STATE, "%s during a run", who);
+    if (!d_band || !d_x || !d_y) return fail(WLD_E_ARG, "%s: null %s", who, !d_band ? "band" : !d_x ? "X" : "Y");
+    if (band_dtype != WLD_MATRIX_F32 && band_dtype != WLD_MATRIX_F16)
+        return fail(WLD_E_ARG, "%s: unknown band dtype %d", who, band_dtype);
+    if (x_dtype != WLD_APPLY_X_F32 && x_dtype != WLD_APPLY_X_F64)
+        return fail(WLD_E_ARG, "%s: unknown X dtype %d", who, x_dtype);
+    if (!n_sites) return fail(WLD_E_ARG, "%s: no site", who);
+    if (!n_cols) return fail(WLD_E_ARG, "%s: no column", who);
+    if ((uint64_t)ld < (uint64_t)bandwidth + 1)
+        return fail(WLD_E_ARG, "%s: ld %zu is below bandwidth + 1 = %llu", who, ld, (unsigned long long)bandwidth + 1);
+    if (ldx < n_cols || ldy < n_cols)
+        return fail(WLD_E_ARG, "%s: ldx %zu or ldy %zu is below the %u columns", who, ldx, ldy, n_cols);
+    const BandedApplyArgs a{d_band, ld,   n_sites, bandwidth, band_dtype == WLD_MATRIX_F16, x_dtype == WLD_APPLY_X_F64,
+                            d_x,    ldx,  n_cols,  d_y,       ldy};
+    launch_banded_apply(a, c->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return WLD_OK;
+}
+
+namespace {
 // What wld_run_partners refuses, checked on a loaded single-device context
 // (every member of a group holds the same load).
 int partners_check(wld_ctx *c, uint32_t k, float thr) {

@@ -58,6 +58,10 @@
 //                      <f4, C order; the indices in FILE.sites); NaN entries
 //                      become 0 (1 on the r / r2 diagonal) with
 //                      --matrix-zero-missing; obeys --max-distance/--max-sites
+//   --matrix-banded          with --matrix-format npy and a window: FILE holds
+//                      the [n, K + 1] upper band of every site of interest
+//                      (wld_run_matrix_banded; element [i, k] = entry (i, i + k),
+//                      K the width the window needs) instead of the square
 //   --annot-input FILE       partitioned LD scores (wld_run_annot_scores): FILE is
 //   --annot-score-output FILE  a TSV "site<TAB>name1<TAB>..." of per-site
 //   --annot-self             annotations by parent index; the output has site,
@@ -285,7 +289,7 @@ struct Opt {
     int matrix_stat = WLD_MATRIX_R;
     uint64_t matrix_lo = 0, matrix_hi = 0;
     bool have_matrix_stat = false, have_matrix_region = false, have_matrix_format = false, matrix_npy = false,
-         matrix_zero_missing = false;
+         matrix_zero_missing = false, matrix_banded = false;
     // --annot-input / --annot-score-output / --annot-self: wld_run_annot_scores
     std::string annot_input, annot_score_output;
     bool annot_self = false;
@@ -389,6 +393,10 @@ void usage(FILE *f) {
             "                                             <matrix-output>.sites) [default: tsv]\n"
             "        --matrix-zero-missing                (addition) entries without a value become 0 (1 on the r / r2\n"
             "                                             diagonal)\n"
+            "        --matrix-banded                      (addition) write the band of the windowed matrix instead of the\n"
+            "                                             square: an [n, K+1] array, element [i, k] = entry (i, i+k), K\n"
+            "                                             the width the window needs; needs --matrix-format npy and\n"
+            "                                             --max-distance or --max-sites, takes no --matrix-region\n"
             "        --annot-input <annot-input>          (addition) per-site annotations, Tab Separated: a header\n"
             "                                             \"site<TAB>name1<TAB>...\" (1 to 128 names), then per site its\n"
             "                                             parent coordinate (as the pair output's site columns) and\n"
@@ -612,6 +620,8 @@ Opt parse(int argc, char **argv) {
             o.have_matrix_format = true;
         } else if (a == "--matrix-zero-missing") {
             o.matrix_zero_missing = true;
+        } else if (a == "--matrix-banded") {
+            o.matrix_banded = true;
         } else if (a == "--annot-input") {
             o.annot_input = need("--annot-input");
         } else if (a == "--annot-score-output") {
@@ -660,12 +670,19 @@ Opt parse(int argc, char **argv) {
     if (o.annot_self && o.annot_score_output.empty())
         arg_error("The argument '--annot-self' needs", "--annot-input <annot-input> and --annot-score-output <annot-score-output>");
     if (o.matrix_output.empty() &&
-        (o.have_matrix_stat || o.have_matrix_region || o.have_matrix_format || o.matrix_zero_missing))
-        arg_error(o.have_matrix_stat     ? "The argument '--matrix-stat' needs"
-                  : o.have_matrix_region ? "The argument '--matrix-region' needs"
-                  : o.have_matrix_format ? "The argument '--matrix-format' needs"
-                                         : "The argument '--matrix-zero-missing' needs",
+        (o.have_matrix_stat || o.have_matrix_region || o.have_matrix_format || o.matrix_zero_missing || o.matrix_banded))
+        arg_error(o.have_matrix_stat      ? "The argument '--matrix-stat' needs"
+                  : o.have_matrix_region  ? "The argument '--matrix-region' needs"
+                  : o.have_matrix_format  ? "The argument '--matrix-format' needs"
+                  : o.matrix_zero_missing ? "The argument '--matrix-zero-missing' needs"
+                                          : "The argument '--matrix-banded' needs",
                   "--matrix-output <matrix-output>");
+    if (o.matrix_banded && !o.matrix_npy)
+        arg_error("The argument '--matrix-banded' needs", "--matrix-format npy (a band has no tsv form)");
+    if (o.matrix_banded && o.have_matrix_region)
+        arg_error("The argument '--matrix-banded' cannot be used with", "--matrix-region (the band holds every site of interest)");
+    if (o.matrix_banded && !o.max_distance && !o.max_sites)
+        arg_error("The argument '--matrix-banded' needs", "--max-distance or --max-sites (without a window the band is the square)");
     if (!o.matrix_output.empty() && o.devices.size() > 1)
         arg_error("The argument '--matrix-output' cannot be used with", "--devices (the LD matrix runs on one device)");
     if (!have_pair && !ld_sel && o.partners_output.empty() && o.blocks_output.empty() && o.annot_score_output.empty() &&
@@ -1269,20 +1286,42 @@ void write_matrix(const Opt &opt, wld_ctx *ctx, const std::vector<uint64_t> &par
         quit(1);
     }
     const size_t n = e - b;
+    size_t width = n;  // the file's columns: n, or --matrix-banded's K + 1
     std::vector<float> m;
-    try {
-        m.resize(n * n);
-    } catch (const std::bad_alloc &) {
-        fprintf(stderr, "error: --matrix-output: a %zu x %zu matrix does not fit in memory (use --matrix-region)\n", n, n);
-        quit(1);
+    if (opt.matrix_banded) {
+        uint32_t K = 0;
+        int st = wld_matrix_banded_width(ctx, &K);
+        if (st != WLD_OK) die(st, "matrix_banded_width");
+        width = (size_t)K + 1;
+        try {
+            m.resize(n * width);
+        } catch (const std::bad_alloc &) {
+            fprintf(stderr, "error: --matrix-output: a %zu x %zu band does not fit in memory\n", n, width);
+            quit(1);
+        }
+        wld_matrix_banded_info info;
+        st = wld_run_matrix_banded(ctx, 0, 0, K, opt.matrix_stat, WLD_MATRIX_F32,
+                                   opt.matrix_zero_missing ? WLD_MATRIX_ZERO_MISSING : 0, m.data(), width, &info);
+        if (st != WLD_OK) die(st, "run_matrix_banded");
+        INFO("Computed the %zu x %zu band of the LD matrix from %s pairs (%s without a statistic) in %s", n, width,
+             human((double)info.pairs).c_str(), human((double)(info.none_pairs + info.nonfinite_pairs)).c_str(),
+             fmt_duration(clk::now() - sw).c_str());
+    } else {
+        try {
+            m.resize(n * n);
+        } catch (const std::bad_alloc &) {
+            fprintf(stderr, "error: --matrix-output: a %zu x %zu matrix does not fit in memory (use --matrix-region)\n", n, n);
+            quit(1);
+        }
+        wld_matrix_info info;
+        const int st = wld_run_matrix(ctx, (uint32_t)b, (uint32_t)e, (uint32_t)b, (uint32_t)e, opt.matrix_stat,
+                                      WLD_MATRIX_F32, opt.matrix_zero_missing ? WLD_MATRIX_ZERO_MISSING : 0, m.data(), n,
+                                      &info);
+        if (st != WLD_OK) die(st, "run_matrix");
+        INFO("Computed the %zu x %zu LD matrix from %s pairs (%s without a statistic) in %s", n, n,
+             human((double)info.pairs).c_str(), human((double)(info.none_pairs + info.nonfinite_pairs)).c_str(),
+             fmt_duration(clk::now() - sw).c_str());
     }
-    wld_matrix_info info;
-    const int st = wld_run_matrix(ctx, (uint32_t)b, (uint32_t)e, (uint32_t)b, (uint32_t)e, opt.matrix_stat, WLD_MATRIX_F32,
-                                  opt.matrix_zero_missing ? WLD_MATRIX_ZERO_MISSING : 0, m.data(), n, &info);
-    if (st != WLD_OK) die(st, "run_matrix");
-    INFO("Computed the %zu x %zu LD matrix from %s pairs (%s without a statistic) in %s", n, n,
-         human((double)info.pairs).c_str(), human((double)(info.none_pairs + info.nonfinite_pairs)).c_str(),
-         fmt_duration(clk::now() - sw).c_str());
     INFO("Writing output to %s", debug_path(opt.matrix_output).c_str());
     auto write_all = [&](const std::string &path, const std::string &head, const void *body, size_t bytes) {
         FILE *f = fopen(path.c_str(), "wb");
@@ -1298,7 +1337,7 @@ void write_matrix(const Opt &opt, wld_ctx *ctx, const std::vector<uint64_t> &par
         // npy 1.0: magic, version, u16 header length, a dict padded with spaces
         // to a multiple of 64 bytes in all, newline-terminated
         std::string dict = "{'descr': '<f4', 'fortran_order': False, 'shape': (" + std::to_string(n) + ", " +
-                           std::to_string(n) + "), }";
+                           std::to_string(width) + "), }";
         while ((10 + dict.size() + 1) % 64) dict += ' ';
         dict += '\n';
         std::string head("\x93NUMPY\x01\x00", 8);

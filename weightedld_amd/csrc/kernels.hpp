@@ -6,6 +6,7 @@
 #include <cstdint>
 #include <vector>
 
+#include "matrix_banded_plan.hpp"
 #include "matrix_plan.hpp"
 #include "screen_policy.hpp"
 
@@ -231,6 +232,39 @@ struct MatrixArgs {
     unsigned long long *counts;
 };
 
+// The destination of a banded LD matrix launch (pair_matrix_banded.hip;
+// wld_run_matrix_banded_device / wld_run_matrix_banded; matrix_banded_plan.hpp
+// lists the tiles and the fill blocks).  dst: the element k = 0 of row r0, ld
+// elements per row, float (f16 false) or IEEE binary16; element k of row u is
+// entry (u, u + k); only the elements k <= K of the rows [r0, r1) are written,
+// by plain stores.  counts = {pairs, none, nonfinite, counted} of the in-window
+// pairs a < b with a in [r0, r1), zero before the launch, one atomic each per
+// tile.  stat: WLD_MATRIX_*; zero_missing: WLD_MATRIX_ZERO_MISSING.
+struct MatrixBandedArgs {
+    void *dst;
+    size_t ld;
+    uint32_t r0, r1, K;
+    int stat;
+    bool f16, zero_missing;
+    unsigned long long *counts;
+};
+
+// The operands of a band product (banded_apply.hip; wld_banded_apply_device):
+// Y[n][ldy] f64 := S X, S the symmetric matrix whose upper band (elements k =
+// 0..K of every row, ld apart, float or binary16) is `band`, X[n][ldx] float
+// (x64 false) or double, n_cols columns.
+struct BandedApplyArgs {
+    const void *band;
+    size_t ld;
+    uint32_t n, K;
+    bool band_f16, x64;
+    const void *x;
+    size_t ldx;
+    uint32_t n_cols;
+    double *y;
+    size_t ldy;
+};
+
 // The staging of one batch of a best-partner run (pair_partners.hip;
 // wld_run_partners; layout in partners_plan.hpp).  Tile position p of the
 // launch's list (p < n_tiles, the workgroup id) owns the parts (2 p + side) *
@@ -360,6 +394,21 @@ void launch_pair_annot(const ValuLaunch &v, const OrderArgs &o, const AnnotArgs 
 void launch_pair_matrix(const ValuLaunch &v, const OrderArgs &o, const MatrixArgs &m, hipStream_t st);
 void launch_matrix_fill(const uint32_t *blocks, uint32_t n_blocks, const uint8_t *site_ok, const MatrixArgs &m,
                         hipStream_t st);
+
+// pair_matrix_banded.hip
+// The same sums over v's list (the call's own list of the row range's tiles);
+// every tile's values staged in LDS and stored into the rows of m.dst, each
+// tile row one contiguous run of k; o gives the window only.
+// launch_matrix_banded_fill writes the elements of the n_blocks listed blocks
+// that no tile of the list covers: +0.0, and the diagonal rule at k = 0.
+void launch_pair_matrix_banded(const ValuLaunch &v, const OrderArgs &o, const MatrixBandedArgs &m, hipStream_t st);
+void launch_matrix_banded_fill(const matrix_banded_plan::FillBlock *blocks, uint32_t n_blocks, const uint8_t *site_ok,
+                               const MatrixBandedArgs &m, hipStream_t st);
+
+// banded_apply.hip
+// Y := S X on st: one workgroup per 64 output rows and 16 or 64 columns, each Y
+// element summed by its owner in a fixed order (f64 MFMA accumulation).
+void launch_banded_apply(const BandedApplyArgs &a, hipStream_t st);
 
 // pair_blocks.hip
 // The same sums over v's list: pass 1 (every tile of the range and window)

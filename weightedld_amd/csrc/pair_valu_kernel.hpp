@@ -46,7 +46,7 @@
 //
 // The kernel template lives in this header so that pair_valu.hip (the row
 // kernels), pair_summary.hip, pair_heatmap.hip, pair_partners.hip,
-// pair_blocks.hip, pair_annot.hip and pair_matrix.hip (REDUCE: the same operands, sums and
+// pair_blocks.hip, pair_annot.hip, pair_matrix.hip and pair_matrix_banded.hip (REDUCE: the same operands, sums and
 // ld_epilogue, each tile reduced on chip instead of compacted into rows)
 // instantiate one body: there is no second copy of the sum stages to drift.
 #pragma once
@@ -91,11 +91,15 @@ typedef float v4f __attribute__((ext_vector_type(4)));
 // times the annotation tiles of its column and row sites, per site and
 // annotation column; kReduceMatrix (pair_matrix.hip, matrix_epilogue): nothing
 // reduced but the class counts — the tile's r2, r, d or d' stored into a
-// caller's matrix, directly and transposed.  The kernel then takes SummaryArgs
-// / HeatmapArgs / PartnersArgs / BlockBreakArgs / BlockStatsArgs / AnnotArgs /
-// MatrixArgs where the row kernels take DenseArgs; o gives it the window only.
+// caller's matrix, directly and transposed; kReduceMatrixBanded
+// (pair_matrix_banded.hip, matrix_banded_epilogue): the same values stored once,
+// into the upper band of a caller's banded matrix.  The kernel then takes
+// SummaryArgs / HeatmapArgs / PartnersArgs / BlockBreakArgs / BlockStatsArgs /
+// AnnotArgs / MatrixArgs / MatrixBandedArgs where the row kernels take
+// DenseArgs; o gives it the window only.
 constexpr int kReduceNone = 0, kReduceSummary = 1, kReduceHeatmap = 2, kReducePartners = 3;
 constexpr int kReduceBreaks = 4, kReduceBlockStats = 5, kReduceAnnot = 6, kReduceMatrix = 7;
+constexpr int kReduceMatrixBanded = 8;
 template <int REDUCE>
 struct ReduceArgsOf { using type = DenseArgs; };
 template <> struct ReduceArgsOf<kReduceSummary> { using type = SummaryArgs; };
@@ -105,6 +109,7 @@ template <> struct ReduceArgsOf<kReduceBreaks> { using type = BlockBreakArgs; };
 template <> struct ReduceArgsOf<kReduceBlockStats> { using type = BlockStatsArgs; };
 template <> struct ReduceArgsOf<kReduceAnnot> { using type = AnnotArgs; };
 template <> struct ReduceArgsOf<kReduceMatrix> { using type = MatrixArgs; };
+template <> struct ReduceArgsOf<kReduceMatrixBanded> { using type = MatrixBandedArgs; };
 __device__ __attribute__((always_inline)) void summary_epilogue(const SummaryArgs &s, const OrderArgs &o,
                                                                 const uint8_t *site_ok, uint32_t L, uint32_t a0,
                                                                 uint32_t b0, uint32_t tid,
@@ -133,6 +138,10 @@ __device__ __attribute__((always_inline)) void matrix_epilogue(const MatrixArgs 
                                                                const uint8_t *site_ok, uint32_t L, uint32_t a0,
                                                                uint32_t b0, uint32_t tid,
                                                                const float (&tot)[4][4][4]);
+__device__ __attribute__((always_inline)) void matrix_banded_epilogue(const MatrixBandedArgs &m, const OrderArgs &o,
+                                                                      const uint8_t *site_ok, uint32_t L, uint32_t a0,
+                                                                      uint32_t b0, uint32_t tid,
+                                                                      const float (&tot)[4][4][4]);
 template <bool DENSE, bool SAFE, bool MF, bool REF, bool LOOP, int REDUCE = kReduceNone>
 __global__ __launch_bounds__(256, MF ? (REF ? WLD_VALU_REF_WG : WLD_VALU_MF_WG) : 2) void pair_valu_kernel(
     const uint8_t *__restrict__ codes, const float *__restrict__ w, const uint8_t *__restrict__ site_ok,
@@ -454,7 +463,8 @@ __global__ __launch_bounds__(256, MF ? (REF ? WLD_VALU_REF_WG : WLD_VALU_MF_WG) 
             else if constexpr (REDUCE == kReduceBreaks) blocks_break_epilogue(dn, o, site_ok, L, a0, b0, tid, tot);
             else if constexpr (REDUCE == kReduceBlockStats) blocks_stats_epilogue(dn, o, site_ok, L, a0, b0, tid, tot);
             else if constexpr (REDUCE == kReduceAnnot) annot_epilogue(dn, o, site_ok, L, a0, b0, tid, tot);
-            else matrix_epilogue(dn, o, site_ok, L, a0, b0, tid, tot);
+            else if constexpr (REDUCE == kReduceMatrix) matrix_epilogue(dn, o, site_ok, L, a0, b0, tid, tot);
+            else matrix_banded_epilogue(dn, o, site_ok, L, a0, b0, tid, tot);
             return;
         }
         // ---- epilogue ------------------------------------------------------
