@@ -10,7 +10,7 @@ set -e
 cd "$(dirname "$0")/.."
 name=$1; flags=$2
 src=${SRC:-pair_mfma}
-all="encode prepass pair_valu pair_summary pair_heatmap pair_annot pair_partners pair_blocks pair_mfma prune order pair_targets capi host"
+all="encode prepass pair_valu pair_summary pair_heatmap pair_annot pair_matrix pair_matrix_banded banded_apply pair_partners pair_blocks pair_mfma prune order pair_targets capi host"
 make -s $(for o in $all; do echo build/obj/$o.o; done)
 out=build/exp/$name; mkdir -p $out
 slp=-fno-slp-vectorize

@@ -154,6 +154,7 @@ struct wld_ctx {
     DevBuf rcodes, rw;       // WLD_OPT_REF_SUMS: codes and weights in lane-class order (ref_layout_kernel)
     // the fp6 screen (fp6_prepare): weight codes, packed operands, constants
     DevBuf w6, f6a, f6b, f6marg;  // (f6marg: the per-site marginals of the complement-coded images)
+    DevBuf f6rec;                  // (the site records built from them: launch_fp6_records)
     DevBuf w4;                    // the weights' e2m1 codes, where the A image is fp4 (Fp6Screen::a4)
     Fp6Screen f6{};
     // the i8 one-plane screen's pre-multiplied images (i8img_prepare, at the
@@ -296,7 +297,7 @@ struct wld_ctx {
         // work queued on a borrowed stream (wld_set_stream) may still use the
         // buffers: it completes before they are freed
         if (stream && stream != own_stream) (void)hipStreamSynchronize(stream);
-        DevBuf *all[] = {&keep, &htab, &htab_kept, &site_index, &raw, &wraw, &codes, &w_pad, &wstats, &site_ok, &site_map, &planes, &frag, &rcodes, &rw, &w6, &w4, &f6a, &f6b, &f6marg, &i8a, &i8b, &tiles, &cand, &f6_pairs, &fp6_probe_buf,
+        DevBuf *all[] = {&keep, &htab, &htab_kept, &site_index, &raw, &wraw, &codes, &w_pad, &wstats, &site_ok, &site_map, &planes, &frag, &rcodes, &rw, &w6, &w4, &f6a, &f6b, &f6marg, &f6rec, &i8a, &i8b, &tiles, &cand, &f6_pairs, &fp6_probe_buf,
                          &seg_cnt, &seg_off, &chunk_total, &chunk_base, &counters, &chunk_left, &prog_n, &win_hi, &win_pairs, &sum_buf, &heat_buf, &heat_tiles, &heat_map, &an_buf, &an_tiles, &an_img, &mx_lists, &mx_cnt, &pt_tiles, &pt_stage, &pt_cnt, &pt_csr, &pt_run, &pt_words, &blk_brk, &blk_acc, &blk_map, &blk_tiles, &st_a, &st_b, &st_d,
                          &st_dp, &st_r2, &out_a, &out_b, &out_d, &out_dp, &out_r2};
         for (DevBuf *b : all) release(*b);
@@ -434,6 +435,7 @@ int fp6_prepare(wld_ctx *c) {
         WLD_TRY(ensure(c->f6a, fp6_a_bytes(c->LP, c->NP, c->f6.a4)));
     WLD_TRY(ensure(c->f6b, fp6_b_bytes(c->LP, c->NP)));
     WLD_TRY(ensure(c->f6marg, 2 * c->LP * sizeof(float)));
+    WLD_TRY(ensure(c->f6rec, fp6_rec_bytes(c->LP)));
     // (codes: zero past N, which the complement coding needs, pair_mfma.hip frag6_kernel)
     HIP_TRY(hipMemcpyAsync(c->w6.p, codes.data(), c->NP, hipMemcpyHostToDevice, c->stream));
     std::vector<uint8_t> codes4;  // (outlives the copy: the stream is synchronized below)
@@ -447,10 +449,14 @@ int fp6_prepare(wld_ctx *c) {
                  c->f6.shared, c->LP, c->NP, c->N, ptr<uint8_t>(c->f6a), ptr<uint8_t>(c->f6b), ptr<float>(c->f6marg),
                  c->stream);
     HIP_TRY(hipGetLastError());
+    // (the site records: of this load's marginals, W6, R and wv, all set above
+    // and changed by nothing but the next fp6_prepare)
+    c->f6.marg = ptr<float>(c->f6marg);
+    launch_fp6_records(c->f6, c->LP, c->f6rec.p, c->stream);
+    HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->f6.b6 = ptr<uint8_t>(c->f6b);
     c->f6.a6 = c->f6.shared ? c->f6.b6 : ptr<uint8_t>(c->f6a);  // (shared: the row tiles are read from b6)
-    c->f6.marg = ptr<float>(c->f6marg);
     c->fp6_ok = true;
     c->fp6_better = c->fp6_rel <= std::max(2.0 * c->i8_rel, 0.02);
     return WLD_OK;

@@ -519,9 +519,19 @@ struct Fp6Screen {
     // the restored sums by wv; the padded sequences are coded 0 in b6
     bool shared;
     float wv;
+    // the per-load site records of the tile-pair kernel's three-sum tests
+    // (launch_fp6_records; pair_common.hpp F6RowRec): fp6_rec_bytes(LP) bytes,
+    // built from marg, W6 and R at the load, so valid as long as those are;
+    // counts: held in count units (shared and wv a power of two)
+    const void *rec;
+    bool counts;
 };
 size_t fp6_a_bytes(size_t LP, size_t NP, bool a4);
 size_t fp6_b_bytes(size_t LP, size_t NP);
+size_t fp6_rec_bytes(size_t LP);
+// f: marg, W6, R, shared and wv set; writes LP sites' records to rec and sets
+// f.rec and f.counts
+void launch_fp6_records(Fp6Screen &f, size_t LP, void *rec, hipStream_t s);
 // w6: NP fp6 (e2m3) codes of the rounded weights (0 for padding: a padded
 // sequence reads as missing and must weigh nothing); wa: the codes the A
 // image holds, w6 itself or (a4) their e2m1 codes; marg: 2 LP floats.

@@ -471,6 +471,98 @@ __host__ __device__ __forceinline__ float f6q_lane_terms(const F6qAcc &acc, cons
 }
 // (written so that a NaN does not skip)
 __host__ __device__ __forceinline__ bool f6q_skip(float t1, float mlo, float mloc) { return t1 <= 0.0f && mlo >= mloc; }
+// The quick test on a one-sided cap (f6q_pair1; round 15).  f6q_pair bounds
+// P00 by cap2 = min(2 M_a - 2 p, 2 M_b - d); either side alone is an upper
+// bound of 2 P00 too, and the row side's makes the interval's upper end
+//   X0lo + (2 M_a - 2 p) = ((row + col) + 2 M_a) - p = cW - p,  cW = col + 2 W6
+// (row + 2 M_a = 2 (W6 - M_a) + 2 M_a = 2 W6: every value on the 1/16 grid
+// below 2^20, exact however it is associated), a term of the column site alone.
+// The upper end n(X) = fl(X t - q) is nondecreasing in X (t >= 0, one fmaf), and
+// cW - p >= X0lo + cap2, so the pair's nt' = max(|n(X0lo)|, |n(cW - p)|) >= its
+// nt: the proof above goes through with nt' for nt, and no slack term is
+// needed.  d is still formed for dmax.  On the synth sample with C4's
+// constants 54 of 1,984 row blocks fall through where f6q_pair leaves 32
+// (tests/cpp/f6_quick_units_check.cpp).
+// kTwice: ap is 2 p (the shared image's count of 2 C01, count units below)
+// and the halving rides in the three fmaf, each of which rounds a value that
+// is exact; acc.pmax is then kept in ap's units (f6q_pmax).
+template <bool kTwice>
+__host__ __device__ __forceinline__ float f6q_pair1(float ap, float s, float t, float ma2, float row, float mb,
+                                                    float col, float cW, F6qAcc &acc) {
+    const float d = s - t;
+    acc.dmax = fmaxf(acc.dmax, d);
+    acc.pmax = fmaxf(acc.pmax, ap);
+    const float rc = row + col;
+    const float y0 = kTwice ? fmaf(-0.5f, ap, mb) : mb - ap;
+    const float lo = kTwice ? fmaf(0.5f, ap, rc) : ap + rc;
+    const float hi = kTwice ? fmaf(-0.5f, ap, cW) : cW - ap;
+    const float q = -((ma2 - s) * y0);
+    const float nt = fmaxf(fabsf(fmaf(lo, t, q)), fabsf(fmaf(hi, t, q)));
+    acc.nt = fmaxf(acc.nt, nt);
+    return nt;
+}
+// the lane's pmax for f6q_lane_terms from f6q_pair1's
+template <bool kTwice>
+__host__ __device__ __forceinline__ void f6q_pmax(F6qAcc &acc) {
+    if (kTwice) acc.pmax *= 0.5f;
+}
+// Per-load site records (pair_mfma.hip fp6_records_kernel; round 15): what
+// f6t_row and f6t_col return depends on the load alone (W6, R, the site's
+// marginals), so it is formed once per load, by those very functions, and the
+// tile-pair kernel's epilogue reads it where every wave of every entry formed
+// it anew.  A row site's record is its F6tRow; a column site's its F6tCol with
+// cW = col + 2 W6 (f6q_pair1); the quick test's lane minima (f6q_row_min over
+// an aligned group of 4 sites, f6q_col_min over a tile's 4 sites of equal index
+// mod 16: both groupings are the kernel's, fixed per load) are records of
+// their own.  M = Ma2 / 2 and m = ma2 / 2 are exact, so f6c_rebuild reads
+// the same records.
+// Count units (inv = 1 / wv; the shared image of a load whose one weight
+// value wv is a power of two, 0.125 ... 4): every field is stored times inv,
+// and the quick test and the three-sum test take the shared image's counts as
+// they are (2 C01, 2 C10 + C11, C11), E / wv^2 and mloc / wv, where the scaled
+// path multiplies each count by wv first.  Every operation of f6q_pair,
+// f6q_pair1, f6q_lane_terms and r2_screen_terms_f6t is a sum, difference,
+// product, fmaf, minimum, maximum or absolute value of values each of which
+// scales by a fixed power of wv (the site terms, sums, d, p, the marginals and
+// mloc by wv; q, nt, nub and E by wv^2; the marginals' pair products by wv^2,
+// the product of the four by wv^4; thr_c by 1; t1 by wv^4), and scaling by a
+// power of two commutes with IEEE rounding where nothing under- or overflows:
+// magnitudes lie below 2^80 8^4, and the nonzero sums, marginals and their
+// products above 2^-16 8^-4.  (thr_c P alone can be smaller, under a tiny
+// threshold; but a skip needs thr_c P >= nub^2 >= E^2 > 2^-60 8^-4, so where
+// it could round differently both paths have t1 > 0.)  So the count-unit t1 is
+// the scaled path's times wv^-4 and mlo - mloc its difference times 1 / wv,
+// bit for bit wherever the sign is in question: every verdict is the same.
+// Other weight values keep the scaled path (inv = 1).
+struct alignas(8) F6RowRec {
+    F6tRow a;
+};
+struct alignas(16) F6ColRec {
+    F6tCol b;
+    float cW, pad;
+};
+struct alignas(16) F6MinRec {  // row group: c1, rA2, rA; column group: cB2, cB3, c4
+    float x, y, z, pad;
+};
+__host__ __device__ __forceinline__ F6RowRec f6_row_rec(float W6, float Ma, float ma, float R2, float inv) {
+    const F6tRow a = f6t_row(W6, Ma, ma, R2);
+    return F6RowRec{{a.rA * inv, a.rA2 * inv, a.c1 * inv, a.Ma2 * inv, a.ma2 * inv, a.row * inv}};
+}
+__host__ __device__ __forceinline__ F6ColRec f6_col_rec(float W6, float Mb, float mb, float R2, float inv) {
+    const F6tCol b = f6t_col(Mb, mb, R2);
+    return F6ColRec{{b.cB2 * inv, b.cB3 * inv, b.c4 * inv, b.Mb2 * inv, b.mb * inv, b.col * inv},
+                    fmaf(2.0f, W6, b.col) * inv, 0.0f};
+}
+__host__ __device__ __forceinline__ F6MinRec f6_row_min_rec(const F6RowRec (&r)[4]) {
+    F6qRowMin m{INFINITY, INFINITY, INFINITY};
+    for (int e = 0; e < 4; ++e) f6q_row_min(m, r[e].a);
+    return F6MinRec{m.c1, m.rA2, m.rA, 0.0f};
+}
+__host__ __device__ __forceinline__ F6MinRec f6_col_min_rec(const F6ColRec (&c)[4]) {
+    const F6tCol b[4] = {c[0].b, c[1].b, c[2].b, c[3].b};
+    const F6qColMin m = f6q_col_min(b);
+    return F6MinRec{m.cB2, m.cB3, m.c4, 0.0f};
+}
 __host__ __device__ __forceinline__ float r2_screen_violation(float T, float A, float B, float AB, float R,
                                                               float thr_c) {
     float E, mloc, t2;

@@ -1060,6 +1060,32 @@ __global__ __launch_bounds__(256) void fp6_marginals_kernel(const uint8_t *__res
     }
 }
 
+// The per-load site records of the tile-pair kernel's three-sum epilogue
+// (pair_common.hpp f6_row_rec ...): one thread per site writes its row and its
+// column record; the first site of an aligned group of 4 that group's row
+// minima, and the first 16 sites of a tile the column minima of the tile's
+// four sites of their index mod 16 (the lanes' groupings, pair_fp6_screen2w_kernel).
+// LP is a multiple of the tile, so every site read exists.
+__global__ __launch_bounds__(256) void fp6_records_kernel(const float2 *__restrict__ marg, float W6, float R2, float inv,
+                                                           uint32_t LP, F6RowRec *__restrict__ row,
+                                                           F6ColRec *__restrict__ col, F6MinRec *__restrict__ rmin,
+                                                           F6MinRec *__restrict__ cmin) {
+    const uint32_t s = blockIdx.x * 256 + threadIdx.x;
+    if (s >= LP) return;
+    auto row_of = [&](uint32_t i) { return f6_row_rec(W6, marg[i].x, marg[i].y, R2, inv); };
+    auto col_of = [&](uint32_t i) { return f6_col_rec(W6, marg[i].x, marg[i].y, R2, inv); };
+    row[s] = row_of(s);
+    col[s] = col_of(s);
+    if ((s & 3) == 0) {
+        const F6RowRec r[4] = {row_of(s), row_of(s + 1), row_of(s + 2), row_of(s + 3)};
+        rmin[s >> 2] = f6_row_min_rec(r);
+    }
+    if ((s & (kTile - 1)) < 16) {
+        const F6ColRec c[4] = {col_of(s), col_of(s + 16), col_of(s + 32), col_of(s + 48)};
+        cmin[(s >> 6) * 16 + (s & 15)] = f6_col_min_rec(c);
+    }
+}
+
 namespace {
 // a 16-site block's fp6 operand from its 1536 B LDS image: dwords 0-3, then
 // 4-5 (the empty asm keeps the compiler from pairing two blocks' b64 reads
@@ -1188,6 +1214,25 @@ struct F6Epi {
 // only here: 12 sites per lane, no register held across the stage loop).
 // kShared: the accumulators are the shared image's counts, scaled by the
 // load's one weight value wv on the way (f6s_direct: the same four values).
+// (row site e of the lane against its four column sites)
+template <bool kShared>
+__device__ __forceinline__ void f6c_rebuild_row(v4f (&acc)[4][2][2], int e, float row, float ma2,
+                                                const float (&col)[4], const float (&mb)[4], float wv) {
+#pragma unroll
+    for (int n = 0; n < 4; ++n) {
+        float x0 = acc[n][0][0][e], y0 = acc[n][0][1][e], x1 = acc[n][1][0][e];
+        if constexpr (kShared) {
+            float y1 = acc[n][1][1][e];
+            f6s_direct(x0, y0, x1, y1, row, col[n], ma2, mb[n], wv, 0.5f * wv);
+            acc[n][1][1][e] = y1;
+        } else {
+            f6c_direct(x0, y0, x1, row, col[n], ma2, mb[n]);
+        }
+        acc[n][0][0][e] = x0;
+        acc[n][0][1][e] = y0;
+        acc[n][1][0][e] = x1;
+    }
+}
 template <bool kShared>
 __device__ __forceinline__ void f6c_rebuild(v4f (&acc)[4][2][2], const float2 *sA, const float2 *sB, uint32_t wq,
                                             uint32_t lane, float W6, float wv) {
@@ -1201,21 +1246,35 @@ __device__ __forceinline__ void f6c_rebuild(v4f (&acc)[4][2][2], const float2 *s
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
         const float2 a = sA[16 * wq + 4 * (lane >> 4) + e];
-        const float row = f6c_row_term(W6, a.x), ma2 = 2.0f * a.y;
+        f6c_rebuild_row<kShared>(acc, e, f6c_row_term(W6, a.x), 2.0f * a.y, col, mb, wv);
+    }
+}
+// The entry's site records in LDS (pair_common.hpp F6RowRec ...; the three-sum
+// tile-pair kernel stages them with its first stage): the row tile's 64 row
+// records and 16 groups' minima, and this half's column tile's 64 column
+// records and 16 groups' minima.
+struct F6Site {
+    const F6RowRec *row;
+    const F6ColRec *col;
+    const F6MinRec *rmin, *cmin;
+};
+// f6c_rebuild from the records: row, 2 m_a, col and m_b are fields of theirs,
+// in weight units after an exact multiply by wv where the records hold count
+// units (kCounts).
+template <bool kShared, bool kCounts>
+__device__ __forceinline__ void f6c_rebuild_rec(v4f (&acc)[4][2][2], const F6Site &st, uint32_t wq, uint32_t lane,
+                                                float wv) {
+    float col[4], mb[4];
 #pragma unroll
-        for (int n = 0; n < 4; ++n) {
-            float x0 = acc[n][0][0][e], y0 = acc[n][0][1][e], x1 = acc[n][1][0][e];
-            if constexpr (kShared) {
-                float y1 = acc[n][1][1][e];
-                f6s_direct(x0, y0, x1, y1, row, col[n], ma2, mb[n], wv, 0.5f * wv);
-                acc[n][1][1][e] = y1;
-            } else {
-                f6c_direct(x0, y0, x1, row, col[n], ma2, mb[n]);
-            }
-            acc[n][0][0][e] = x0;
-            acc[n][0][1][e] = y0;
-            acc[n][1][0][e] = x1;
-        }
+    for (int n = 0; n < 4; ++n) {
+        const F6tCol &b = st.col[(lane & 15) + 16 * n].b;
+        col[n] = kCounts ? b.col * wv : b.col;
+        mb[n] = kCounts ? b.mb * wv : b.mb;
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const F6tRow &a = st.row[16 * wq + 4 * (lane >> 4) + e].a;
+        f6c_rebuild_row<kShared>(acc, e, kCounts ? a.row * wv : a.row, kCounts ? a.ma2 * wv : a.ma2, col, mb, wv);
     }
 }
 // The three-sum epilogue of one wave's 16 rows x 64 columns: is any of its
@@ -1225,19 +1284,20 @@ __device__ __forceinline__ void f6c_rebuild(v4f (&acc)[4][2][2], const float2 *s
 // pair not in doubt is rejected by the four-sum test too (pair_common.hpp
 // r2_screen_terms_xy2_t), so a wave without doubt has no candidate.  kShared:
 // the accumulators are counts, scaled by the load's one weight value (exact,
-// f6s_direct's argument).
-template <bool kShared>
-__device__ __forceinline__ bool f6t_any_doubt(const v4f (&acc)[4][2][2], const F6Epi &ep, const float2 *sA,
-                                              const float2 *sB, float W6, float wv) {
+// f6s_direct's argument); kCounts: they stay counts but for p's half, the
+// records and ep.E, ep.mloc being in count units (pair_common.hpp F6RowRec).
+// The sites' terms are read from the load's records (st).
+template <bool kShared, bool kCounts>
+__device__ __forceinline__ bool f6t_any_doubt(const v4f (&acc)[4][2][2], const F6Epi &ep, const F6Site &st, float wv) {
     F6tCol cb[4];
 #pragma unroll
-    for (int n = 0; n < 4; ++n) {
-        const float2 b = sB[(ep.lane & 15) + 16 * n];
-        cb[n] = f6t_col(b.x, b.y, ep.R2);
-    }
+    for (int n = 0; n < 4; ++n) cb[n] = st.col[(ep.lane & 15) + 16 * n].b;
     auto terms = [&](const F6tRow &ra, int n, int e, float &mlo) {
         float p = acc[n][0][1][e], s = acc[n][1][0][e], t = acc[n][1][1][e];
-        if constexpr (kShared) p *= 0.5f * wv, s *= wv, t *= wv;
+        if constexpr (kCounts)
+            p *= 0.5f;
+        else if constexpr (kShared)
+            p *= 0.5f * wv, s *= wv, t *= wv;
         return r2_screen_terms_f6t(p, s, t, ra, cb[n], ep.thr_c, ep.E, mlo);
     };
     if (ep.okA == ~0ull && ep.okB == ~0ull && ep.ta != ep.tb) {
@@ -1246,8 +1306,7 @@ __device__ __forceinline__ bool f6t_any_doubt(const v4f (&acc)[4][2][2], const F
         float mlo_all = INFINITY;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            const float2 a = sA[16 * ep.wq + 4 * (ep.lane >> 4) + e];
-            const F6tRow ra = f6t_row(W6, a.x, a.y, ep.R2);
+            const F6tRow ra = st.row[16 * ep.wq + 4 * (ep.lane >> 4) + e].a;
 #pragma unroll
             for (int n = 0; n < 4; ++n) {
                 float mlo;
@@ -1260,8 +1319,7 @@ __device__ __forceinline__ bool f6t_any_doubt(const v4f (&acc)[4][2][2], const F
     bool doubt = false;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-        const float2 a = sA[16 * ep.wq + 4 * (ep.lane >> 4) + e];
-        const F6tRow ra = f6t_row(W6, a.x, a.y, ep.R2);
+        const F6tRow ra = st.row[16 * ep.wq + 4 * (ep.lane >> 4) + e].a;
 #pragma unroll
         for (int n = 0; n < 4; ++n) {
             float mlo;
@@ -1279,28 +1337,36 @@ __device__ __forceinline__ bool f6t_any_doubt(const v4f (&acc)[4][2][2], const F
 // row blocks.  Padded and filtered pairs are tested as the others: one that
 // fails only sends the wave to f6t_any_doubt, which masks it (diagonal tiles
 // do not come here: f6t_wave_doubt).  The result is wave-uniform (one ballot).
-template <bool kShared>
-__device__ __forceinline__ bool f6t_quick_skip(const v4f (&acc)[4][2][2], const F6Epi &ep, const float2 *sA,
-                                               const F6tCol (&cb)[4], const F6qColMin &cm, float W6, float wv) {
-    F6qRowMin rm{INFINITY, INFINITY, INFINITY};
+// Round 15: the numerator on the one-sided cap (f6q_pair1), the sites' terms
+// and the lane's minima read from the load's records (st; a row site's 2 m_a
+// and row, the group's minima) instead of formed here, and with kCounts the
+// shared image's counts taken as they are (ep.E, ep.mloc in count units).
+struct F6qCol {  // what f6q_pair1 takes of a column site's record
+    float mb, col, cW;
+};
+template <bool kShared, bool kCounts>
+__device__ __forceinline__ bool f6t_quick_skip(const v4f (&acc)[4][2][2], const F6Epi &ep, const F6Site &st,
+                                               const F6qCol (&cb)[4], const F6qColMin &cm, float wv) {
+    const uint32_t grp = 4 * ep.wq + (ep.lane >> 4);
     F6qAcc q;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-        const float2 a = sA[16 * ep.wq + 4 * (ep.lane >> 4) + e];
-        const F6tRow ra = f6t_row(W6, a.x, a.y, ep.R2);
-        f6q_row_min(rm, ra);
+        const F6tRow &ra = st.row[4 * grp + e].a;
+        const float ma2 = ra.ma2, row = ra.row;
 #pragma unroll
         for (int n = 0; n < 4; ++n) {
             float p = acc[n][0][1][e], s = acc[n][1][0][e], t = acc[n][1][1][e];
-            if constexpr (kShared) p *= 0.5f * wv, s *= wv, t *= wv;
-            f6q_pair(p, s, t, ra, cb[n], q);
+            if constexpr (kShared && !kCounts) p *= 0.5f * wv, s *= wv, t *= wv;
+            f6q_pair1<kCounts>(p, s, t, ma2, row, cb[n].mb, cb[n].col, cb[n].cW, q);
             // (one pair at a time: left to itself the scheduler interleaves
             // the 32 pairs' chains, and the accumulators spill)
             __builtin_amdgcn_sched_barrier(0);
         }
     }
+    f6q_pmax<kCounts>(q);
+    const F6MinRec r = st.rmin[grp];
     float mlo;
-    const float t1 = f6q_lane_terms(q, rm, cm, ep.thr_c, ep.E, mlo);
+    const float t1 = f6q_lane_terms(q, F6qRowMin{r.x, r.y, r.z}, cm, ep.thr_c, ep.E, mlo);
     return __ballot(!f6q_skip(t1, mlo, ep.mloc)) == 0;
 }
 // Is any pair of the wave's two row blocks in doubt on three sums?  kQuick: a
@@ -1316,21 +1382,22 @@ __device__ __forceinline__ bool f6t_quick_skip(const v4f (&acc)[4][2][2], const 
 // through empty statements, in place and at no instruction).  Values the
 // compiler keeps live across the quick test for it cost the registers the
 // accumulators need: they spill.
-template <bool kShared, bool kQuick>
+template <bool kShared, bool kQuick, bool kCounts>
 __device__ __forceinline__ bool f6t_wave_doubt(v4f (&acc)[2][4][2][2], const F6Epi &ep0, const F6Epi &ep1,
-                                               const float2 *sA, const float2 *sB, float W6, float wv, uint32_t *full) {
+                                               const F6Site &st, float wv, uint32_t *full) {
     if constexpr (kQuick) {
         bool full0 = true, full1 = true;  // (uniform)
         if (ep0.ta != ep0.tb) {
-            F6tCol cb[4];
+            F6qCol cb[4];
 #pragma unroll
             for (int n = 0; n < 4; ++n) {
-                const float2 b = sB[(ep0.lane & 15) + 16 * n];
-                cb[n] = f6t_col(b.x, b.y, ep0.R2);
+                const F6ColRec &b = st.col[(ep0.lane & 15) + 16 * n];
+                cb[n] = F6qCol{b.b.mb, b.b.col, b.cW};
             }
-            const F6qColMin cm = f6q_col_min(cb);
-            full0 = !f6t_quick_skip<kShared>(acc[0], ep0, sA, cb, cm, W6, wv);
-            full1 = !f6t_quick_skip<kShared>(acc[1], ep1, sA, cb, cm, W6, wv);
+            const F6MinRec c = st.cmin[ep0.lane & 15];
+            const F6qColMin cm{c.x, c.y, c.z};
+            full0 = !f6t_quick_skip<kShared, kCounts>(acc[0], ep0, st, cb, cm, wv);
+            full1 = !f6t_quick_skip<kShared, kCounts>(acc[1], ep1, st, cb, cm, wv);
             if ((full0 || full1) && ep0.lane == 0) atomicAdd(full, (uint32_t)full0 + (uint32_t)full1);
         }
         uint32_t lane = ep0.lane;
@@ -1341,11 +1408,10 @@ __device__ __forceinline__ bool f6t_wave_doubt(v4f (&acc)[2][4][2][2], const F6E
             for (int n = 0; n < 4; ++n) asm volatile("" : "+v"(acc[j][n][1][1]));
         F6Epi e0 = ep0, e1 = ep1;
         e0.lane = e1.lane = lane;
-        return (full0 && f6t_any_doubt<kShared>(acc[0], e0, sA, sB, W6, wv)) ||
-               (full1 && f6t_any_doubt<kShared>(acc[1], e1, sA, sB, W6, wv));
+        return (full0 && f6t_any_doubt<kShared, kCounts>(acc[0], e0, st, wv)) ||
+               (full1 && f6t_any_doubt<kShared, kCounts>(acc[1], e1, st, wv));
     }
-    return f6t_any_doubt<kShared>(acc[0], ep0, sA, sB, W6, wv) ||
-           f6t_any_doubt<kShared>(acc[1], ep1, sA, sB, W6, wv);
+    return f6t_any_doubt<kShared, kCounts>(acc[0], ep0, st, wv) || f6t_any_doubt<kShared, kCounts>(acc[1], ep1, st, wv);
 }
 }  // namespace
 
@@ -1515,16 +1581,46 @@ extern "C" int wld_debug_f6_clock(unsigned long long *out) {
 // the row blocks where some lane cannot (counted in sQuickFull, then by one
 // atomic per workgroup that has any).  The branch is wave-uniform and lies
 // between the same barriers.
-template <int kFmt, bool kThree = false, bool kQuick = false>
+// Round 15 (kThree): the sites' terms of the three-sum tests are not formed
+// from {M, m} by every wave of every entry but read from the load's records
+// (F6Recs; pair_common.hpp F6RowRec ...), 6.25 KB per entry staged where the
+// four-sum kernel stages its 1.5 KB of marginals; f6c_rebuild after a second
+// pass reads the same records.  kCounts (the shared image of a load whose one
+// weight value is a power of two): the records, E and mloc are in count units
+// and the quick and three-sum tests take the accumulators' counts unscaled.
+struct F6Recs {  // (launch_fp6_records; device pointers)
+    const F6ColRec *col;
+    const F6RowRec *row;
+    const F6MinRec *rmin, *cmin;
+    float inv;  // the records' unit: 1 / wv in count units, else 1
+};
+constexpr int kF6SiteCol = 0, kF6SiteRow = 2 * kTile * sizeof(F6ColRec), kF6SiteRmin = kF6SiteRow + kTile * sizeof(F6RowRec),
+              kF6SiteCmin = kF6SiteRmin + kTile / 4 * sizeof(F6MinRec),
+              kF6SiteBytes = kF6SiteCmin + 2 * 16 * sizeof(F6MinRec);
+static_assert(sizeof(F6ColRec) == 32 && sizeof(F6RowRec) == 24 && sizeof(F6MinRec) == 16 && kF6SiteBytes == 6400 &&
+                  kF6SiteRow % 16 == 0 && kF6SiteRmin % 16 == 0,
+              "the entry's records are staged as 400 16-byte pieces");
+// a half's view of the entry's records in LDS
+__device__ __forceinline__ F6Site f6_site_of(const uint8_t *site, uint32_t half) {
+    return F6Site{reinterpret_cast<const F6RowRec *>(site + kF6SiteRow),
+                  reinterpret_cast<const F6ColRec *>(site + kF6SiteCol) + kTile * half,
+                  reinterpret_cast<const F6MinRec *>(site + kF6SiteRmin),
+                  reinterpret_cast<const F6MinRec *>(site + kF6SiteCmin) + 16 * half};
+}
+template <int kFmt, bool kThree = false, bool kQuick = false, bool kCounts = false>
 __global__ __launch_bounds__(256, 3) void pair_fp6_screen2w_kernel(
     const uint8_t *__restrict__ a6, const uint8_t *__restrict__ b6, const float2 *__restrict__ marg, float W6,
     const uint64_t *__restrict__ ok_bits,
     const uint32_t *__restrict__ pairs, uint32_t n_pairs, uint32_t NK, uint32_t L, uint32_t n_chunk_rows, float thr,
-    OrderArgs o, ScreenArgs sc, float wv) {
+    OrderArgs o, ScreenArgs sc, float wv, F6Recs rec) {
     using F = F6Fmt<kFmt>;
     constexpr int kF6AStage = F::kAStage, kF6ABytes = F::kABytes, kF6PStage = F::kPStage;
+    static_assert(!kCounts || (kThree && F::kShared), "count units: the shared image's three-sum tests");
     __shared__ __attribute__((aligned(16))) uint8_t smem[2 * kF6PStage];
-    __shared__ float2 sMarg[3 * kTile];  // {M, m} of the row tile's sites, then each half's column tile's
+    // four sums: {M, m} of the row tile's sites, then each half's column
+    // tile's; kThree: the entry's site records (kF6Site... offsets)
+    __shared__ __attribute__((aligned(kThree ? 16 : 8))) uint8_t sSite[kThree ? kF6SiteBytes : 3 * kTile * sizeof(float2)];
+    const float2 *const sMarg = reinterpret_cast<const float2 *>(sSite);
     __shared__ unsigned long long sMask[2];
     __shared__ uint32_t sBail, sCand[2];
     __shared__ uint32_t sDoubt[2];  // kThree: some pair of the half's tile is in doubt on three sums
@@ -1576,9 +1672,23 @@ __global__ __launch_bounds__(256, 3) void pair_fp6_screen2w_kernel(
         // the entry's marginals (1.5 KB), in flight with the first stage,
         // published by its barrier and read by the epilogue alone (a single
         // entry's second column tile is its first, as its B image)
-        if (tid < 3 * kTile) {
+        if constexpr (kThree) {
+            // (the records instead: every thread a 16-byte piece of the two
+            // column tiles' records, threads 0-95 the row tile's, 96-111 its
+            // groups' minima, 112-143 the column tiles' groups' minima)
+            const uint32_t tb1 = tb0 + (single ? 0u : 1u);
+            uint4 *const dst = reinterpret_cast<uint4 *>(sSite);
+            dst[tid] = reinterpret_cast<const uint4 *>(rec.col + (tid < 128 ? tb0 : tb1) * kTile)[tid & 127];
+            if (tid < 96)
+                dst[kF6SiteRow / 16 + tid] = reinterpret_cast<const uint4 *>(rec.row + ta * kTile)[tid];
+            else if (tid < 112)
+                dst[kF6SiteRmin / 16 + (tid - 96)] = reinterpret_cast<const uint4 *>(rec.rmin + ta * (kTile / 4))[tid - 96];
+            else if (tid < 144)
+                dst[kF6SiteCmin / 16 + (tid - 112)] =
+                    reinterpret_cast<const uint4 *>(rec.cmin + (tid < 128 ? tb0 : tb1) * 16)[tid & 15];
+        } else if (tid < 3 * kTile) {
             const uint32_t t = tid < kTile ? ta : tb0 + ((tid >= 2 * kTile && !single) ? 1u : 0u);
-            sMarg[tid] = marg[t * kTile + (tid & (kTile - 1))];
+            reinterpret_cast<float2 *>(sSite)[tid] = marg[t * kTile + (tid & (kTile - 1))];
         }
         if (tid == 0) {  // the give-up test (as the single-tile kernel)
             uint32_t v = 0;
@@ -1671,9 +1781,12 @@ __global__ __launch_bounds__(256, 3) void pair_fp6_screen2w_kernel(
         const F6Epi ep0{ta, tb, 2 * rp, lane, okA, okB, 2.0f * sc.Rf, thr * (1.0f - 0x1p-7f), sc.E, sc.mloc};
         const F6Epi ep1{ta, tb, 2 * rp + 1, lane, okA, okB, 2.0f * sc.Rf, thr * (1.0f - 0x1p-7f), sc.E, sc.mloc};
         if constexpr (kThree) {
-            const float2 *sB = sMarg + kTile * (1 + half);
+            const F6Site st = f6_site_of(sSite, half);
+            F6Epi t0 = ep0, t1 = ep1;  // (the three-sum tests' E and mloc in the records' unit: exact)
+            t0.E = t1.E = kCounts ? sc.E * rec.inv * rec.inv : sc.E;
+            t0.mloc = t1.mloc = kCounts ? sc.mloc * rec.inv : sc.mloc;
             const bool doubt =
-                !idle && f6t_wave_doubt<F::kShared, kQuick>(acc, ep0, ep1, sMarg, sB, W6, wv, &sQuickFull);
+                !idle && f6t_wave_doubt<F::kShared, kQuick, kCounts>(acc, t0, t1, st, wv, &sQuickFull);
             if (doubt) sDoubt[half] = 1u;  // (benign race: every writer stores 1)
             // every wave's LDS reads of the first pass lie before this barrier
             // (the last stage's wait, the marginals just read)
@@ -1729,8 +1842,14 @@ __global__ __launch_bounds__(256, 3) void pair_fp6_screen2w_kernel(
             }
         }
         if (!idle) {
-            f6c_rebuild<F::kShared>(acc[0], sMarg, sMarg + kTile * (1 + half), 2 * rp, lane, W6, wv);
-            f6c_rebuild<F::kShared>(acc[1], sMarg, sMarg + kTile * (1 + half), 2 * rp + 1, lane, W6, wv);
+            if constexpr (kThree) {
+                const F6Site st = f6_site_of(sSite, half);
+                f6c_rebuild_rec<F::kShared, kCounts>(acc[0], st, 2 * rp, lane, wv);
+                f6c_rebuild_rec<F::kShared, kCounts>(acc[1], st, 2 * rp + 1, lane, wv);
+            } else {
+                f6c_rebuild<F::kShared>(acc[0], sMarg, sMarg + kTile * (1 + half), 2 * rp, lane, W6, wv);
+                f6c_rebuild<F::kShared>(acc[1], sMarg, sMarg + kTile * (1 + half), 2 * rp + 1, lane, W6, wv);
+            }
         }
         const bool cand = !idle && (ep0.any(acc[0]) || ep1.any(acc[1]));
         if (cand) sCand[half] = 1u;  // (benign race: every writer stores 1)
@@ -1947,6 +2066,40 @@ void launch_frag6(const uint8_t *codes, const uint8_t *w6, const uint8_t *wa, bo
                        (uint32_t)NP, marg);
 }
 
+namespace {
+// the fp6 screen's R of a load (fp6_prepare's Fp6Screen::R) as every pass and
+// the load's site records take it: rounded up to a multiple of 1/32, so the
+// doubled R2 = 2 R lies on the accumulators' grid (1/8 or 1/16: the exact
+// marginals of r2_screen_terms_xy2 / _fg; exact in f32, R <= the sum of the
+// fp6 weights < 2^17)
+double fp6_screen_R(const Fp6Screen &f) { return std::ceil(f.R * 32.0) / 32.0; }
+// one buffer: LP column records, LP row records, LP / 4 and LP / 4 group minima
+// (LP is a multiple of 256, so every part starts on 16 bytes)
+F6Recs fp6_recs_of(const void *rec, size_t LP, float inv) {
+    const uint8_t *p = static_cast<const uint8_t *>(rec);
+    F6Recs r;
+    r.col = reinterpret_cast<const F6ColRec *>(p);
+    r.row = reinterpret_cast<const F6RowRec *>(p + LP * sizeof(F6ColRec));
+    r.rmin = reinterpret_cast<const F6MinRec *>(p + LP * (sizeof(F6ColRec) + sizeof(F6RowRec)));
+    r.cmin = r.rmin + LP / 4;
+    r.inv = inv;
+    return r;
+}
+}  // namespace
+size_t fp6_rec_bytes(size_t LP) {
+    return LP * (sizeof(F6ColRec) + sizeof(F6RowRec)) + (LP / 4 + LP / kTile * 16) * sizeof(F6MinRec);
+}
+void launch_fp6_records(Fp6Screen &f, size_t LP, void *rec, hipStream_t s) {
+    int e = 0;
+    f.counts = f.shared && std::frexp(f.wv, &e) == 0.5f;  // (a power of two: 1 / wv and every multiple by it exact)
+    f.rec = rec;
+    const F6Recs r = fp6_recs_of(rec, LP, f.counts ? 1.0f / f.wv : 1.0f);
+    hipLaunchKernelGGL(fp6_records_kernel, dim3((unsigned)((LP + 255) / 256)), dim3(256), 0, s,
+                       reinterpret_cast<const float2 *>(f.marg), f.W6, 2.0f * (float)fp6_screen_R(f), r.inv,
+                       (uint32_t)LP, const_cast<F6RowRec *>(r.row), const_cast<F6ColRec *>(r.col),
+                       const_cast<F6MinRec *>(r.rmin), const_cast<F6MinRec *>(r.cmin));
+}
+
 // Site-major variant (one tile per workgroup, codes read straight into
 // registers, all three digit planes): the reference for the LDS path's race
 // screen (WLD_OPT_MFMA_LAYOUT).
@@ -2085,12 +2238,13 @@ void launch_candidates(const MfmaLaunch &m, uint32_t n, uint32_t idx, const uint
 }  // namespace
 
 namespace {
-// the fp6 screen's R, E, mloc in its own units (fp6_prepare): R rounded up to
-// a multiple of 1/32, so the doubled R2 = 2 R lies on the accumulators' grid
-// (1/8 or 1/16: the exact marginals of r2_screen_terms_xy2 / _fg; exact in f32,
-// R <= the sum of the fp6 weights < 2^17); Tg bounds every doubled T
+// the fp6 screen's R, E, mloc in its own units (fp6_prepare): R on the 1/32
+// grid (fp6_screen_R); Tg bounds every doubled T.  R is the load's: no
+// option, window or pass enters it (the reference order's and the fixed
+// point's allowances are both inside Fp6Screen::R), so the load's site records
+// (launch_fp6_records), built with the same fp6_screen_R, hold every pass's R2.
 void fp6_screen_args(const MfmaLaunch &m, ScreenArgs &sc) {
-    sc.R = std::ceil(m.fp6->R * 32.0) / 32.0;
+    sc.R = fp6_screen_R(*m.fp6);
     sc.Rf = (float)sc.R;
     sc.f32 = 2;
     screen_consts(m.fp6->Tg, 2.0f * sc.Rf, sc.E, sc.mloc);
@@ -2100,24 +2254,29 @@ void fp6_screen_args(const MfmaLaunch &m, ScreenArgs &sc) {
 template <int kFmt>
 void launch_fp6_screen_fmt(const MfmaLaunch &m, const uint64_t *ok_bits, const OrderArgs &o, const ScreenArgs &sc,
                            uint32_t stride, hipStream_t s) {
+    // (the records' unit: count units only in the shared format's kernels)
+    const bool counts = kFmt == kF6Shared && m.fp6->counts;
+    const F6Recs rec = fp6_recs_of(m.fp6->rec, m.LP, counts ? 1.0f / m.fp6->wv : 1.0f);
+    auto pairs = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((m.f6_n_pairs + stride - 1) / stride), dim3(256), 0, s, m.fp6->a6, m.fp6->b6,
+                           reinterpret_cast<const float2 *>(m.fp6->marg), m.fp6->W6, ok_bits, m.f6_pairs, m.f6_n_pairs,
+                           m.fp6->NK, m.L, m.n_chunk_rows, m.thr, o, sc, m.fp6->wv, rec);
+    };
     if (m.f6_pairs && m.fp6_three && m.fp6_quick) {
         // (three sums per pair behind the lane-shared quick test)
-        hipLaunchKernelGGL((pair_fp6_screen2w_kernel<kFmt, true, true>), dim3((m.f6_n_pairs + stride - 1) / stride),
-                           dim3(256), 0, s, m.fp6->a6, m.fp6->b6, reinterpret_cast<const float2 *>(m.fp6->marg),
-                           m.fp6->W6, ok_bits, m.f6_pairs, m.f6_n_pairs, m.fp6->NK, m.L, m.n_chunk_rows, m.thr, o, sc,
-                           m.fp6->wv);
+        if constexpr (kFmt == kF6Shared) {
+            if (counts) return pairs(pair_fp6_screen2w_kernel<kFmt, true, true, true>);
+        }
+        pairs(pair_fp6_screen2w_kernel<kFmt, true, true>);
     } else if (m.f6_pairs && m.fp6_three) {
         // (three sums per pair, the fourth where an entry needs it)
-        hipLaunchKernelGGL((pair_fp6_screen2w_kernel<kFmt, true>), dim3((m.f6_n_pairs + stride - 1) / stride),
-                           dim3(256), 0, s, m.fp6->a6, m.fp6->b6, reinterpret_cast<const float2 *>(m.fp6->marg),
-                           m.fp6->W6, ok_bits, m.f6_pairs, m.f6_n_pairs, m.fp6->NK, m.L, m.n_chunk_rows, m.thr, o, sc,
-                           m.fp6->wv);
+        if constexpr (kFmt == kF6Shared) {
+            if (counts) return pairs(pair_fp6_screen2w_kernel<kFmt, true, false, true>);
+        }
+        pairs(pair_fp6_screen2w_kernel<kFmt, true>);
     } else if (m.f6_pairs) {
         // (a tile group per workgroup, the XCD-ordered group list)
-        hipLaunchKernelGGL(pair_fp6_screen2w_kernel<kFmt>, dim3((m.f6_n_pairs + stride - 1) / stride), dim3(256), 0, s,
-                           m.fp6->a6, m.fp6->b6, reinterpret_cast<const float2 *>(m.fp6->marg), m.fp6->W6, ok_bits,
-                           m.f6_pairs, m.f6_n_pairs, m.fp6->NK, m.L, m.n_chunk_rows,
-                           m.thr, o, sc, m.fp6->wv);
+        pairs(pair_fp6_screen2w_kernel<kFmt>);
     } else {
         // (one tile per workgroup, the XCD-ordered list)
         hipLaunchKernelGGL(pair_fp6_screen_kernel<kFmt>, dim3((m.n_tiles + stride - 1) / stride), dim3(256), 0, s,
