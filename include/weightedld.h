@@ -989,6 +989,62 @@ int wld_banded_apply_device(wld_ctx *ctx, const void *d_band, int band_dtype, si
                             uint32_t bandwidth, const void *d_x, int x_dtype, size_t ldx, uint32_t n_cols, double *d_y,
                             size_t ldy);
 
+/* The banded Cholesky factorisation and its triangular solves, on the device.
+ * Like wld_banded_apply_device the context supplies only the device and the
+ * stream; no load is needed, n_sites is the caller's, every pointer is device
+ * memory of the context's device, and each call returns after its work has
+ * completed.
+ *
+ * Matrix.  A is the symmetric matrix of the band d_band as wld_banded_apply_
+ * device reads it (WLD_MATRIX_F32 or _F16, ld >= K + 1, elements with i + k >=
+ * n_sites never read), every element converted to f64, with the diagonal
+ * fl(fl(B[i][0] + ridge) + d_diag[i]) (the second addition skipped when d_diag
+ * is NULL).  That rounded value is the definition of A.
+ *
+ * Factor.  A = U^T U, U upper triangular with U[i][i] > 0, in the same band
+ * layout in f64: d_factor[i * ldf + k] = U(i, i + k), ldf >= K + 1.  Every
+ * element of [n_sites] x [K + 1] is written, those with i + k >= n_sites with
+ * +0.0; nothing else is touched, the padding between rows included.  d_factor
+ * must not overlap the band.  Every element is produced by one owner in a
+ * fixed order without atomics: two calls give identical bytes.
+ *
+ * A matrix that is not positive definite is a result, not an error: where a
+ * pivot is not > 0 (NaN included) the call returns WLD_OK with first_bad = that
+ * row; the factor's rows [0, 64 * floor(first_bad / 64)) are the valid factor
+ * rows of the leading block, the rest is unspecified.  No pivot is replaced.
+ *
+ * Solve.  wld_banded_solve_device overwrites the n_cols columns of d_b
+ * ([n_sites][ldb] f64, ldb >= n_cols, n_cols >= 1 with no upper limit) with the
+ * solution of U^T y = b (WLD_SOLVE_FORWARD), U x = y (_BACKWARD) or A x = b
+ * (_FULL: forward, then backward).  Diagonal blocks are solved by
+ * substitution, never through an inverse.  Neither the factor nor b is
+ * validated; non-finite values propagate (the solve runs on 64x64 blocks
+ * padded with zeros, so a non-finite entry can reach any row within 64 + K
+ * sites of it).  Deterministic as above.  For e ~ N(0, I) the _BACKWARD
+ * solution has covariance A^-1; the _FORWARD solution of b ~ N(0, A) is white.
+ *
+ * WLD_E_ARG: a null pointer, n_sites or n_cols 0, ld or ldf < K + 1, ldb <
+ * n_cols, an unknown dtype or mode, a non-finite ridge, d_factor overlapping
+ * d_band.  WLD_E_STATE: while a run is in flight, on a device group.
+ * wld_last_stats, the last run's rows and every cached list stay as they were. */
+typedef struct {
+    uint32_t n_sites, bandwidth;
+    uint32_t first_bad; /* n_sites: positive definite; else the first row whose pivot was not > 0 (NaN included) */
+    double min_pivot;   /* smallest U[i][0] over the rows factored (a conditioning hint) */
+    double kernel_ms;   /* HIP-event time of the launches */
+} wld_banded_chol_info;
+
+int wld_banded_cholesky_device(wld_ctx *ctx, const void *d_band, int band_dtype, size_t ld, uint32_t n_sites,
+                               uint32_t bandwidth, double ridge, const double *d_diag /* n_sites, may be NULL */,
+                               double *d_factor, size_t ldf, wld_banded_chol_info *out);
+
+#define WLD_SOLVE_FULL 0     /* A x = b   */
+#define WLD_SOLVE_FORWARD 1  /* U^T y = b */
+#define WLD_SOLVE_BACKWARD 2 /* U x = y   */
+int wld_banded_solve_device(wld_ctx *ctx, const double *d_factor, size_t ldf, uint32_t n_sites, uint32_t bandwidth,
+                            int mode, double *d_b /* [n_sites][ldb], overwritten by the solution */, size_t ldb,
+                            uint32_t n_cols, double *kernel_ms /* may be NULL */);
+
 /* ---- LD pruning: a greedy r2-independent site set with tags (not in the
  * reference; PLINK's --indep-pairwise, bcftools +prune) ----
  *

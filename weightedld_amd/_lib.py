@@ -158,6 +158,17 @@ class MatrixInfoC(ctypes.Structure):
 
 
 APPLY_X_F32, APPLY_X_F64 = 0, 1  # WLD_APPLY_X_*
+SOLVE_MODES = {"full": 0, "forward": 1, "backward": 2}  # WLD_SOLVE_*
+
+
+class BandedCholInfoC(ctypes.Structure):
+    _fields_ = [
+        ("n_sites", ctypes.c_uint32),
+        ("bandwidth", ctypes.c_uint32),
+        ("first_bad", ctypes.c_uint32),
+        ("min_pivot", ctypes.c_double),
+        ("kernel_ms", ctypes.c_double),
+    ]
 
 
 class MatrixBandedInfoC(ctypes.Structure):
@@ -371,6 +382,10 @@ SIGNATURES = {
                                      ctypes.POINTER(MatrixBandedInfoC)]),
     "wld_banded_apply_device": (_int, [_vp, _vp, _int, _sz, ctypes.c_uint32, ctypes.c_uint32, _vp, _int, _sz,
                                        ctypes.c_uint32, _vp, _sz]),
+    "wld_banded_cholesky_device": (_int, [_vp, _vp, _int, _sz, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_double, _vp, _vp,
+                                          _sz, ctypes.POINTER(BandedCholInfoC)]),
+    "wld_banded_solve_device": (_int, [_vp, _vp, _sz, ctypes.c_uint32, ctypes.c_uint32, _int, _vp, _sz, ctypes.c_uint32,
+                                       ctypes.POINTER(ctypes.c_double)]),
     "wld_run_prune": (_int, [_vp, ctypes.c_float, _f32p, ctypes.POINTER(Prune)]),
     "wld_prune_free": (None, [ctypes.POINTER(Prune)]),
     "wld_loaded_sites": (_sz, [_vp]),

@@ -15,14 +15,14 @@ import numpy as np
 
 from ._lib import (ANNOT_MAX, ANNOT_SELF, AnnotScoresC, BLOCKS_ABS_DPRIME, BLOCKS_ALL, BLOCKS_NONE, BLOCKS_R2, BLOCKS_SPINE, BlockBreaksC, BlocksC,
                    HEAT_ABS_DPRIME, HEAT_MAX_CELLS, HEAT_R2, KERNEL_AUTO, KERNEL_MFMA, KERNEL_VALU, MATRIX_F16, MATRIX_F32,
-                   MATRIX_STATS, MATRIX_ZERO_MISSING, APPLY_X_F32, APPLY_X_F64, MatrixBandedInfoC, MatrixInfoC, OPTIONS,
+                   MATRIX_STATS, MATRIX_ZERO_MISSING, APPLY_X_F32, APPLY_X_F64, SOLVE_MODES, BandedCholInfoC, MatrixBandedInfoC, MatrixInfoC, OPTIONS,
                    PARTNERS_MAX_K, PARTNERS_NONE, PROGRESS_FN, Heatmap, Pairs, PartnersC, Prune, RunStats, Summary,
                    TargetRowsC, WldError, check, lib)
 
 __all__ = [
     "Symbol", "SymbolHistogram", "SiteSet", "LdStats", "PairStore", "read_fasta", "read_vcf",
     "is_site_of_interest", "henikoff_weights", "single_weighted_ld_pair", "all_weighted_ld_pairs",
-    "ld_summary", "LdSummary", "ld_heatmap", "LdHeatmap", "heatmap_cells", "ld_annot_scores", "LdAnnotScores", "annot_matrix", "ANNOT_MAX", "ld_matrix", "LdMatrixInfo", "matrix_args", "matrix_region", "ld_banded", "LdBandedInfo", "banded_args", "banded_from_dense", "banded_to_dense", "banded_matmul_host", "banded_cg_solve", "ld_prune", "LdPrune", "maf_priority", "ld_targets", "TargetRows", "ld_partners", "LdPartners", "PARTNERS_MAX_K", "PARTNERS_NONE", "ld_blocks", "LdBlocks", "LdBlockBreaks", "BLOCKS_NONE", "Context", "default_context", "KERNEL_AUTO", "KERNEL_VALU", "KERNEL_MFMA", "OPTIONS", "WldError",
+    "ld_summary", "LdSummary", "ld_heatmap", "LdHeatmap", "heatmap_cells", "ld_annot_scores", "LdAnnotScores", "annot_matrix", "ANNOT_MAX", "ld_matrix", "LdMatrixInfo", "matrix_args", "matrix_region", "ld_banded", "LdBandedInfo", "banded_args", "banded_from_dense", "banded_to_dense", "banded_matmul_host", "banded_cg_solve", "banded_cholesky_host", "banded_solve_host", "banded_logdet", "banded_chol_args", "banded_solve_args", "LdBandedCholInfo", "ld_prune", "LdPrune", "maf_priority", "ld_targets", "TargetRows", "ld_partners", "LdPartners", "PARTNERS_MAX_K", "PARTNERS_NONE", "ld_blocks", "LdBlocks", "LdBlockBreaks", "BLOCKS_NONE", "Context", "default_context", "KERNEL_AUTO", "KERNEL_VALU", "KERNEL_MFMA", "OPTIONS", "WldError",
 ]
 
 
@@ -552,6 +552,190 @@ def banded_cg_solve(apply, B, b, ridge=0.0, tol=1e-8, max_iter=None):
         p = r + (rs_new / rs) * p
         rs = rs_new
     return x, it, rs ** 0.5 / bnorm, False
+
+
+LdBandedCholInfo = namedtuple("LdBandedCholInfo", ["ok", "first_bad", "min_pivot", "kernel_ms"])
+LdBandedCholInfo.__doc__ = """wld_banded_chol_info (Context.banded_cholesky): ok, True when every pivot was > 0;
+first_bad, None when ok, else the first row whose pivot was not > 0 (NaN included); min_pivot, the smallest U[i, 0] of the
+rows factored (a conditioning hint); kernel_ms."""
+
+
+def _band_f64(B, ridge, diag):
+    """(A's band in float64 with the shifted diagonal, n, K) of the host twins: the diagonal is
+    fl(fl(B[i, 0] + ridge) + diag[i]), the device's own rounding."""
+    B = np.asarray(B)
+    if B.ndim != 2 or B.shape[0] < 1 or B.shape[1] < 1:
+        raise ValueError("B must be a [n, K + 1] band")
+    ridge = float(ridge)
+    if not np.isfinite(ridge):
+        raise ValueError("ridge must be finite")
+    n = B.shape[0]
+    A = B.astype(np.float64)
+    A[:, 0] = A[:, 0] + ridge
+    if diag is not None:
+        diag = np.asarray(diag, dtype=np.float64)
+        if diag.shape != (n,):
+            raise ValueError("diag must be [n] with n = %d" % n)
+        A[:, 0] = A[:, 0] + diag
+    return A, n, B.shape[1] - 1
+
+
+def banded_cholesky_host(B, ridge=0.0, diag=None):
+    """The host twin of Context.banded_cholesky, in float64: the plain
+    row-oriented Cholesky factorisation A = U^T U of the symmetric matrix A of
+    the band B ([n, K + 1]) with the diagonal fl(fl(B[i, 0] + ridge) +
+    diag[i]).  Returns (U_band, first_bad): U_band [n, K + 1] float64 in the
+    same layout (U_band[i, k] = U[i, i + k], +0.0 where i + k >= n), first_bad
+    None when every pivot was > 0, else the first row whose pivot was not (the
+    rows before it are valid, the rest is zero).  Elements with i + k >= n are
+    not read.  numpy."""
+    A, n, K = _band_f64(B, ridge, diag)
+    Kc = min(K, n - 1)
+    U = np.zeros((n, K + 1), dtype=np.float64)
+    for i in range(n):
+        m = min(Kc, n - 1 - i)
+        row = A[i, :m + 1].copy()
+        for p in range(max(0, i - Kc), i):
+            d = i - p
+            ln = min(m + 1, Kc + 1 - d)
+            row[:ln] -= U[p, d] * U[p, d:d + ln]
+        if not row[0] > 0.0:  # (also NaN)
+            return U, i
+        U[i, 0] = np.sqrt(row[0])
+        U[i, 1:m + 1] = row[1:] / U[i, 0]
+    return U, None
+
+
+def banded_solve_host(U_band, b, mode="full"):
+    """The host twin of Context.banded_solve, in float64, by substitution:
+    mode "forward" solves U^T y = b, "backward" U x = b, "full" A x = b (forward,
+    then backward) for the factor U_band ([n, K + 1]) of banded_cholesky_host or
+    Context.banded_cholesky and b ([n] or [n, n_cols]).  Returns a new float64
+    array of b's shape.  numpy."""
+    if mode not in SOLVE_MODES:
+        raise ValueError('mode must be "full", "forward" or "backward"')
+    U = np.asarray(U_band, dtype=np.float64)
+    b = np.asarray(b)
+    if U.ndim != 2 or U.shape[0] < 1 or U.shape[1] < 1:
+        raise ValueError("U_band must be a [n, K + 1] band")
+    n = U.shape[0]
+    if b.ndim not in (1, 2) or b.shape[0] != n:
+        raise ValueError("b must be [n] or [n, n_cols] with n = %d" % n)
+    Kc = min(U.shape[1] - 1, n - 1)
+    x = b.astype(np.float64).reshape(n, -1).copy()
+    if mode != "backward":
+        for i in range(n):
+            m = min(Kc, n - 1 - i)
+            x[i] = x[i] / U[i, 0]
+            x[i + 1:i + m + 1] -= U[i, 1:m + 1, None] * x[i]
+    if mode != "forward":
+        for i in range(n - 1, -1, -1):
+            m = min(Kc, n - 1 - i)
+            x[i] = (x[i] - U[i, 1:m + 1] @ x[i + 1:i + m + 1]) / U[i, 0]
+    return x.reshape(b.shape)
+
+
+def banded_logdet(U_band):
+    """log det A = 2 sum_i log U[i, 0] for the factor U_band ([n, K + 1], a numpy
+    array or a torch tensor) of A = U^T U.  A float."""
+    if hasattr(U_band, "data_ptr"):
+        return 2.0 * float(U_band[:, 0].double().log().sum())
+    U = np.asarray(U_band, dtype=np.float64)
+    if U.ndim != 2 or U.shape[1] < 1:
+        raise ValueError("U_band must be a [n, K + 1] band")
+    return 2.0 * float(np.log(U[:, 0]).sum())
+
+
+def _dev_tensor(t, what, names, device=None):
+    """t checked as a device tensor of one of the dtype names; its dtype name."""
+    if not all(hasattr(t, a) for a in ("data_ptr", "stride", "dtype", "shape", "device")):
+        raise ValueError("%s must be a device tensor" % what)
+    if getattr(t.device, "type", "") != "cuda":
+        raise ValueError("%s must be on the context's GPU, not on %s" % (what, t.device))
+    if device is not None and t.device.index is not None and t.device.index != device:
+        raise ValueError("%s is on device %d; the context runs on %d" % (what, t.device.index, device))
+    name = str(t.dtype).replace("torch.", "")
+    if name not in names:
+        raise ValueError("%s has dtype %s; it must be one of %s" % (what, name, ", ".join(names)))
+    return name
+
+
+def _row_stride(t, width, what):
+    """The row stride in elements of a [n] or [n, width] tensor with contiguous rows."""
+    shape, strides = tuple(int(x) for x in t.shape), tuple(int(x) for x in t.stride())
+    if len(shape) == 2 and shape[1] > 1 and strides[1] != 1:
+        raise ValueError("%s must have contiguous rows (last stride 1)" % what)
+    ld = strides[0] if shape[0] > 1 else max(width, 1)
+    if ld < width:
+        raise ValueError("%s's row stride %d is below its width %d" % (what, ld, width))
+    return ld
+
+
+def banded_chol_args(band, ridge=0.0, diag=None, out=None, bandwidth=None, device=None):
+    """Context.banded_cholesky's arguments checked before any device call:
+    returns (n, K, dtype id, ld, ldf) with ldf None without out.  ValueError on
+    anything the call would refuse: band not a float32 or float16 [n, >= K + 1]
+    device tensor with contiguous rows, a bandwidth outside the band's columns,
+    a non-finite ridge, diag not a contiguous float64 [n] device tensor, out not
+    a float64 [n, K + 1] device tensor with contiguous rows."""
+    name = _dev_tensor(band, "band", ("float32", "float16"), device)
+    shape = tuple(int(x) for x in band.shape)
+    if len(shape) != 2 or shape[0] < 1 or shape[1] < 1:
+        raise ValueError("band must be a [n, bandwidth + 1] tensor")
+    n = shape[0]
+    try:
+        K = shape[1] - 1 if bandwidth is None else int(bandwidth)
+    except (TypeError, ValueError):
+        raise ValueError("bandwidth must be None or an integer")
+    if K < 0 or K > shape[1] - 1:
+        raise ValueError("bandwidth %d does not fit the band's %d columns" % (K, shape[1]))
+    try:
+        ridge = float(ridge)
+    except (TypeError, ValueError):
+        raise ValueError("ridge must be a number")
+    if not np.isfinite(ridge):
+        raise ValueError("ridge must be finite")
+    ld = _row_stride(band, shape[1], "band")
+    if diag is not None:
+        _dev_tensor(diag, "diag", ("float64",), device)
+        if tuple(int(x) for x in diag.shape) != (n,):
+            raise ValueError("diag must be [n] with n = %d, not %s" % (n, tuple(diag.shape)))
+        if n > 1 and int(diag.stride()[0]) != 1:
+            raise ValueError("diag must be contiguous")
+    ldf = None
+    if out is not None:
+        _dev_tensor(out, "out", ("float64",), device)
+        if tuple(int(x) for x in out.shape) != (n, K + 1):
+            raise ValueError("out has shape %s; the call writes %s" % (tuple(out.shape), (n, K + 1)))
+        ldf = _row_stride(out, K + 1, "out")
+    return n, K, _MATRIX_DTYPES[name], ld, ldf
+
+
+def banded_solve_args(factor, b, mode="full", out=None, device=None):
+    """Context.banded_solve's arguments checked before any device call: returns
+    (n, K, ldf, mode id, n_cols).  ValueError on anything the call would refuse:
+    an unknown mode, factor not a float64 [n, K + 1] device tensor with
+    contiguous rows, b not a float32 or float64 [n] or [n, n_cols] device
+    tensor, out not a float64 device tensor of b's shape with contiguous rows."""
+    if mode not in SOLVE_MODES:
+        raise ValueError('mode must be "full", "forward" or "backward"')
+    _dev_tensor(factor, "factor", ("float64",), device)
+    shape = tuple(int(x) for x in factor.shape)
+    if len(shape) != 2 or shape[0] < 1 or shape[1] < 1:
+        raise ValueError("factor must be a [n, bandwidth + 1] tensor")
+    n, K = shape[0], shape[1] - 1
+    ldf = _row_stride(factor, K + 1, "factor")
+    _dev_tensor(b, "b", ("float32", "float64"), device)
+    bshape = tuple(int(x) for x in b.shape)
+    if len(bshape) not in (1, 2) or bshape[0] != n or (len(bshape) == 2 and bshape[1] < 1):
+        raise ValueError("b must be [n] or [n, n_cols] with n = %d, not %s" % (n, bshape))
+    n_cols = 1 if len(bshape) == 1 else bshape[1]
+    if out is not None:
+        _dev_tensor(out, "out", ("float64",), device)
+        if tuple(int(x) for x in out.shape) != bshape:
+            raise ValueError("out has shape %s; b has %s" % (tuple(out.shape), bshape))
+        _row_stride(out, n_cols, "out")
+    return n, K, ldf, SOLVE_MODES[mode], n_cols
 
 
 def annot_matrix(annot, n_sites=None):
@@ -1356,6 +1540,71 @@ class Context:
             self._h, ctypes.c_void_p(int(band.data_ptr())), MATRIX_F16 if band.dtype == torch.float16 else MATRIX_F32, ld,
             n, K, ctypes.c_void_p(int(X.data_ptr())), APPLY_X_F64 if X.dtype == torch.float64 else APPLY_X_F32, ldx,
             n_cols, ctypes.c_void_p(int(out.data_ptr())), ldy), "wld_banded_apply_device")
+        return out
+
+    def banded_cholesky(self, band, ridge=0.0, diag=None, out=None, bandwidth=None):
+        """wld_banded_cholesky_device: the Cholesky factor U (A = U^T U, upper
+        triangular, U[i, i] > 0) of the symmetric matrix A whose upper band is
+        `band` — a [n, W] float32 or float16 device tensor as banded_apply
+        takes it (bandwidth None: W - 1) — with the diagonal fl(fl(band[i, 0] +
+        ridge) + diag[i]) (diag: a float64 [n] device tensor or None).  Returns
+        (factor, LdBandedCholInfo): factor a float64 [n, K + 1] device tensor in
+        the same layout (factor[i, k] = U[i, i + k], +0.0 where i + k >= n; out:
+        such a tensor, rows may be strided, overwritten).  About n K^2 flops on
+        f64 MFMAs; every element has one owner and a fixed order, so two calls
+        give identical bytes.
+
+        A band that is not positive definite is a result, not an error:
+        info.ok is False, info.first_bad the first row whose pivot was not > 0,
+        and only the factor's rows below 64 * (first_bad // 64) are valid; no
+        pivot is ever replaced.  banded_logdet(factor) gives log det A.
+
+        Sampling: for e ~ N(0, I), banded_solve(factor, e, "backward") has
+        covariance A^-1 (a draw from N(0, A^-1)); U^T e, i.e. the inverse of
+        the "forward" solve, has covariance A.  Whitening: for z ~ N(0, A),
+        banded_solve(factor, z, "forward") is N(0, I).  The tensors' pending
+        work is synchronised first; needs no load."""
+        import torch
+
+        n, K, dt, ld, ldf = banded_chol_args(band, ridge, diag, out, bandwidth, self.device)
+        if out is None:
+            out = torch.empty((n, K + 1), dtype=torch.float64, device=band.device)
+            ldf = K + 1
+        info = BandedCholInfoC()
+        torch.cuda.synchronize(band.device)
+        check(lib().wld_banded_cholesky_device(
+            self._h, ctypes.c_void_p(int(band.data_ptr())), dt, ld, n, K, float(ridge),
+            None if diag is None else ctypes.c_void_p(int(diag.data_ptr())), ctypes.c_void_p(int(out.data_ptr())), ldf,
+            ctypes.byref(info)), "wld_banded_cholesky_device")
+        ok = int(info.first_bad) == n
+        return out, LdBandedCholInfo(ok=ok, first_bad=None if ok else int(info.first_bad),
+                                     min_pivot=float(info.min_pivot), kernel_ms=float(info.kernel_ms))
+
+    def banded_solve(self, factor, b, mode="full", out=None):
+        """wld_banded_solve_device: the solution of A x = b (mode "full"), U^T y
+        = b ("forward") or U x = b ("backward") for the factor of
+        banded_cholesky (a float64 [n, K + 1] device tensor, rows may be
+        strided) and b a [n] or [n, n_cols] float32 or float64 device tensor,
+        which is converted to float64 and never modified.  Returns a new
+        float64 tensor of b's shape (out: such a tensor, overwritten; it may be
+        b itself).  Substitution throughout, one owner and a fixed order per
+        element: two calls give identical bytes.  Neither argument is
+        validated: non-finite values propagate.
+
+        For e ~ N(0, I), "backward" gives a draw with covariance A^-1;
+        "forward" whitens a draw from N(0, A)."""
+        import torch
+
+        n, K, ldf, md, n_cols = banded_solve_args(factor, b, mode, out, self.device)
+        if out is None:
+            out = torch.empty(tuple(b.shape), dtype=torch.float64, device=b.device)
+        if out.data_ptr() != b.data_ptr() or b.dtype != torch.float64:
+            out.copy_(b)
+        ldb = _row_stride(out, n_cols, "out")
+        torch.cuda.synchronize(out.device)
+        check(lib().wld_banded_solve_device(self._h, ctypes.c_void_p(int(factor.data_ptr())), ldf, n, K, md,
+                                            ctypes.c_void_p(int(out.data_ptr())), ldb, n_cols, None),
+              "wld_banded_solve_device")
         return out
 
     def run_partners(self, k, r2_threshold, chunk_begin=0, chunk_end=0):

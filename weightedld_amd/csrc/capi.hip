@@ -257,6 +257,11 @@ struct wld_ctx {
     DevBuf mx_lists, mx_cnt;
     hipEvent_t ev_mx[2] = {};
 
+    // wld_banded_cholesky_device / wld_banded_solve_device: the factorisation's
+    // status word and the two events around a call's launches
+    DevBuf chol_status;
+    hipEvent_t ev_chol[2] = {};
+
     // wld_run_partners: its own tile list, a batch's staging (entries and
     // counts), the batch's CSR, the running lists and the words {classes[3],
     // guard}; its events are created per call
@@ -298,7 +303,7 @@ struct wld_ctx {
         // buffers: it completes before they are freed
         if (stream && stream != own_stream) (void)hipStreamSynchronize(stream);
         DevBuf *all[] = {&keep, &htab, &htab_kept, &site_index, &raw, &wraw, &codes, &w_pad, &wstats, &site_ok, &site_map, &planes, &frag, &rcodes, &rw, &w6, &w4, &f6a, &f6b, &f6marg, &f6rec, &i8a, &i8b, &tiles, &cand, &f6_pairs, &fp6_probe_buf,
-                         &seg_cnt, &seg_off, &chunk_total, &chunk_base, &counters, &chunk_left, &prog_n, &win_hi, &win_pairs, &sum_buf, &heat_buf, &heat_tiles, &heat_map, &an_buf, &an_tiles, &an_img, &mx_lists, &mx_cnt, &pt_tiles, &pt_stage, &pt_cnt, &pt_csr, &pt_run, &pt_words, &blk_brk, &blk_acc, &blk_map, &blk_tiles, &st_a, &st_b, &st_d,
+                         &seg_cnt, &seg_off, &chunk_total, &chunk_base, &counters, &chunk_left, &prog_n, &win_hi, &win_pairs, &sum_buf, &heat_buf, &heat_tiles, &heat_map, &an_buf, &an_tiles, &an_img, &mx_lists, &mx_cnt, &chol_status, &pt_tiles, &pt_stage, &pt_cnt, &pt_csr, &pt_run, &pt_words, &blk_brk, &blk_acc, &blk_map, &blk_tiles, &st_a, &st_b, &st_d,
                          &st_dp, &st_r2, &out_a, &out_b, &out_d, &out_dp, &out_r2};
         for (DevBuf *b : all) release(*b);
         for (DevBuf *b : tg.all()) release(*b);
@@ -313,6 +318,8 @@ struct wld_ctx {
         for (auto &e : ev_an)
             if (e) (void)hipEventDestroy(e);
         for (auto &e : ev_mx)
+            if (e) (void)hipEventDestroy(e);
+        for (auto &e : ev_chol)
             if (e) (void)hipEventDestroy(e);
         for (auto &e : ev_blk)
             if (e) (void)hipEventDestroy(e);
@@ -3090,6 +3097,75 @@ int wld_banded_apply_device(wld_ctx *c, const void *d_band, int band_dtype, size
     launch_banded_apply(a, c->stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(c->stream));
+    return WLD_OK;
+}
+
+int wld_banded_cholesky_device(wld_ctx *c, const void *d_band, int band_dtype, size_t ld, uint32_t n_sites,
+                               uint32_t bandwidth, double ridge, const double *d_diag, double *d_factor, size_t ldf,
+                               wld_banded_chol_info *out) {
+    const char *who = "wld_banded_cholesky_device";
+    if (!c) return fail(WLD_E_ARG, "null context");
+    WLD_TRY(set_dev(c));
+    if (c->pend.active) return fail(WLD_E_STATE, "%s during a run", who);
+    if (!d_band || !d_factor || !out)
+        return fail(WLD_E_ARG, "%s: null %s", who, !d_band ? "band" : !d_factor ? "factor" : "info");
+    if (band_dtype != WLD_MATRIX_F32 && band_dtype != WLD_MATRIX_F16)
+        return fail(WLD_E_ARG, "%s: unknown band dtype %d", who, band_dtype);
+    if (!n_sites) return fail(WLD_E_ARG, "%s: no site", who);
+    if ((uint64_t)ld < (uint64_t)bandwidth + 1 || (uint64_t)ldf < (uint64_t)bandwidth + 1)
+        return fail(WLD_E_ARG, "%s: ld %zu or ldf %zu is below bandwidth + 1 = %llu", who, ld, ldf,
+                    (unsigned long long)bandwidth + 1);
+    if (!std::isfinite(ridge)) return fail(WLD_E_ARG, "%s: the ridge is not finite", who);
+    {  // the extents [first element, one past the last element read or written)
+        const size_t esz = band_dtype == WLD_MATRIX_F16 ? 2 : 4;
+        const uintptr_t b0 = (uintptr_t)d_band, b1 = b0 + ((size_t)(n_sites - 1) * ld + bandwidth + 1) * esz;
+        const uintptr_t f0 = (uintptr_t)d_factor, f1 = f0 + ((size_t)(n_sites - 1) * ldf + bandwidth + 1) * sizeof(double);
+        if (b0 < f1 && f0 < b1) return fail(WLD_E_ARG, "%s: the factor overlaps the band", who);
+    }
+    for (auto &e : c->ev_chol)
+        if (!e) HIP_TRY(hipEventCreate(&e));
+    WLD_TRY(ensure(c->chol_status, sizeof(BandedCholStatus)));
+    const BandedCholArgs a{d_band,   ld,  band_dtype == WLD_MATRIX_F16,         n_sites, bandwidth, ridge, d_diag,
+                           d_factor, ldf, ptr<BandedCholStatus>(c->chol_status)};
+    HIP_TRY(hipEventRecord(c->ev_chol[0], c->stream));
+    launch_banded_chol(a, c->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c->ev_chol[1], c->stream));
+    BandedCholStatus st{};
+    HIP_TRY(hipMemcpyAsync(&st, c->chol_status.p, sizeof(st), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    out->n_sites = n_sites;
+    out->bandwidth = bandwidth;
+    out->first_bad = st.first_bad;
+    out->min_pivot = st.min_pivot;
+    out->kernel_ms = event_ms(c->ev_chol[0], c->ev_chol[1]);
+    return WLD_OK;
+}
+
+int wld_banded_solve_device(wld_ctx *c, const double *d_factor, size_t ldf, uint32_t n_sites, uint32_t bandwidth,
+                            int mode, double *d_b, size_t ldb, uint32_t n_cols, double *kernel_ms) {
+    const char *who = "wld_banded_solve_device";
+    if (!c) return fail(WLD_E_ARG, "null context");
+    WLD_TRY(set_dev(c));
+    if (c->pend.active) return fail(WLD_E_STATE, "%s during a run", who);
+    if (!d_factor || !d_b) return fail(WLD_E_ARG, "%s: null %s", who, !d_factor ? "factor" : "b");
+    if (mode != WLD_SOLVE_FULL && mode != WLD_SOLVE_FORWARD && mode != WLD_SOLVE_BACKWARD)
+        return fail(WLD_E_ARG, "%s: unknown mode %d", who, mode);
+    if (!n_sites) return fail(WLD_E_ARG, "%s: no site", who);
+    if (!n_cols) return fail(WLD_E_ARG, "%s: no column", who);
+    if ((uint64_t)ldf < (uint64_t)bandwidth + 1)
+        return fail(WLD_E_ARG, "%s: ldf %zu is below bandwidth + 1 = %llu", who, ldf, (unsigned long long)bandwidth + 1);
+    if (ldb < n_cols) return fail(WLD_E_ARG, "%s: ldb %zu is below the %u columns", who, ldb, n_cols);
+    for (auto &e : c->ev_chol)
+        if (!e) HIP_TRY(hipEventCreate(&e));
+    const BandedSolveArgs a{d_factor, ldf, n_sites, bandwidth, mode != WLD_SOLVE_BACKWARD, mode != WLD_SOLVE_FORWARD,
+                            d_b,      ldb, n_cols};
+    HIP_TRY(hipEventRecord(c->ev_chol[0], c->stream));
+    launch_banded_solve(a, c->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c->ev_chol[1], c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (kernel_ms) *kernel_ms = event_ms(c->ev_chol[0], c->ev_chol[1]);
     return WLD_OK;
 }
 

@@ -265,6 +265,45 @@ struct BandedApplyArgs {
     size_t ldy;
 };
 
+// The status of a banded Cholesky factorisation (banded_chol.hip), on the
+// device: first_bad = n while every pivot so far was > 0, else the first row
+// whose pivot was not (every later kernel reads it and returns); min_pivot the
+// smallest U[i][0] of the rows factored.  Written by the fill kernel and by the
+// one workgroup of each diagonal-block launch, with plain stores.
+struct BandedCholStatus {
+    uint32_t first_bad, pad;
+    double min_pivot;
+};
+
+// A banded Cholesky factorisation (wld_banded_cholesky_device): A = the
+// symmetric matrix of `band` (float or binary16, ld apart) with fl(fl(B[i][0] +
+// ridge) + diag[i]) on the diagonal (diag may be null), factored in place in f
+// ([n][ldf] f64, the same band layout, U of A = U^T U).
+struct BandedCholArgs {
+    const void *band;
+    size_t ld;
+    bool band_f16;
+    uint32_t n, K;
+    double ridge;
+    const double *diag;
+    double *f;
+    size_t ldf;
+    BandedCholStatus *status;
+};
+
+// The triangular solves with such a factor (wld_banded_solve_device): b
+// ([n][ldb] f64, n_cols columns) is overwritten by the solution; fwd: U^T y =
+// b, bwd: U x = y, both: A x = b.
+struct BandedSolveArgs {
+    const double *f;
+    size_t ldf;
+    uint32_t n, K;
+    bool fwd, bwd;
+    double *b;
+    size_t ldb;
+    uint32_t n_cols;
+};
+
 // The staging of one batch of a best-partner run (pair_partners.hip;
 // wld_run_partners; layout in partners_plan.hpp).  Tile position p of the
 // launch's list (p < n_tiles, the workgroup id) owns the parts (2 p + side) *
@@ -409,6 +448,15 @@ void launch_matrix_banded_fill(const matrix_banded_plan::FillBlock *blocks, uint
 // Y := S X on st: one workgroup per 64 output rows and 16 or 64 columns, each Y
 // element summed by its owner in a fixed order (f64 MFMA accumulation).
 void launch_banded_apply(const BandedApplyArgs &a, hipStream_t st);
+
+// banded_chol.hip
+// launch_banded_chol: the fill (f := f64(band) + shifts, +0.0 tails, the status
+// reset), then per block row of 64 rows a diagonal-block launch, a panel
+// launch and a window launch (the trailing update on f64 MFMAs); ordered by
+// the stream alone.  launch_banded_solve: one workgroup per 16 or 64 columns
+// marches over the block rows, forward and/or backward.
+void launch_banded_chol(const BandedCholArgs &a, hipStream_t st);
+void launch_banded_solve(const BandedSolveArgs &a, hipStream_t st);
 
 // pair_blocks.hip
 // The same sums over v's list: pass 1 (every tile of the range and window)
