@@ -14,13 +14,13 @@ PKG := weightedld_amd
 CSRC := $(PKG)/csrc
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -fno-slp-vectorize -Wall -Iinclude -I$(CSRC)
 HIP_SRCS := $(CSRC)/encode.hip $(CSRC)/prepass.hip $(CSRC)/pair_valu.hip $(CSRC)/pair_summary.hip \
-            $(CSRC)/pair_heatmap.hip $(CSRC)/pair_annot.hip $(CSRC)/pair_matrix.hip $(CSRC)/pair_matrix_banded.hip $(CSRC)/banded_apply.hip $(CSRC)/banded_chol.hip $(CSRC)/pair_partners.hip $(CSRC)/pair_blocks.hip $(CSRC)/pair_mfma.hip $(CSRC)/prune.hip $(CSRC)/order.hip $(CSRC)/pair_targets.hip $(CSRC)/capi.hip
+            $(CSRC)/pair_heatmap.hip $(CSRC)/pair_annot.hip $(CSRC)/pair_matrix.hip $(CSRC)/pair_matrix_banded.hip $(CSRC)/banded_apply.hip $(CSRC)/banded_chol.hip $(CSRC)/banded_omega.hip $(CSRC)/pair_partners.hip $(CSRC)/pair_blocks.hip $(CSRC)/pair_mfma.hip $(CSRC)/prune.hip $(CSRC)/order.hip $(CSRC)/pair_targets.hip $(CSRC)/capi.hip
 CXX_SRCS := $(CSRC)/host.cpp
 HDRS := include/weightedld.h $(CSRC)/common.hpp $(CSRC)/kernels.hpp $(CSRC)/pair_common.hpp $(CSRC)/tile_order.hpp \
         $(CSRC)/window_plan.hpp $(CSRC)/pair_valu_kernel.hpp $(CSRC)/summary_plan.hpp $(CSRC)/prune_plan.hpp \
         $(CSRC)/screen_policy.hpp $(CSRC)/fp6_scale.hpp $(CSRC)/fp6_pack.hpp $(CSRC)/targets_plan.hpp \
         $(CSRC)/heatmap_plan.hpp $(CSRC)/partners_plan.hpp $(CSRC)/blocks_plan.hpp $(CSRC)/annot_plan.hpp \
-        $(CSRC)/matrix_plan.hpp $(CSRC)/matrix_banded_plan.hpp $(CSRC)/banded_chol_plan.hpp
+        $(CSRC)/matrix_plan.hpp $(CSRC)/matrix_banded_plan.hpp $(CSRC)/banded_chol_plan.hpp $(CSRC)/banded_omega_plan.hpp
 OBJDIR := build/obj
 OBJS := $(patsubst $(CSRC)/%.hip,$(OBJDIR)/%.o,$(HIP_SRCS)) $(patsubst $(CSRC)/%.cpp,$(OBJDIR)/%.o,$(CXX_SRCS))
 

@@ -1045,6 +1045,106 @@ int wld_banded_solve_device(wld_ctx *ctx, const double *d_factor, size_t ldf, ui
                             int mode, double *d_b /* [n_sites][ldb], overwritten by the solution */, size_t ldb,
                             uint32_t n_cols, double *kernel_ms /* may be NULL */);
 
+/* ---- Sweep scan: Kim and Nielsen's omega and Kelly's ZnS from an r2 band (not
+ * in the reference; OmegaPlus) ----
+ * Every value below is one fixed sequence of IEEE f64 operations; the numpy
+ * twins of the Python package (banded_pairsum_host, banded_omega_host) perform
+ * the same sequence, and the device results equal them bit for bit.
+ *
+ * Pair sums.  wld_banded_pairsum_device reads a band as wld_banded_apply_device
+ * does (WLD_MATRIX_F32 or _F16, ld >= K + 1; elements with j + k >= n_sites and
+ * column 0 are never read) and writes the table M in the same layout in f64
+ * (d_sums[j * lds_ + k] = M[j][k], lds_ >= K + 1).  With b(j, k) = f64(B[j][k])
+ * where that is finite, else +0.0:
+ *   P[j][0] = 0,  P[j][k] = P[j][k-1] + b(j, k)   k = 1..K in that order,
+ *   M[j][0] = 0,  M[j][k] = M[j+1][k-1] + P[j][k],
+ * so M[j][k] is the sum of the entries (u, v), j <= u < v <= j + k.  Elements
+ * with j + k >= n_sites are +0.0.  Every element of [n_sites] x [K + 1] is
+ * written, nothing else, the padding between rows included; d_sums must not
+ * overlap the band.  Each element has one owner and one order: two calls give
+ * identical bytes.  Like wld_banded_apply_device the context supplies only the
+ * device and the stream; no load is needed.
+ *
+ * Scan.  wld_banded_omega_device takes such a table and n_splits splits; entry
+ * g is the split between the sites c = d_split[g] and c + 1, its left flank the
+ * sites a..c with d_lo[g] <= a, its right flank c+1..b with b <= d_hi[g], both
+ * flanks at least min_side >= 2 sites.  For a candidate (a, b), l = c - a + 1,
+ * r = b - c:
+ *   SL = M[a][c-a]   SR = M[c+1][b-c-1]   ST = M[a][b-a]   X = (ST - SL) - SR
+ *   t1 = (SL + SR) / f64(l(l-1)/2 + r(r-1)/2)     t2 = X / f64(l r) + eps
+ *   omega = t1 / t2, the candidate skipped (and counted) unless t2 > 0.
+ * d_omega[g] is the largest omega of the split's candidates, d_left[g] and
+ * d_right[g] its (a, b); among equal omega the smallest a wins, then the
+ * smallest b.  A split without an unskipped candidate gives NaN, UINT32_MAX,
+ * UINT32_MAX.  d_zns[g] = M[lo][hi-lo] / f64(w(w-1)/2), w = hi - lo + 1.  Splits
+ * may repeat and come in any order.  The device arrays are validated by a small
+ * launch before the scan: every split needs lo <= c < hi < n_sites and hi - lo
+ * <= bandwidth, else WLD_E_ARG naming the first offender, and nothing is
+ * written.  The table's values are not validated.  The outputs must not overlap
+ * the table or the split arrays (not checked).
+ *
+ * WLD_E_ARG: a null pointer, n_sites or n_splits 0, ld or lds_ < K + 1, an
+ * unknown dtype, d_sums overlapping d_band, min_side < 2, eps negative or not
+ * finite, a bad split.  WLD_E_STATE: while a run is in flight, on a device
+ * group.  wld_last_stats, the last run's rows and every cached list stay as
+ * they were. */
+typedef struct {
+    uint32_t n_sites, bandwidth;
+    uint64_t nonfinite; /* band elements (k >= 1, i + k < n_sites) that were NaN or +-inf and counted as 0 */
+    double kernel_ms;
+} wld_banded_pairsum_info;
+int wld_banded_pairsum_device(wld_ctx *ctx, const void *d_band, int band_dtype, size_t ld, uint32_t n_sites,
+                              uint32_t bandwidth, double *d_sums, size_t lds_, wld_banded_pairsum_info *out);
+
+typedef struct {
+    uint32_t n_splits;
+    uint64_t evaluated, skipped; /* candidate border pairs with t2 > 0 / without */
+    double kernel_ms;
+} wld_banded_omega_info;
+int wld_banded_omega_device(wld_ctx *ctx, const double *d_sums, size_t lds_, uint32_t n_sites, uint32_t bandwidth,
+                            const uint32_t *d_split, const uint32_t *d_lo, const uint32_t *d_hi, uint32_t n_splits,
+                            uint32_t min_side, double eps, double *d_omega, uint32_t *d_left, uint32_t *d_right,
+                            double *d_zns, wld_banded_omega_info *out);
+
+/* The splits of a scan from coordinates; host only, no device.  site_map: the
+ * n_sites >= 2 coordinates, non-decreasing as wld_set_window requires (NULL:
+ * site_map[i] = i).  n_grid 0: every split c = 0..n_sites-2 at position
+ * site_map[c]; n_grid >= 1: the equidistant positions x_g = site_map[0] +
+ * floor(span g / (n_grid - 1)) (n_grid 1: the midpoint), c the last site with
+ * coordinate <= x_g, clamped to [0, n_sites - 2].  lo = max(c - max_side + 1,
+ * first site with coordinate >= x_g - max_distance), at most c; hi = min(c +
+ * max_side, last site with coordinate <= x_g + max_distance, n_sites - 1), at
+ * least c + 1; max_distance 0: no distance limit.  Writes wld_omega_n_splits
+ * entries of each output.  WLD_E_ARG: a null output, n_sites < 2, max_side 0, a
+ * descending site_map. */
+uint64_t wld_omega_n_splits(uint32_t n_sites, uint32_t n_grid);
+int wld_omega_splits(const uint64_t *site_map, uint32_t n_sites, uint32_t n_grid, uint32_t max_side,
+                     uint64_t max_distance, uint64_t *position, uint32_t *split, uint32_t *lo, uint32_t *hi);
+
+/* The whole scan on a loaded single-device context: the splits from the load's
+ * site_map (wld_omega_splits), an r2 band with WLD_MATRIX_ZERO_MISSING of width
+ * wld_matrix_banded_width under the context's CURRENT window in a buffer the
+ * call owns, its pair sums, the scan, and the results on the host (malloc'ed;
+ * wld_omega_free).  A split whose sites lo..hi are not all in each other's
+ * window is refused with WLD_E_ARG (the window would drop pairs the scan
+ * needs): a window of max_sites >= 2 max_side - 1 (and no max_distance) always
+ * suffices, and the message names that number.  WLD_E_OOM leaves the context
+ * usable.  wld_last_stats and the last run's rows stay as they were. */
+typedef struct {
+    uint32_t n_sites, bandwidth, n_splits, min_side;
+    uint64_t *position;            /* [n_splits] the splits' coordinates */
+    uint32_t *split, *lo, *hi;     /* [n_splits] loaded site indices */
+    double *omega;                 /* [n_splits] NaN: no candidate */
+    uint32_t *left, *right;        /* [n_splits] the best borders, UINT32_MAX: none */
+    double *zns;                   /* [n_splits] */
+    wld_matrix_banded_info band;   /* the band fill: its pair counts and time */
+    wld_banded_pairsum_info sums;
+    wld_banded_omega_info scan;
+} wld_omega;
+int wld_run_omega(wld_ctx *ctx, uint32_t n_grid, uint32_t max_side, uint32_t min_side, uint64_t max_distance, double eps,
+                  int band_dtype, wld_omega *out);
+void wld_omega_free(wld_omega *o);
+
 /* ---- LD pruning: a greedy r2-independent site set with tags (not in the
  * reference; PLINK's --indep-pairwise, bcftools +prune) ----
  *

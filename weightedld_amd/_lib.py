@@ -188,6 +188,44 @@ class MatrixBandedInfoC(ctypes.Structure):
     ]
 
 
+class BandedPairsumInfoC(ctypes.Structure):
+    _fields_ = [
+        ("n_sites", ctypes.c_uint32),
+        ("bandwidth", ctypes.c_uint32),
+        ("nonfinite", ctypes.c_uint64),
+        ("kernel_ms", ctypes.c_double),
+    ]
+
+
+class BandedOmegaInfoC(ctypes.Structure):
+    _fields_ = [
+        ("n_splits", ctypes.c_uint32),
+        ("evaluated", ctypes.c_uint64),
+        ("skipped", ctypes.c_uint64),
+        ("kernel_ms", ctypes.c_double),
+    ]
+
+
+class OmegaC(ctypes.Structure):
+    _fields_ = [
+        ("n_sites", ctypes.c_uint32),
+        ("bandwidth", ctypes.c_uint32),
+        ("n_splits", ctypes.c_uint32),
+        ("min_side", ctypes.c_uint32),
+        ("position", ctypes.POINTER(ctypes.c_uint64)),
+        ("split", ctypes.POINTER(ctypes.c_uint32)),
+        ("lo", ctypes.POINTER(ctypes.c_uint32)),
+        ("hi", ctypes.POINTER(ctypes.c_uint32)),
+        ("omega", ctypes.POINTER(ctypes.c_double)),
+        ("left", ctypes.POINTER(ctypes.c_uint32)),
+        ("right", ctypes.POINTER(ctypes.c_uint32)),
+        ("zns", ctypes.POINTER(ctypes.c_double)),
+        ("band", MatrixBandedInfoC),
+        ("sums", BandedPairsumInfoC),
+        ("scan", BandedOmegaInfoC),
+    ]
+
+
 BLOCKS_R2, BLOCKS_ABS_DPRIME, BLOCKS_ALL, BLOCKS_SPINE, BLOCKS_NONE = 0, 1, 0, 1, 0xFFFFFFFF
 
 
@@ -386,6 +424,17 @@ SIGNATURES = {
                                           _sz, ctypes.POINTER(BandedCholInfoC)]),
     "wld_banded_solve_device": (_int, [_vp, _vp, _sz, ctypes.c_uint32, ctypes.c_uint32, _int, _vp, _sz, ctypes.c_uint32,
                                        ctypes.POINTER(ctypes.c_double)]),
+    "wld_banded_pairsum_device": (_int, [_vp, _vp, _int, _sz, ctypes.c_uint32, ctypes.c_uint32, _vp, _sz,
+                                         ctypes.POINTER(BandedPairsumInfoC)]),
+    "wld_banded_omega_device": (_int, [_vp, _vp, _sz, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp, _vp, ctypes.c_uint32,
+                                       ctypes.c_uint32, ctypes.c_double, _vp, _vp, _vp, _vp,
+                                       ctypes.POINTER(BandedOmegaInfoC)]),
+    "wld_omega_n_splits": (ctypes.c_uint64, [ctypes.c_uint32, ctypes.c_uint32]),
+    "wld_omega_splits": (_int, [_vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64, _vp, _vp, _vp,
+                                _vp]),
+    "wld_run_omega": (_int, [_vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_double, _int,
+                             ctypes.POINTER(OmegaC)]),
+    "wld_omega_free": (None, [ctypes.POINTER(OmegaC)]),
     "wld_run_prune": (_int, [_vp, ctypes.c_float, _f32p, ctypes.POINTER(Prune)]),
     "wld_prune_free": (None, [ctypes.POINTER(Prune)]),
     "wld_loaded_sites": (_sz, [_vp]),

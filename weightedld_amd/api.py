@@ -15,14 +15,14 @@ import numpy as np
 
 from ._lib import (ANNOT_MAX, ANNOT_SELF, AnnotScoresC, BLOCKS_ABS_DPRIME, BLOCKS_ALL, BLOCKS_NONE, BLOCKS_R2, BLOCKS_SPINE, BlockBreaksC, BlocksC,
                    HEAT_ABS_DPRIME, HEAT_MAX_CELLS, HEAT_R2, KERNEL_AUTO, KERNEL_MFMA, KERNEL_VALU, MATRIX_F16, MATRIX_F32,
-                   MATRIX_STATS, MATRIX_ZERO_MISSING, APPLY_X_F32, APPLY_X_F64, SOLVE_MODES, BandedCholInfoC, MatrixBandedInfoC, MatrixInfoC, OPTIONS,
+                   MATRIX_STATS, MATRIX_ZERO_MISSING, APPLY_X_F32, APPLY_X_F64, SOLVE_MODES, BandedCholInfoC, BandedOmegaInfoC, BandedPairsumInfoC, OmegaC, MatrixBandedInfoC, MatrixInfoC, OPTIONS,
                    PARTNERS_MAX_K, PARTNERS_NONE, PROGRESS_FN, Heatmap, Pairs, PartnersC, Prune, RunStats, Summary,
                    TargetRowsC, WldError, check, lib)
 
 __all__ = [
     "Symbol", "SymbolHistogram", "SiteSet", "LdStats", "PairStore", "read_fasta", "read_vcf",
     "is_site_of_interest", "henikoff_weights", "single_weighted_ld_pair", "all_weighted_ld_pairs",
-    "ld_summary", "LdSummary", "ld_heatmap", "LdHeatmap", "heatmap_cells", "ld_annot_scores", "LdAnnotScores", "annot_matrix", "ANNOT_MAX", "ld_matrix", "LdMatrixInfo", "matrix_args", "matrix_region", "ld_banded", "LdBandedInfo", "banded_args", "banded_from_dense", "banded_to_dense", "banded_matmul_host", "banded_cg_solve", "banded_cholesky_host", "banded_solve_host", "banded_logdet", "banded_chol_args", "banded_solve_args", "LdBandedCholInfo", "ld_prune", "LdPrune", "maf_priority", "ld_targets", "TargetRows", "ld_partners", "LdPartners", "PARTNERS_MAX_K", "PARTNERS_NONE", "ld_blocks", "LdBlocks", "LdBlockBreaks", "BLOCKS_NONE", "Context", "default_context", "KERNEL_AUTO", "KERNEL_VALU", "KERNEL_MFMA", "OPTIONS", "WldError",
+    "ld_summary", "LdSummary", "ld_heatmap", "LdHeatmap", "heatmap_cells", "ld_annot_scores", "LdAnnotScores", "annot_matrix", "ANNOT_MAX", "ld_matrix", "LdMatrixInfo", "matrix_args", "matrix_region", "ld_banded", "LdBandedInfo", "banded_args", "banded_from_dense", "banded_to_dense", "banded_matmul_host", "banded_cg_solve", "banded_cholesky_host", "banded_solve_host", "banded_logdet", "banded_chol_args", "banded_solve_args", "LdBandedCholInfo", "banded_pairsum_host", "banded_nonfinite_host", "banded_omega_host", "banded_pairsum_args", "omega_args", "omega_splits", "ld_omega", "LdOmega", "LdPairsumInfo", "OMEGA_NONE", "ld_prune", "LdPrune", "maf_priority", "ld_targets", "TargetRows", "ld_partners", "LdPartners", "PARTNERS_MAX_K", "PARTNERS_NONE", "ld_blocks", "LdBlocks", "LdBlockBreaks", "BLOCKS_NONE", "Context", "default_context", "KERNEL_AUTO", "KERNEL_VALU", "KERNEL_MFMA", "OPTIONS", "WldError",
 ]
 
 
@@ -671,13 +671,12 @@ def _row_stride(t, width, what):
     return ld
 
 
-def banded_chol_args(band, ridge=0.0, diag=None, out=None, bandwidth=None, device=None):
-    """Context.banded_cholesky's arguments checked before any device call:
-    returns (n, K, dtype id, ld, ldf) with ldf None without out.  ValueError on
-    anything the call would refuse: band not a float32 or float16 [n, >= K + 1]
-    device tensor with contiguous rows, a bandwidth outside the band's columns,
-    a non-finite ridge, diag not a contiguous float64 [n] device tensor, out not
-    a float64 [n, K + 1] device tensor with contiguous rows."""
+def _band_out_args(band, out, bandwidth, device):
+    """What the calls that read a band and write a float64 array of its shape
+    share: band a float32 or float16 [n, >= K + 1] device tensor with contiguous
+    rows, bandwidth inside its columns, out (or None) a float64 [n, K + 1] device
+    tensor with contiguous rows.  Returns (n, K, dtype id, ld, out's row stride
+    or None); ValueError otherwise."""
     name = _dev_tensor(band, "band", ("float32", "float16"), device)
     shape = tuple(int(x) for x in band.shape)
     if len(shape) != 2 or shape[0] < 1 or shape[1] < 1:
@@ -689,26 +688,37 @@ def banded_chol_args(band, ridge=0.0, diag=None, out=None, bandwidth=None, devic
         raise ValueError("bandwidth must be None or an integer")
     if K < 0 or K > shape[1] - 1:
         raise ValueError("bandwidth %d does not fit the band's %d columns" % (K, shape[1]))
+    ld = _row_stride(band, shape[1], "band")
+    ldo = None
+    if out is not None:
+        _dev_tensor(out, "out", ("float64",), device)
+        if tuple(int(x) for x in out.shape) != (n, K + 1):
+            raise ValueError("out has shape %s; the call writes %s" % (tuple(out.shape), (n, K + 1)))
+        ldo = _row_stride(out, K + 1, "out")
+    return n, K, _MATRIX_DTYPES[name], ld, ldo
+
+
+def banded_chol_args(band, ridge=0.0, diag=None, out=None, bandwidth=None, device=None):
+    """Context.banded_cholesky's arguments checked before any device call:
+    returns (n, K, dtype id, ld, ldf) with ldf None without out.  ValueError on
+    anything the call would refuse: band not a float32 or float16 [n, >= K + 1]
+    device tensor with contiguous rows, a bandwidth outside the band's columns,
+    a non-finite ridge, diag not a contiguous float64 [n] device tensor, out not
+    a float64 [n, K + 1] device tensor with contiguous rows."""
+    n, K, dt, ld, ldf = _band_out_args(band, out, bandwidth, device)
     try:
         ridge = float(ridge)
     except (TypeError, ValueError):
         raise ValueError("ridge must be a number")
     if not np.isfinite(ridge):
         raise ValueError("ridge must be finite")
-    ld = _row_stride(band, shape[1], "band")
     if diag is not None:
         _dev_tensor(diag, "diag", ("float64",), device)
         if tuple(int(x) for x in diag.shape) != (n,):
             raise ValueError("diag must be [n] with n = %d, not %s" % (n, tuple(diag.shape)))
         if n > 1 and int(diag.stride()[0]) != 1:
             raise ValueError("diag must be contiguous")
-    ldf = None
-    if out is not None:
-        _dev_tensor(out, "out", ("float64",), device)
-        if tuple(int(x) for x in out.shape) != (n, K + 1):
-            raise ValueError("out has shape %s; the call writes %s" % (tuple(out.shape), (n, K + 1)))
-        ldf = _row_stride(out, K + 1, "out")
-    return n, K, _MATRIX_DTYPES[name], ld, ldf
+    return n, K, dt, ld, ldf
 
 
 def banded_solve_args(factor, b, mode="full", out=None, device=None):
@@ -736,6 +746,230 @@ def banded_solve_args(factor, b, mode="full", out=None, device=None):
             raise ValueError("out has shape %s; b has %s" % (tuple(out.shape), bshape))
         _row_stride(out, n_cols, "out")
     return n, K, ldf, SOLVE_MODES[mode], n_cols
+
+
+LdPairsumInfo = namedtuple("LdPairsumInfo", ["bandwidth", "nonfinite", "kernel_ms"])
+LdPairsumInfo.__doc__ = """wld_banded_pairsum_info (Context.banded_pairsum): bandwidth; nonfinite, the band elements
+(k >= 1, i + k < n) that were NaN or +-inf and counted as 0; kernel_ms."""
+
+OMEGA_NONE = 0xFFFFFFFF
+
+
+class LdOmega:
+    """A sweep scan (Context.banded_omega, Context.run_omega, ld_omega,
+    banded_omega_host) as numpy arrays, one entry per split: split, lo, hi
+    (uint32 site indices of the scanned table), omega (float64, NaN where no
+    candidate had t2 > 0), left and right (uint32, the best borders a and b,
+    OMEGA_NONE where omega is NaN), zns (float64, Kelly's ZnS of the sites
+    lo..hi), and the ints min_side, evaluated and skipped (candidate border
+    pairs with t2 > 0 / without), eps and kernel_ms (None from the host twin).
+    run_omega and ld_omega add position (uint64, the splits' coordinates),
+    n_sites, bandwidth and the infos band (LdBandedInfo) and sums
+    (LdPairsumInfo)."""
+
+    FIELDS = ("split", "lo", "hi", "omega", "left", "right", "zns")
+
+    def __init__(self, **kw):
+        self.position = None
+        self.__dict__.update(kw)
+
+    @property
+    def n_splits(self):
+        return int(self.split.shape[0])
+
+    def parents(self, site_map=None):
+        """(left, right) in parent coordinates as uint64: site_map[a] and
+        site_map[b] of the best borders (None: the indices themselves), 2^64 -
+        1 where the split has none."""
+        none = self.left == OMEGA_NONE
+        a, b = np.where(none, 0, self.left).astype(np.int64), np.where(none, 0, self.right).astype(np.int64)
+        if site_map is None:
+            pa, pb = a.astype(np.uint64), b.astype(np.uint64)
+        else:
+            sm = np.asarray(site_map, dtype=np.uint64).reshape(-1)
+            if a.size and max(int(a.max()), int(b.max())) >= sm.size:
+                raise ValueError("site_map has %d entries; the borders reach site %d" % (sm.size, int(b.max())))
+            pa, pb = sm[a], sm[b]
+        full = np.uint64(0xFFFFFFFFFFFFFFFF)
+        return np.where(none, full, pa), np.where(none, full, pb)
+
+    def rows(self, site_map=None):
+        """The scan as a list of (position, left parent, right parent, omega,
+        zns) tuples, the CLI's columns; position is the split's own coordinate
+        (site_map[split]) where the scan has none."""
+        pa, pb = self.parents(site_map)
+        if self.position is not None:
+            pos = self.position
+        elif site_map is None:
+            pos = self.split.astype(np.uint64)
+        else:
+            pos = np.asarray(site_map, dtype=np.uint64).reshape(-1)[self.split.astype(np.int64)]
+        return [(int(p), int(x), int(y), float(w), float(z)) for p, x, y, w, z in zip(pos, pa, pb, self.omega, self.zns)]
+
+
+def banded_pairsum_host(B):
+    """The host twin, and the definition, of Context.banded_pairsum: the
+    pair-sum table M ([n, K + 1] float64) of the band B ([n, K + 1], any float
+    dtype).  With b = float64(B) where that is finite, else +0.0, b[:, 0] and
+    the elements with j + k >= n taken as +0.0:
+    P = cumsum(b) along k (P[j, k] = P[j, k - 1] + b[j, k]), then M[j, 0] = 0 and
+    M[j, k] = M[j + 1, k - 1] + P[j, k] for j + k < n, +0.0 elsewhere — so M[j, k]
+    is the sum of the entries (u, v) with j <= u < v <= j + k.  The device gives
+    the same bytes.  numpy."""
+    B = np.asarray(B)
+    if B.ndim != 2 or B.shape[0] < 1 or B.shape[1] < 1:
+        raise ValueError("B must be a [n, K + 1] band")
+    n, width = B.shape
+    b = B.astype(np.float64)
+    j, k = np.arange(n)[:, None], np.arange(width)[None, :]
+    b[~np.isfinite(b) | (k == 0) | (j + k >= n)] = 0.0
+    P = np.cumsum(b, axis=1)
+    M = np.zeros((n, width), dtype=np.float64)
+    for kk in range(1, min(width, n)):
+        M[:n - kk, kk] = M[1:n - kk + 1, kk - 1] + P[:n - kk, kk]
+    return M
+
+
+def banded_nonfinite_host(B):
+    """The count Context.banded_pairsum reports as nonfinite: the elements of
+    the band B with k >= 1 and j + k < n that are NaN or +-inf.  numpy."""
+    B = np.asarray(B)
+    n, width = B.shape
+    j, k = np.arange(n)[:, None], np.arange(width)[None, :]
+    return int(np.count_nonzero(~np.isfinite(B.astype(np.float64)) & (k >= 1) & (j + k < n)))
+
+
+def omega_args(n, K, split, lo, hi, min_side=2, eps=1e-5):
+    """The scan's arguments checked before any device call: returns (split, lo,
+    hi) as uint32 arrays and min_side, eps.  ValueError on anything
+    wld_banded_omega_device would refuse: arrays of different lengths or none,
+    a split without lo <= split < hi < n or with hi - lo > K, min_side < 2, eps
+    negative or not finite."""
+    try:
+        arrs = [np.asarray(x).reshape(-1) for x in (split, lo, hi)]
+    except Exception:
+        raise ValueError("split, lo and hi must be integer arrays")
+    for x in arrs:
+        if x.dtype.kind not in "iu" and x.size:
+            raise ValueError("split, lo and hi must be integer arrays")
+    c, l, h = [x.astype(np.int64) for x in arrs]
+    if not (c.size == l.size == h.size) or c.size < 1:
+        raise ValueError("split, lo and hi must have the same length, at least 1")
+    bad = np.flatnonzero(~((l >= 0) & (l <= c) & (c < h) & (h < n) & (h - l <= K)))
+    if bad.size:
+        g = int(bad[0])
+        raise ValueError("split %d (lo %d, split %d, hi %d) breaks lo <= split < hi < %d sites or hi - lo <= bandwidth %d"
+                         % (g, l[g], c[g], h[g], n, K))
+    try:
+        min_side, eps = int(min_side), float(eps)
+    except (TypeError, ValueError):
+        raise ValueError("min_side must be an integer and eps a number")
+    if min_side < 2 or min_side > 0xFFFFFFFF:
+        raise ValueError("min_side must be at least 2")
+    if not np.isfinite(eps) or eps < 0:
+        raise ValueError("eps must be finite and >= 0")
+    return c.astype(np.uint32), l.astype(np.uint32), h.astype(np.uint32), min_side, eps
+
+
+def banded_omega_host(M, split, lo, hi, min_side=2, eps=1e-5):
+    """The host twin, and the definition, of Context.banded_omega on a pair-sum
+    table M ([n, K + 1] float64, banded_pairsum_host's).  Entry g is the split
+    between the sites c = split[g] and c + 1; the left flank is a..c with lo[g]
+    <= a, the right flank c+1..b with b <= hi[g], both at least min_side sites.
+    Per candidate (a, b), l = c - a + 1, r = b - c:
+        SL = M[a, c-a]   SR = M[c+1, b-c-1]   ST = M[a, b-a]   X = (ST - SL) - SR
+        t1 = (SL + SR) / float(l(l-1)/2 + r(r-1)/2)     t2 = X / float(l r) + eps
+        omega = t1 / t2, skipped (and counted) unless t2 > 0.
+    The split's omega is the largest; among equal ones the smallest a, then the
+    smallest b.  zns = M[lo, hi-lo] / float(w(w-1)/2), w = hi - lo + 1.  Returns an
+    LdOmega.  numpy."""
+    M = np.asarray(M, dtype=np.float64)
+    if M.ndim != 2 or M.shape[0] < 1 or M.shape[1] < 1:
+        raise ValueError("M must be a [n, K + 1] table")
+    n, K = M.shape[0], M.shape[1] - 1
+    cs, ls, hs, min_side, eps = omega_args(n, K, split, lo, hi, min_side, eps)
+    G = cs.size
+    omega = np.full(G, np.nan)
+    left, right = np.full(G, OMEGA_NONE, dtype=np.uint32), np.full(G, OMEGA_NONE, dtype=np.uint32)
+    zns = np.empty(G)
+    evaluated = skipped = 0
+    for g in range(G):
+        c, l0, h0 = int(cs[g]), int(ls[g]), int(hs[g])
+        w = h0 - l0 + 1
+        zns[g] = M[l0, h0 - l0] / np.float64(w * (w - 1) // 2)
+        a = np.arange(l0, c + 1 - min_side + 1, dtype=np.int64)
+        b = np.arange(c + min_side, h0 + 1, dtype=np.int64)
+        if a.size == 0 or b.size == 0:
+            continue
+        l, r = c - a + 1, b - c
+        SL, SR = M[a, c - a][:, None], M[c + 1, b - c - 1][None, :]
+        ST = M[a[:, None], b[None, :] - a[:, None]]
+        X = (ST - SL) - SR
+        den1 = ((l * (l - 1) // 2)[:, None] + (r * (r - 1) // 2)[None, :]).astype(np.float64)
+        den2 = (l[:, None] * r[None, :]).astype(np.float64)
+        t1 = (SL + SR) / den1
+        t2 = X / den2 + np.float64(eps)
+        ok = t2 > 0
+        evaluated += int(np.count_nonzero(ok))
+        skipped += int(ok.size - np.count_nonzero(ok))
+        if not ok.any():
+            continue
+        with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+            om = t1 / np.where(ok, t2, 1.0)
+        best = om[ok].max()
+        flat = int(np.flatnonzero((ok & (om == best)).reshape(-1))[0])  # row-major: smallest a, then smallest b
+        omega[g] = best
+        left[g], right[g] = a[flat // b.size], b[flat % b.size]
+    return LdOmega(split=cs, lo=ls, hi=hs, omega=omega, left=left, right=right, zns=zns, min_side=min_side, eps=eps,
+                   evaluated=evaluated, skipped=skipped, kernel_ms=None)
+
+
+def omega_splits(site_map, n_sites=None, n_grid=0, max_side=None, max_distance=None):
+    """wld_omega_splits (host only): the splits of a sweep scan from
+    coordinates.  site_map: the sites' non-decreasing coordinates (None: the
+    indices 0..n_sites-1).  n_grid 0: every split c = 0..n-2 at position
+    site_map[c]; n_grid >= 1: the equidistant positions x_g = site_map[0] +
+    floor(span g / (n_grid - 1)) (n_grid 1: the midpoint), c the last site with
+    coordinate <= x_g, clamped to [0, n - 2].  lo = max(c - max_side + 1, first
+    site with coordinate >= x_g - max_distance), at most c; hi = min(c +
+    max_side, last site with coordinate <= x_g + max_distance, n - 1), at least
+    c + 1; max_distance None or 0: no distance limit.  Returns (position
+    uint64, split, lo, hi uint32).  ValueError where the library refuses."""
+    if site_map is None:
+        if n_sites is None:
+            raise ValueError("give site_map or n_sites")
+        sm, n = None, int(n_sites)
+    else:
+        sm = np.ascontiguousarray(np.asarray(site_map).reshape(-1), dtype=np.uint64)
+        n = int(sm.size)
+        if n_sites is not None and int(n_sites) != n:
+            raise ValueError("site_map has %d entries for %d sites" % (n, int(n_sites)))
+    if max_side is None:
+        raise ValueError("max_side is required")
+    n_grid, max_side, D = int(n_grid), int(max_side), int(max_distance or 0)
+    if n < 2 or n > 0xFFFFFFFF:
+        raise ValueError("a split needs two sites, not %d" % n)
+    if n_grid < 0 or n_grid > 0xFFFFFFFF or max_side < 1 or max_side > 0xFFFFFFFF or D < 0 or D >= 1 << 64:
+        raise ValueError("n_grid, max_side (at least 1) and max_distance must be non-negative integers")
+    G = int(lib().wld_omega_n_splits(n, n_grid))
+    position = np.empty(G, dtype=np.uint64)
+    split, lo, hi = (np.empty(G, dtype=np.uint32) for _ in range(3))
+    st = lib().wld_omega_splits(None if sm is None else ctypes.c_void_p(sm.ctypes.data), n, n_grid, max_side, D,
+                                ctypes.c_void_p(position.ctypes.data), ctypes.c_void_p(split.ctypes.data),
+                                ctypes.c_void_p(lo.ctypes.data), ctypes.c_void_p(hi.ctypes.data))
+    if st == -1:
+        raise ValueError(lib().wld_last_error().decode())
+    check(st, "wld_omega_splits")
+    return position, split, lo, hi
+
+
+def banded_pairsum_args(band, out=None, bandwidth=None, device=None):
+    """Context.banded_pairsum's arguments checked before any device call:
+    returns (n, K, dtype id, ld, lds) with lds None without out.  ValueError on
+    anything the call would refuse: band not a float32 or float16 [n, >= K + 1]
+    device tensor with contiguous rows, a bandwidth outside the band's columns,
+    out not a float64 [n, K + 1] device tensor with contiguous rows."""
+    return _band_out_args(band, out, bandwidth, device)
 
 
 def annot_matrix(annot, n_sites=None):
@@ -1607,6 +1841,139 @@ class Context:
               "wld_banded_solve_device")
         return out
 
+    def banded_pairsum(self, band, out=None, bandwidth=None):
+        """wld_banded_pairsum_device: the pair-sum table M of `band` — a [n, W]
+        float32 or float16 device tensor as banded_apply takes it (bandwidth
+        None: W - 1; column 0 and the elements with j + k >= n are never read,
+        NaN and +-inf count as 0) — as a float64 [n, K + 1] device tensor in
+        the same layout: M[j, k] is the sum of the band's entries (u, v) with
+        j <= u < v <= j + k, +0.0 where j + k >= n (out: such a tensor, rows may
+        be strided, overwritten; it must not overlap the band).  The bytes are
+        banded_pairsum_host's; two calls give identical bytes.  Returns (M,
+        LdPairsumInfo).  The tensors' pending work is synchronised first; needs
+        no load."""
+        import torch
+
+        n, K, dt, ld, lds = banded_pairsum_args(band, out, bandwidth, self.device)
+        if out is None:
+            out = torch.empty((n, K + 1), dtype=torch.float64, device=band.device)
+            lds = K + 1
+        info = BandedPairsumInfoC()
+        torch.cuda.synchronize(band.device)
+        check(lib().wld_banded_pairsum_device(self._h, ctypes.c_void_p(int(band.data_ptr())), dt, ld, n, K,
+                                              ctypes.c_void_p(int(out.data_ptr())), lds, ctypes.byref(info)),
+              "wld_banded_pairsum_device")
+        return out, LdPairsumInfo(bandwidth=int(info.bandwidth), nonfinite=int(info.nonfinite),
+                                  kernel_ms=float(info.kernel_ms))
+
+    def banded_omega(self, M, split, lo, hi, min_side=2, eps=1e-5, out=None):
+        """wld_banded_omega_device: the sweep scan of banded_omega_host on the
+        device, with the same bytes.  M: banded_pairsum's table, a float64
+        [n, K + 1] device tensor (rows may be strided).  split, lo, hi: uint32
+        or int32 device tensors, or lists / numpy arrays (copied to the
+        device); they are checked on the host before the call when they are
+        host arrays, and by the library on the device in either case.  out: a
+        dict of contiguous device tensors omega, zns (float64) and left, right
+        (int32 or uint32 storage) of n_splits entries to write into.  Returns
+        an LdOmega (numpy arrays)."""
+        import torch
+
+        _dev_tensor(M, "M", ("float64",), self.device)
+        shape = tuple(int(x) for x in M.shape)
+        if len(shape) != 2 or shape[0] < 1 or shape[1] < 1:
+            raise ValueError("M must be a [n, bandwidth + 1] tensor")
+        n, K = shape[0], shape[1] - 1
+        lds = _row_stride(M, K + 1, "M")
+        on_dev = [hasattr(x, "data_ptr") for x in (split, lo, hi)]
+        if any(on_dev) and not all(on_dev):
+            raise ValueError("split, lo and hi must all be device tensors or all host arrays")
+        if all(on_dev):
+            ts = []
+            for x, what in ((split, "split"), (lo, "lo"), (hi, "hi")):
+                _dev_tensor(x, what, ("int32", "uint32"), self.device)
+                if x.dim() != 1 or (x.shape[0] > 1 and x.stride(0) != 1):
+                    raise ValueError("%s must be a contiguous 1-D tensor" % what)
+                ts.append(x)
+            if not (ts[0].shape[0] == ts[1].shape[0] == ts[2].shape[0]) or ts[0].shape[0] < 1:
+                raise ValueError("split, lo and hi must have the same length, at least 1")
+            try:
+                min_side, eps = int(min_side), float(eps)
+            except (TypeError, ValueError):
+                raise ValueError("min_side must be an integer and eps a number")
+            if min_side < 2 or min_side > 0xFFFFFFFF or not np.isfinite(eps) or eps < 0:
+                raise ValueError("min_side must be at least 2 and eps finite and >= 0")
+        else:
+            c, l, h, min_side, eps = omega_args(n, K, split, lo, hi, min_side, eps)
+            ts = [torch.from_numpy(x.view(np.int32)).to(M.device) for x in (c, l, h)]
+        G = int(ts[0].shape[0])
+        if out is None:
+            out = {"omega": torch.empty(G, dtype=torch.float64, device=M.device),
+                   "zns": torch.empty(G, dtype=torch.float64, device=M.device),
+                   "left": torch.empty(G, dtype=torch.int32, device=M.device),
+                   "right": torch.empty(G, dtype=torch.int32, device=M.device)}
+        else:
+            for name, names in (("omega", ("float64",)), ("zns", ("float64",)), ("left", ("int32", "uint32")),
+                                ("right", ("int32", "uint32"))):
+                if name not in out:
+                    raise ValueError("out needs the tensors omega, zns, left and right")
+                _dev_tensor(out[name], "out[%r]" % name, names, self.device)
+                if tuple(out[name].shape) != (G,) or (G > 1 and out[name].stride(0) != 1):
+                    raise ValueError("out[%r] must be a contiguous [%d] tensor" % (name, G))
+        info = BandedOmegaInfoC()
+        torch.cuda.synchronize(M.device)
+        p = lambda t: ctypes.c_void_p(int(t.data_ptr()))  # noqa: E731
+        check(lib().wld_banded_omega_device(self._h, p(M), lds, n, K, p(ts[0]), p(ts[1]), p(ts[2]), G, min_side, eps,
+                                            p(out["omega"]), p(out["left"]), p(out["right"]), p(out["zns"]),
+                                            ctypes.byref(info)), "wld_banded_omega_device")
+        u32 = lambda t: t.cpu().numpy().view(np.uint32).copy()  # noqa: E731
+        return LdOmega(split=u32(ts[0]), lo=u32(ts[1]), hi=u32(ts[2]), omega=out["omega"].cpu().numpy(),
+                       left=u32(out["left"]), right=u32(out["right"]), zns=out["zns"].cpu().numpy(), min_side=min_side,
+                       eps=eps, evaluated=int(info.evaluated), skipped=int(info.skipped), kernel_ms=float(info.kernel_ms))
+
+    def run_omega(self, n_grid=0, max_side=None, min_side=2, max_distance=None, eps=1e-5, dtype="float32"):
+        """wld_run_omega: the whole sweep scan on the loaded set under the
+        context's CURRENT window: the splits of omega_splits(site_map, n_grid,
+        max_side, max_distance), an r2 band with zero_missing of the width the
+        window needs (dtype "float32" or "float16"), its pair sums and the scan.
+        A window that drops pairs some split needs is refused (WldError): a
+        window of max_sites 2 max_side - 1 and no max_distance always
+        suffices.  Returns an LdOmega with position, n_sites, bandwidth, band
+        and sums."""
+        if max_side is None:
+            raise ValueError("max_side is required")
+        if dtype not in _MATRIX_DTYPES:
+            raise ValueError('dtype must be "float32" or "float16"')
+        try:
+            n_grid, max_side, min_side, D, eps = int(n_grid), int(max_side), int(min_side), int(max_distance or 0), float(eps)
+        except (TypeError, ValueError):
+            raise ValueError("n_grid, max_side, min_side and max_distance must be integers and eps a number")
+        if n_grid < 0 or n_grid > 0xFFFFFFFF or max_side < 1 or max_side > 0xFFFFFFFF or D < 0 or D >= 1 << 64:
+            raise ValueError("n_grid, max_side (at least 1) and max_distance must be non-negative integers")
+        if min_side < 2 or min_side > 0xFFFFFFFF or not np.isfinite(eps) or eps < 0:
+            raise ValueError("min_side must be at least 2 and eps finite and >= 0")
+        o = OmegaC()
+        check(lib().wld_run_omega(self._h, n_grid, max_side, min_side, D, eps, _MATRIX_DTYPES[dtype], ctypes.byref(o)),
+              "wld_run_omega")
+        G = int(o.n_splits)
+
+        def grab(p, dt):
+            return np.ctypeslib.as_array(p, shape=(G,)).astype(dt, copy=True)
+
+        b = o.band
+        res = LdOmega(position=grab(o.position, np.uint64), split=grab(o.split, np.uint32), lo=grab(o.lo, np.uint32),
+                      hi=grab(o.hi, np.uint32), omega=grab(o.omega, np.float64), left=grab(o.left, np.uint32),
+                      right=grab(o.right, np.uint32), zns=grab(o.zns, np.float64), min_side=min_side, eps=eps,
+                      evaluated=int(o.scan.evaluated), skipped=int(o.scan.skipped), kernel_ms=float(o.scan.kernel_ms),
+                      n_sites=int(o.n_sites), bandwidth=int(o.bandwidth),
+                      band=LdBandedInfo(rows=(int(b.row_begin), int(b.row_end)), bandwidth=int(b.bandwidth), stat="r2",
+                                        dtype=dtype, zero_missing=True, pairs=int(b.pairs), none_pairs=int(b.none_pairs),
+                                        nonfinite_pairs=int(b.nonfinite_pairs), counted_pairs=int(b.counted_pairs),
+                                        tiles=int(b.tiles), kernel_ms=float(b.kernel_ms)),
+                      sums=LdPairsumInfo(bandwidth=int(o.sums.bandwidth), nonfinite=int(o.sums.nonfinite),
+                                         kernel_ms=float(o.sums.kernel_ms)))
+        lib().wld_omega_free(ctypes.byref(o))
+        return res
+
     def run_partners(self, k, r2_threshold, chunk_begin=0, chunk_end=0):
         """wld_run_partners: for every LOADED site its best k partners (r2 >
         r2_threshold, r2 descending then partner ascending) among the pairs of
@@ -1999,6 +2366,37 @@ def ld_banded(site_set, weights, bandwidth=None, stat="r", dtype="float32", zero
     sm = site_set.site_map
     sites = np.arange(n, dtype=np.uint64) if sm is None else np.asarray(sm, dtype=np.uint64).copy()
     return m, info, sites
+
+
+def ld_omega(site_set, weights, n_grid=0, max_side=None, min_side=2, max_distance=None, eps=1e-5, dtype="float32",
+             ctx=None):
+    """A selective-sweep scan of site_set (not in the reference; OmegaPlus):
+    Kim and Nielsen's omega, maximised per split over flanks of min_side to
+    max_side sites, and Kelly's ZnS of each split's largest window.  Loads the
+    set and runs Context.run_omega under the window max_sites = 2 max_side - 1,
+    which it sets itself (the context's own window is restored afterwards).
+    n_grid 0 scans every split, n_grid >= 1 that many equidistant positions;
+    max_distance limits the flanks in coordinates as well.  Returns an LdOmega
+    with site_map, the set's parent coordinates (None without a map)."""
+    if max_side is None:
+        raise ValueError("max_side is required")
+    w = np.ascontiguousarray(weights, dtype=np.float32)
+    if w.size != site_set.n_seqs():
+        raise ValueError("weights must have n_seqs entries")
+    max_side = int(max_side)
+    if max_side < 1 or max_side > 0x7FFFFFFF:
+        raise ValueError("max_side must be at least 1")
+    ctx = ctx or default_context()
+    before = ctx.window()
+    ctx.set_window(None, 2 * max_side - 1)
+    try:
+        sm = site_set.site_map
+        ctx.load(site_set.buffer, w, sm)
+        res = ctx.run_omega(n_grid, max_side, min_side, max_distance, eps, dtype)
+    finally:
+        ctx.set_window(*before)
+    res.site_map = sm
+    return res
 
 
 def ld_prune(site_set, weights, r2_threshold, priority=None, max_distance=None, max_sites=None, ctx=None):

@@ -32,6 +32,7 @@
 #include "partners_plan.hpp"
 #include "prune_plan.hpp"
 #include "targets_plan.hpp"
+#include "banded_omega_plan.hpp"
 #include "kernels.hpp"
 #include "fp6_scale.hpp"
 
@@ -262,6 +263,11 @@ struct wld_ctx {
     DevBuf chol_status;
     hipEvent_t ev_chol[2] = {};
 
+    // wld_banded_pairsum_device / wld_banded_omega_device: the words {nonfinite,
+    // evaluated, skipped, status} and the two events around a call's launches
+    DevBuf om_words;
+    hipEvent_t ev_om[2] = {};
+
     // wld_run_partners: its own tile list, a batch's staging (entries and
     // counts), the batch's CSR, the running lists and the words {classes[3],
     // guard}; its events are created per call
@@ -303,7 +309,7 @@ struct wld_ctx {
         // buffers: it completes before they are freed
         if (stream && stream != own_stream) (void)hipStreamSynchronize(stream);
         DevBuf *all[] = {&keep, &htab, &htab_kept, &site_index, &raw, &wraw, &codes, &w_pad, &wstats, &site_ok, &site_map, &planes, &frag, &rcodes, &rw, &w6, &w4, &f6a, &f6b, &f6marg, &f6rec, &i8a, &i8b, &tiles, &cand, &f6_pairs, &fp6_probe_buf,
-                         &seg_cnt, &seg_off, &chunk_total, &chunk_base, &counters, &chunk_left, &prog_n, &win_hi, &win_pairs, &sum_buf, &heat_buf, &heat_tiles, &heat_map, &an_buf, &an_tiles, &an_img, &mx_lists, &mx_cnt, &chol_status, &pt_tiles, &pt_stage, &pt_cnt, &pt_csr, &pt_run, &pt_words, &blk_brk, &blk_acc, &blk_map, &blk_tiles, &st_a, &st_b, &st_d,
+                         &seg_cnt, &seg_off, &chunk_total, &chunk_base, &counters, &chunk_left, &prog_n, &win_hi, &win_pairs, &sum_buf, &heat_buf, &heat_tiles, &heat_map, &an_buf, &an_tiles, &an_img, &mx_lists, &mx_cnt, &chol_status, &om_words, &pt_tiles, &pt_stage, &pt_cnt, &pt_csr, &pt_run, &pt_words, &blk_brk, &blk_acc, &blk_map, &blk_tiles, &st_a, &st_b, &st_d,
                          &st_dp, &st_r2, &out_a, &out_b, &out_d, &out_dp, &out_r2};
         for (DevBuf *b : all) release(*b);
         for (DevBuf *b : tg.all()) release(*b);
@@ -320,6 +326,8 @@ struct wld_ctx {
         for (auto &e : ev_mx)
             if (e) (void)hipEventDestroy(e);
         for (auto &e : ev_chol)
+            if (e) (void)hipEventDestroy(e);
+        for (auto &e : ev_om)
             if (e) (void)hipEventDestroy(e);
         for (auto &e : ev_blk)
             if (e) (void)hipEventDestroy(e);
@@ -2916,13 +2924,13 @@ const uint32_t *banded_limits(wld_ctx *c) { return window_on(c) ? c->win_hi_host
 // state, then the arguments (matrix_banded_plan::validate), then the load's
 // weights.  *q: the rows with their end resolved.
 int banded_check(wld_ctx *c, const char *who, uint32_t rb, uint32_t re, uint32_t K, int stat, int dtype, int flags,
-                 const void *dst, size_t ld, mbp::Rows *q) {
+                 bool have_dst, size_t ld, mbp::Rows *q) {
     WLD_TRY(set_dev(c));
     if (!c->loaded) return fail(WLD_E_STATE, "%s before wld_load", who);
     if (c->pend.active) return fail(WLD_E_STATE, "%s during a run", who);
     if (window_on(c) && c->win_hi_host.size() != c->L) return fail(WLD_E_STATE, "internal: the window has no plan");
     const uint32_t needed = mbp::width((uint32_t)std::min<size_t>(c->L, mbp::kMaxSites), banded_limits(c));
-    switch (mbp::validate(c->L, rb, re, K, needed, stat, dtype, flags, ld, dst != nullptr, q)) {
+    switch (mbp::validate(c->L, rb, re, K, needed, stat, dtype, flags, ld, have_dst, q)) {
         case mbp::kOk: break;
         case mbp::kStat: return fail(WLD_E_ARG, "%s: unknown stat %d", who, stat);
         case mbp::kDtype: return fail(WLD_E_ARG, "%s: unknown dtype %d", who, dtype);
@@ -3037,8 +3045,8 @@ int wld_run_matrix_banded_device(wld_ctx *c, uint32_t row_begin, uint32_t row_en
     memset(out, 0, sizeof(*out));
     if (!c) return fail(WLD_E_ARG, "null context");
     mbp::Rows q{};
-    WLD_TRY(banded_check(c, "wld_run_matrix_banded_device", row_begin, row_end, bandwidth, stat, dtype, flags, d_dst, ld,
-                         &q));
+    WLD_TRY(banded_check(c, "wld_run_matrix_banded_device", row_begin, row_end, bandwidth, stat, dtype, flags,
+                         d_dst != nullptr, ld, &q));
     banded_info_init(out, q, bandwidth, stat, dtype, flags);
     WLD_TRY(banded_strip(c, q, bandwidth, stat, dtype, flags, d_dst, ld, out));
     return banded_account(c, q, out);
@@ -3050,7 +3058,8 @@ int wld_run_matrix_banded(wld_ctx *c, uint32_t row_begin, uint32_t row_end, uint
     memset(out, 0, sizeof(*out));
     if (!c) return fail(WLD_E_ARG, "null context");
     mbp::Rows q{};
-    WLD_TRY(banded_check(c, "wld_run_matrix_banded", row_begin, row_end, bandwidth, stat, dtype, flags, h_dst, ld, &q));
+    WLD_TRY(banded_check(c, "wld_run_matrix_banded", row_begin, row_end, bandwidth, stat, dtype, flags, h_dst != nullptr,
+                         ld, &q));
     banded_info_init(out, q, bandwidth, stat, dtype, flags);
     const size_t eb = dtype == WLD_MATRIX_F16 ? 2 : 4, width = (size_t)bandwidth + 1;
     std::vector<mbp::Rows> strips;
@@ -3167,6 +3176,261 @@ int wld_banded_solve_device(wld_ctx *c, const double *d_factor, size_t ldf, uint
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (kernel_ms) *kernel_ms = event_ms(c->ev_chol[0], c->ev_chol[1]);
     return WLD_OK;
+}
+
+namespace {
+namespace bop = banded_omega_plan;
+
+// the words of the sweep-scan calls on the device
+struct OmegaWords {
+    unsigned long long nonfinite, evaluated, skipped;
+    uint32_t status, pad;
+};
+
+// the pair sums' launches and their counter, after the arguments were checked
+int pairsum_run(wld_ctx *c, const void *d_band, int band_dtype, size_t ld, uint32_t n, uint32_t K, double *d_sums,
+                size_t lds, wld_banded_pairsum_info *out) {
+    for (auto &e : c->ev_om)
+        if (!e) HIP_TRY(hipEventCreate(&e));
+    WLD_TRY(ensure(c->om_words, sizeof(OmegaWords)));
+    OmegaWords *w = ptr<OmegaWords>(c->om_words);
+    HIP_TRY(hipMemsetAsync(w, 0, sizeof(OmegaWords), c->stream));
+    const BandedPairsumArgs a{d_band, ld, band_dtype == WLD_MATRIX_F16, n, K, d_sums, lds, &w->nonfinite};
+    HIP_TRY(hipEventRecord(c->ev_om[0], c->stream));
+    launch_banded_pairsum(a, c->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c->ev_om[1], c->stream));
+    OmegaWords h{};
+    HIP_TRY(hipMemcpyAsync(&h, w, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    out->n_sites = n;
+    out->bandwidth = K;
+    out->nonfinite = h.nonfinite;
+    out->kernel_ms = event_ms(c->ev_om[0], c->ev_om[1]);
+    return WLD_OK;
+}
+
+// the scan's check launch, then the scan itself; the arguments were checked
+int omega_run(wld_ctx *c, const char *who, const double *d_sums, size_t lds, uint32_t n, uint32_t K,
+              const uint32_t *d_split, const uint32_t *d_lo, const uint32_t *d_hi, uint32_t n_splits, uint32_t min_side,
+              double eps, double *d_omega, uint32_t *d_left, uint32_t *d_right, double *d_zns,
+              wld_banded_omega_info *out) {
+    for (auto &e : c->ev_om)
+        if (!e) HIP_TRY(hipEventCreate(&e));
+    WLD_TRY(ensure(c->om_words, sizeof(OmegaWords)));
+    OmegaWords *w = ptr<OmegaWords>(c->om_words);
+    OmegaWords h{};
+    h.status = 0xFFFFFFFFu;
+    HIP_TRY(hipMemcpyAsync(w, &h, sizeof(h), hipMemcpyHostToDevice, c->stream));
+    const BandedOmegaArgs a{d_sums, lds,     n,      K,       d_split, d_lo,          d_hi,      n_splits, min_side,
+                            eps,    d_omega, d_left, d_right, d_zns,   &w->evaluated, &w->status};
+    launch_banded_omega_check(a, c->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(&h, w, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (h.status != 0xFFFFFFFFu)
+        return fail(WLD_E_ARG, "%s: split %u breaks lo <= split < hi < %u sites or hi - lo <= bandwidth %u", who, h.status, n,
+                    K);
+    HIP_TRY(hipEventRecord(c->ev_om[0], c->stream));
+    launch_banded_omega(a, c->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c->ev_om[1], c->stream));
+    HIP_TRY(hipMemcpyAsync(&h, w, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    out->n_splits = n_splits;
+    out->evaluated = h.evaluated;
+    out->skipped = h.skipped;
+    out->kernel_ms = event_ms(c->ev_om[0], c->ev_om[1]);
+    return WLD_OK;
+}
+
+// the refusal of a site_map that descends at i (banded_omega_plan::first_descent)
+int omega_map_descends(const char *who, uint32_t i, uint64_t at_i, uint64_t before) {
+    return fail(WLD_E_ARG, "%s needs a non-decreasing site_map: site_map[%u] = %llu < site_map[%u] = %llu", who, i,
+                (unsigned long long)at_i, i - 1, (unsigned long long)before);
+}
+
+int omega_check_params(const char *who, uint32_t min_side, double eps) {
+    if (min_side < 2) return fail(WLD_E_ARG, "%s: min_side %u is below 2", who, min_side);
+    if (!std::isfinite(eps) || eps < 0.0) return fail(WLD_E_ARG, "%s: eps must be finite and >= 0", who);
+    return WLD_OK;
+}
+
+// the buffers a wld_run_omega call owns on the device, released on every path
+struct OmegaBufs {
+    DevBuf band, sums, in, out;
+    ~OmegaBufs() {
+        for (DevBuf *b : {&band, &sums, &in, &out}) release(*b);
+    }
+};
+}  // namespace
+
+int wld_banded_pairsum_device(wld_ctx *c, const void *d_band, int band_dtype, size_t ld, uint32_t n_sites,
+                              uint32_t bandwidth, double *d_sums, size_t lds_, wld_banded_pairsum_info *out) {
+    const char *who = "wld_banded_pairsum_device";
+    if (!c) return fail(WLD_E_ARG, "null context");
+    WLD_TRY(set_dev(c));
+    if (c->pend.active) return fail(WLD_E_STATE, "%s during a run", who);
+    if (!d_band || !d_sums || !out)
+        return fail(WLD_E_ARG, "%s: null %s", who, !d_band ? "band" : !d_sums ? "sums" : "info");
+    if (band_dtype != WLD_MATRIX_F32 && band_dtype != WLD_MATRIX_F16)
+        return fail(WLD_E_ARG, "%s: unknown band dtype %d", who, band_dtype);
+    if (!n_sites) return fail(WLD_E_ARG, "%s: no site", who);
+    if ((uint64_t)ld < (uint64_t)bandwidth + 1 || (uint64_t)lds_ < (uint64_t)bandwidth + 1)
+        return fail(WLD_E_ARG, "%s: ld %zu or lds %zu is below bandwidth + 1 = %llu", who, ld, lds_,
+                    (unsigned long long)bandwidth + 1);
+    {  // the extents [first element, one past the last element read or written)
+        const size_t esz = band_dtype == WLD_MATRIX_F16 ? 2 : 4;
+        const uintptr_t b0 = (uintptr_t)d_band, b1 = b0 + ((size_t)(n_sites - 1) * ld + bandwidth + 1) * esz;
+        const uintptr_t f0 = (uintptr_t)d_sums, f1 = f0 + ((size_t)(n_sites - 1) * lds_ + bandwidth + 1) * sizeof(double);
+        if (b0 < f1 && f0 < b1) return fail(WLD_E_ARG, "%s: the sums overlap the band", who);
+    }
+    return pairsum_run(c, d_band, band_dtype, ld, n_sites, bandwidth, d_sums, lds_, out);
+}
+
+int wld_banded_omega_device(wld_ctx *c, const double *d_sums, size_t lds_, uint32_t n_sites, uint32_t bandwidth,
+                            const uint32_t *d_split, const uint32_t *d_lo, const uint32_t *d_hi, uint32_t n_splits,
+                            uint32_t min_side, double eps, double *d_omega, uint32_t *d_left, uint32_t *d_right,
+                            double *d_zns, wld_banded_omega_info *out) {
+    const char *who = "wld_banded_omega_device";
+    if (!c) return fail(WLD_E_ARG, "null context");
+    WLD_TRY(set_dev(c));
+    if (c->pend.active) return fail(WLD_E_STATE, "%s during a run", who);
+    if (!d_sums || !d_split || !d_lo || !d_hi || !d_omega || !d_left || !d_right || !d_zns || !out)
+        return fail(WLD_E_ARG, "%s: null %s", who,
+                    !d_sums ? "sums" : !d_split || !d_lo || !d_hi ? "split array" : !out ? "info" : "output");
+    if (!n_sites) return fail(WLD_E_ARG, "%s: no site", who);
+    if (!n_splits) return fail(WLD_E_ARG, "%s: no split", who);
+    if ((uint64_t)lds_ < (uint64_t)bandwidth + 1)
+        return fail(WLD_E_ARG, "%s: lds %zu is below bandwidth + 1 = %llu", who, lds_, (unsigned long long)bandwidth + 1);
+    WLD_TRY(omega_check_params(who, min_side, eps));
+    return omega_run(c, who, d_sums, lds_, n_sites, bandwidth, d_split, d_lo, d_hi, n_splits, min_side, eps, d_omega,
+                     d_left, d_right, d_zns, out);
+}
+
+uint64_t wld_omega_n_splits(uint32_t n_sites, uint32_t n_grid) { return n_sites < 2 ? 0 : bop::n_splits(n_sites, n_grid); }
+
+int wld_omega_splits(const uint64_t *site_map, uint32_t n_sites, uint32_t n_grid, uint32_t max_side,
+                     uint64_t max_distance, uint64_t *position, uint32_t *split, uint32_t *lo, uint32_t *hi) {
+    const char *who = "wld_omega_splits";
+    if (!position || !split || !lo || !hi) return fail(WLD_E_ARG, "%s: null output", who);
+    if (n_sites < 2) return fail(WLD_E_ARG, "%s: a split needs two sites, not %u", who, n_sites);
+    if (!max_side) return fail(WLD_E_ARG, "%s: max_side 0", who);
+    const uint32_t d = bop::first_descent(site_map, n_sites);
+    if (d < n_sites) return omega_map_descends(who, d, site_map[d], site_map[d - 1]);
+    bop::splits(site_map, n_sites, n_grid, max_side, max_distance, position, split, lo, hi);
+    return WLD_OK;
+}
+
+void wld_omega_free(wld_omega *o) {
+    if (!o) return;
+    free(o->position);
+    free(o->split);
+    free(o->lo);
+    free(o->hi);
+    free(o->omega);
+    free(o->left);
+    free(o->right);
+    free(o->zns);
+    memset(o, 0, sizeof(*o));
+}
+
+int wld_run_omega(wld_ctx *c, uint32_t n_grid, uint32_t max_side, uint32_t min_side, uint64_t max_distance, double eps,
+                  int band_dtype, wld_omega *out) {
+    const char *who = "wld_run_omega";
+    if (!out) return fail(WLD_E_ARG, "null out");
+    memset(out, 0, sizeof(*out));
+    if (!c) return fail(WLD_E_ARG, "null context");
+    WLD_TRY(set_dev(c));
+    if (!c->loaded) return fail(WLD_E_STATE, "%s before wld_load", who);
+    if (c->pend.active) return fail(WLD_E_STATE, "%s during a run", who);
+    if (!max_side) return fail(WLD_E_ARG, "%s: max_side 0", who);
+    WLD_TRY(omega_check_params(who, min_side, eps));
+    if (c->L < 2) return fail(WLD_E_ARG, "%s: a split needs two sites; %zu are loaded", who, c->L);
+    if (c->L > mbp::kMaxSites)
+        return fail(WLD_E_ARG, "%s: %zu loaded sites exceed the %llu that 16-bit tile indices address", who, c->L,
+                    (unsigned long long)mbp::kMaxSites);
+    if (window_on(c) && c->win_hi_host.size() != c->L) return fail(WLD_E_STATE, "internal: the window has no plan");
+    const uint32_t n = (uint32_t)c->L;
+    const uint32_t K = mbp::width(n, banded_limits(c));
+    mbp::Rows q{};
+    // (the destination is the call's own buffer, allocated below)
+    WLD_TRY(banded_check(c, who, 0, 0, K, WLD_MATRIX_R2, band_dtype, WLD_MATRIX_ZERO_MISSING, true, (size_t)K + 1, &q));
+    const uint64_t total = bop::n_splits(n, n_grid);
+    if (total > 0xFFFFFFFFull) return fail(WLD_E_ARG, "%s: too many splits", who);
+    const uint32_t G = (uint32_t)total;
+    // the results' host arrays double as the splits' staging
+    out->position = (uint64_t *)malloc(G * sizeof(uint64_t));
+    out->split = (uint32_t *)malloc(G * sizeof(uint32_t));
+    out->lo = (uint32_t *)malloc(G * sizeof(uint32_t));
+    out->hi = (uint32_t *)malloc(G * sizeof(uint32_t));
+    out->omega = (double *)malloc(G * sizeof(double));
+    out->left = (uint32_t *)malloc(G * sizeof(uint32_t));
+    out->right = (uint32_t *)malloc(G * sizeof(uint32_t));
+    out->zns = (double *)malloc(G * sizeof(double));
+    // a failed call returns no arrays (the message survives the frees)
+    auto refuse = [&](int st) {
+        if (st == WLD_OK) return st;
+        const std::string msg = wld_last_error();
+        wld_omega_free(out);
+        return fail(st, "%s", msg.c_str());
+    };
+    if (!out->position || !out->split || !out->lo || !out->hi || !out->omega || !out->left || !out->right || !out->zns) {
+        wld_omega_free(out);
+        return fail(WLD_E_OOM, "%s: host allocation of %u splits failed", who, G);
+    }
+    const uint32_t *pos = c->has_pos ? c->pos_host.data() : nullptr;
+    const uint32_t d = bop::first_descent(pos, n);
+    if (d < n) return refuse(omega_map_descends(who, d, pos[d], pos[d - 1]));
+    bop::splits(pos, n, n_grid, max_side, max_distance, out->position, out->split, out->lo, out->hi);
+    // every pair of lo..hi must be in the window: hi[] is non-decreasing, so
+    // lo's own limit decides
+    const uint32_t *lim = banded_limits(c);
+    for (uint32_t g = 0; g < G; ++g) {
+        const uint32_t reach = lim ? lim[out->lo[g]] : n - 1;
+        if (reach < out->hi[g] || out->hi[g] - out->lo[g] > K) {
+            const uint32_t lo = out->lo[g], hi = out->hi[g];
+            wld_omega_free(out);
+            return fail(WLD_E_ARG, "%s: the context's window drops pairs the scan needs (split %u spans the sites %u..%u, "
+                                   "the window ends site %u's partners at %u): max_side %u needs a window of max_sites %llu "
+                                   "and no max_distance",
+                        who, g, lo, hi, lo, reach, max_side, 2ull * max_side - 1);
+        }
+    }
+    OmegaBufs b;
+    const size_t eb = band_dtype == WLD_MATRIX_F16 ? 2 : 4, width = (size_t)K + 1;
+    int st = ensure(b.band, (size_t)n * width * eb);
+    if (st == WLD_OK) st = ensure(b.sums, (size_t)n * width * sizeof(double));
+    if (st == WLD_OK) st = ensure(b.in, (size_t)G * 3 * sizeof(uint32_t));
+    if (st == WLD_OK) st = ensure(b.out, (size_t)G * (2 * sizeof(double) + 2 * sizeof(uint32_t)));
+    if (st != WLD_OK) return refuse(st);
+    out->n_sites = n, out->bandwidth = K, out->n_splits = G, out->min_side = min_side;
+    banded_info_init(&out->band, q, K, WLD_MATRIX_R2, band_dtype, WLD_MATRIX_ZERO_MISSING);
+    st = banded_strip(c, q, K, WLD_MATRIX_R2, band_dtype, WLD_MATRIX_ZERO_MISSING, b.band.p, width, &out->band);
+    if (st == WLD_OK) st = banded_account(c, q, &out->band);
+    if (st == WLD_OK) st = pairsum_run(c, b.band.p, band_dtype, width, n, K, ptr<double>(b.sums), width, &out->sums);
+    if (st != WLD_OK) return refuse(st);
+    uint32_t *d_split = ptr<uint32_t>(b.in), *d_lo = d_split + G, *d_hi = d_lo + G;
+    double *d_omega = ptr<double>(b.out), *d_zns = d_omega + G;
+    uint32_t *d_left = reinterpret_cast<uint32_t *>(d_zns + G), *d_right = d_left + G;
+    auto copy = [&](void *dst, const void *src, size_t bytes, hipMemcpyKind kind) {
+        if (st != WLD_OK) return;
+        const hipError_t e = hipMemcpyAsync(dst, src, bytes, kind, c->stream);
+        if (e != hipSuccess) st = fail(WLD_E_HIP, "%s copy: %s", who, hipGetErrorString(e));
+    };
+    copy(d_split, out->split, G * sizeof(uint32_t), hipMemcpyHostToDevice);
+    copy(d_lo, out->lo, G * sizeof(uint32_t), hipMemcpyHostToDevice);
+    copy(d_hi, out->hi, G * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (st == WLD_OK)
+        st = omega_run(c, who, ptr<double>(b.sums), width, n, K, d_split, d_lo, d_hi, G, min_side, eps, d_omega, d_left,
+                       d_right, d_zns, &out->scan);
+    copy(out->omega, d_omega, G * sizeof(double), hipMemcpyDeviceToHost);
+    copy(out->zns, d_zns, G * sizeof(double), hipMemcpyDeviceToHost);
+    copy(out->left, d_left, G * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    copy(out->right, d_right, G * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    // always: a copy enqueued before a failure may still be writing the host arrays refuse() frees
+    if (hipStreamSynchronize(c->stream) != hipSuccess && st == WLD_OK) st = fail(WLD_E_HIP, "%s: synchronize failed", who);
+    return refuse(st);
 }
 
 namespace {

@@ -62,6 +62,11 @@
 //                      the [n, K + 1] upper band of every site of interest
 //                      (wld_run_matrix_banded; element [i, k] = entry (i, i + k),
 //                      K the width the window needs) instead of the square
+//   --omega-output FILE --omega-max-side S [--omega-grid G] [--omega-min-side M]
+//   [--omega-max-distance D] [--omega-eps E]
+//                      a selective-sweep scan (wld_run_omega): TSV position, left,
+//                      right, omega, zns per split; sets the window to 2 S - 1 sites
+//                      for the scan unless --max-sites is given
 //   --annot-input FILE       partitioned LD scores (wld_run_annot_scores): FILE is
 //   --annot-score-output FILE  a TSV "site<TAB>name1<TAB>..." of per-site
 //   --annot-self             annotations by parent index; the output has site,
@@ -293,6 +298,13 @@ struct Opt {
     // --annot-input / --annot-score-output / --annot-self: wld_run_annot_scores
     std::string annot_input, annot_score_output;
     bool annot_self = false;
+    // --omega-output / --omega-max-side / --omega-grid / --omega-min-side / --omega-max-distance / --omega-eps: wld_run_omega
+    std::string omega_output;
+    uint32_t omega_max_side = 0, omega_grid = 0, omega_min_side = 2;
+    uint64_t omega_max_distance = 0;
+    double omega_eps = 1e-5;
+    bool have_omega_max_side = false;
+    std::string omega_opt;  // the first --omega-* option given besides --omega-output
 };
 
 void usage(FILE *f) {
@@ -406,7 +418,22 @@ void usage(FILE *f) {
             "                                             to (site, partners, <name>_l2 per annotation: the sum of r2\n"
             "                                             times the partner's annotation over every in-window partner,\n"
             "                                             no threshold); needs --annot-input; obeys --max-distance,\n"
-            "                                             --max-sites and --devices; --pair-output may then be left out\n");
+            "                                             --max-sites and --devices; --pair-output may then be left out\n"
+            "        --omega-output <omega-output>        (addition) Filename to write a selective-sweep scan to, Tab\n"
+            "                                             Separated (position, left, right, omega, zns): per position\n"
+            "                                             Kim and Nielsen's omega maximised over the flank borders,\n"
+            "                                             the borders' parent coordinates (NA without a candidate) and\n"
+            "                                             Kelly's ZnS of the largest window; omega and zns printed\n"
+            "                                             with 17 significant digits; needs --omega-max-side; sets\n"
+            "                                             the window to 2 * max-side - 1 sites unless --max-sites is\n"
+            "                                             given; --pair-output may then be left out\n"
+            "        --omega-max-side <omega-max-side>    (addition) the most sites a flank may hold\n"
+            "        --omega-grid <omega-grid>            (addition) scan this many equidistant positions [default: 0,\n"
+            "                                             every split between two sites of interest]\n"
+            "        --omega-min-side <omega-min-side>    (addition) the fewest sites a flank may hold [default: 2]\n"
+            "        --omega-max-distance <omega-max-distance>  (addition) a flank reaches at most this far from the\n"
+            "                                             position, in parent coordinates [default: 0, no limit]\n"
+            "        --omega-eps <omega-eps>              (addition) added to the cross term of omega [default: 1e-5]\n");
 }
 
 [[noreturn]] void arg_error(const char *msg, const char *arg) {
@@ -622,6 +649,29 @@ Opt parse(int argc, char **argv) {
             o.matrix_zero_missing = true;
         } else if (a == "--matrix-banded") {
             o.matrix_banded = true;
+        } else if (a == "--omega-output") {
+            o.omega_output = need("--omega-output");
+        } else if (a == "--omega-max-side" || a == "--omega-grid" || a == "--omega-min-side" || a == "--omega-max-distance") {
+            const std::string name = a;
+            const std::string v = need(name.c_str());
+            const bool wide = name == "--omega-max-distance";
+            if (v.empty() || v.find_first_not_of("0123456789") != std::string::npos || v.size() > (wide ? 19u : 9u))
+                arg_error(("Invalid value for '" + name + "':").c_str(), v.c_str());
+            const uint64_t x = strtoull(v.c_str(), nullptr, 10);
+            if ((name == "--omega-max-side" && x < 1) || (name == "--omega-min-side" && x < 2))
+                arg_error(("Invalid value for '" + name + "' (too small):").c_str(), v.c_str());
+            if (o.omega_opt.empty()) o.omega_opt = name;
+            if (name == "--omega-max-side") o.omega_max_side = (uint32_t)x, o.have_omega_max_side = true;
+            else if (name == "--omega-grid") o.omega_grid = (uint32_t)x;
+            else if (name == "--omega-min-side") o.omega_min_side = (uint32_t)x;
+            else o.omega_max_distance = x;
+        } else if (a == "--omega-eps") {
+            const std::string v = need("--omega-eps");
+            char *end = nullptr;
+            o.omega_eps = strtod(v.c_str(), &end);
+            if (v.empty() || !end || *end || !(o.omega_eps >= 0.0) || o.omega_eps > 1.79769313486231570815e308)
+                arg_error("Invalid value for '--omega-eps' (finite, at least 0):", v.c_str());
+            if (o.omega_opt.empty()) o.omega_opt = "--omega-eps";
         } else if (a == "--annot-input") {
             o.annot_input = need("--annot-input");
         } else if (a == "--annot-score-output") {
@@ -683,10 +733,16 @@ Opt parse(int argc, char **argv) {
         arg_error("The argument '--matrix-banded' cannot be used with", "--matrix-region (the band holds every site of interest)");
     if (o.matrix_banded && !o.max_distance && !o.max_sites)
         arg_error("The argument '--matrix-banded' needs", "--max-distance or --max-sites (without a window the band is the square)");
+    if (!o.omega_output.empty() && !o.have_omega_max_side)
+        arg_error("The following required arguments were not provided:", "--omega-max-side <omega-max-side>");
+    if (o.omega_output.empty() && !o.omega_opt.empty())
+        arg_error(("The argument '" + o.omega_opt + "' needs").c_str(), "--omega-output <omega-output>");
+    if (!o.omega_output.empty() && o.devices.size() > 1)
+        arg_error("The argument '--omega-output' cannot be used with", "--devices (the sweep scan runs on one device)");
     if (!o.matrix_output.empty() && o.devices.size() > 1)
         arg_error("The argument '--matrix-output' cannot be used with", "--devices (the LD matrix runs on one device)");
     if (!have_pair && !ld_sel && o.partners_output.empty() && o.blocks_output.empty() && o.annot_score_output.empty() &&
-        o.matrix_output.empty())
+        o.matrix_output.empty() && o.omega_output.empty())
         arg_error("The following required arguments were not provided:", "--pair-output <pair-output>");
     if (!o.have_ld_sites_r2) o.ld_sites_r2 = o.r2_threshold;
     if (!o.have_partners_r2) o.partners_r2 = o.r2_threshold;
@@ -1373,6 +1429,53 @@ void write_matrix(const Opt &opt, wld_ctx *ctx, const std::vector<uint64_t> &par
     write_all(opt.matrix_output, out, nullptr, 0);
 }
 
+// --omega-output: the sweep scan of the loaded set (wld_run_omega), one line per
+// position: the position and the best borders in parent coordinates (NA where
+// no candidate had a positive cross term), omega and zns with 17 significant
+// digits, which round-trip the f64 bits.  Without --max-sites the window is set
+// to the 2 * max-side - 1 sites the scan needs for this call and put back.
+void write_omega(const Opt &opt, wld_ctx *ctx, const std::vector<uint64_t> &parent) {
+    if (opt.omega_output.empty()) return;
+    using clk = std::chrono::steady_clock;
+    const auto sw = clk::now();
+    uint64_t win_d = 0, win_k = 0;
+    int st = wld_get_window(ctx, &win_d, &win_k);
+    if (st != WLD_OK) die(st, "get_window");
+    if (!opt.max_sites && (st = wld_set_window(ctx, win_d, 2ull * opt.omega_max_side - 1)) != WLD_OK) die(st, "set_window");
+    wld_omega r;
+    st = wld_run_omega(ctx, opt.omega_grid, opt.omega_max_side, opt.omega_min_side, opt.omega_max_distance, opt.omega_eps,
+                       WLD_MATRIX_F32, &r);
+    if (st != WLD_OK) die(st, "run_omega");
+    if (!opt.max_sites && (st = wld_set_window(ctx, win_d, win_k)) != WLD_OK) die(st, "set_window");
+    INFO("Scanned %u positions for sweeps: %s border pairs evaluated, %s skipped, in %s", r.n_splits,
+         human((double)r.scan.evaluated).c_str(), human((double)r.scan.skipped).c_str(),
+         fmt_duration(clk::now() - sw).c_str());
+    INFO("Writing output to %s", debug_path(opt.omega_output).c_str());
+    std::string out = "position\tleft\tright\tomega\tzns\n";
+    char line[200];
+    for (uint32_t g = 0; g < r.n_splits; ++g) {
+        const bool none = r.left[g] == 0xFFFFFFFFu && r.right[g] == 0xFFFFFFFFu;  // (the library's "no candidate")
+        if (!none && (r.left[g] >= parent.size() || r.right[g] >= parent.size())) {
+            fprintf(stderr, "error: internal: split %u has the borders %u, %u of %zu sites\n", g, r.left[g], r.right[g],
+                    parent.size());
+            quit(1);
+        }
+        int m;
+        if (none) m = snprintf(line, sizeof line, "%" PRIu64 "\tNA\tNA\tnan\t%.17g\n", r.position[g], r.zns[g]);
+        else
+            m = snprintf(line, sizeof line, "%" PRIu64 "\t%" PRIu64 "\t%" PRIu64 "\t%.17g\t%.17g\n", r.position[g],
+                         parent[r.left[g]], parent[r.right[g]], r.omega[g], r.zns[g]);
+        out.append(line, (size_t)m);
+    }
+    FILE *f = fopen(opt.omega_output.c_str(), "wb");
+    const bool ok = f && fwrite(out.data(), 1, out.size(), f) == out.size();
+    if ((f && fclose(f) != 0) || !ok) {
+        fprintf(stderr, "Error: cannot write %s\n", opt.omega_output.c_str());
+        quit(1);
+    }
+    wld_omega_free(&r);
+}
+
 // main.rs:186-212 after the pair computation: timing logs, TSV, clean-up.
 int finish(const Opt &opt, wld_ctx *ctx, wld_pairs &pairs, std::chrono::steady_clock::duration dur,
            uint64_t total_pairs) {
@@ -1448,6 +1551,7 @@ int run_gpu_prepass(const Opt &opt, wld_siteset *siteset, wld_ctx *ctx, const an
     write_blocks(opt, ctx, parent);
     write_annot_scores(opt, ctx, annot_file, annot, parent);
     write_matrix(opt, ctx, parent);
+    write_omega(opt, ctx, parent);
     // (a FASTA set has no site_map: a kept site's parent index is its index in the unfiltered set)
     write_prune(opt, ctx, parent, siteset, std::vector<size_t>(parent.begin(), parent.end()));
     return finish(opt, ctx, pairs, dur, total_pairs);
@@ -1572,6 +1676,7 @@ int main(int argc, char **argv) {
     write_blocks(opt, ctx, parent);
     write_annot_scores(opt, ctx, annot_file, annot, parent);
     write_matrix(opt, ctx, parent);
+    write_omega(opt, ctx, parent);
     std::vector<size_t> self(L);
     for (size_t i = 0; i < L; ++i) self[i] = i;
     write_prune(opt, ctx, parent, filtered, self);

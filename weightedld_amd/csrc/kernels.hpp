@@ -304,6 +304,38 @@ struct BandedSolveArgs {
     uint32_t n_cols;
 };
 
+// The pair-sum table of a band (banded_omega.hip; wld_banded_pairsum_device):
+// sums ([n][lds] f64, the band's layout) := M, M[j][k] the sum of the band's
+// finite entries (u, v) with j <= u < v <= j + k; nonfinite counts the band
+// elements (k >= 1, j + k < n) that were NaN or +-inf and counted as +0.0.
+struct BandedPairsumArgs {
+    const void *band;
+    size_t ld;
+    bool band_f16;
+    uint32_t n, K;
+    double *sums;
+    size_t lds;
+    unsigned long long *nonfinite;
+};
+
+// A sweep scan over such a table (wld_banded_omega_device): per split g the
+// largest omega over the flank borders with its borders, and ZnS of [lo, hi];
+// counts: {evaluated, skipped} candidates; status: the first split that breaks
+// lo <= c < hi < n, hi - lo <= K (UINT32_MAX: none), written by the check launch.
+struct BandedOmegaArgs {
+    const double *sums;
+    size_t lds;
+    uint32_t n, K;
+    const uint32_t *split, *lo, *hi;
+    uint32_t n_splits, min_side;
+    double eps;
+    double *omega;
+    uint32_t *left, *right;
+    double *zns;
+    unsigned long long *counts;
+    uint32_t *status;
+};
+
 // The staging of one batch of a best-partner run (pair_partners.hip;
 // wld_run_partners; layout in partners_plan.hpp).  Tile position p of the
 // launch's list (p < n_tiles, the workgroup id) owns the parts (2 p + side) *
@@ -457,6 +489,15 @@ void launch_banded_apply(const BandedApplyArgs &a, hipStream_t st);
 // marches over the block rows, forward and/or backward.
 void launch_banded_chol(const BandedCholArgs &a, hipStream_t st);
 void launch_banded_solve(const BandedSolveArgs &a, hipStream_t st);
+
+// banded_omega.hip
+// launch_banded_pairsum: the row scan (P in place in a.sums), then the chain
+// scan (M in place, +0.0 tails); a.nonfinite zeroed by the caller.
+// launch_banded_omega_check writes a.status (set to UINT32_MAX by the caller);
+// launch_banded_omega runs one workgroup per split on splits the check passed.
+void launch_banded_pairsum(const BandedPairsumArgs &a, hipStream_t st);
+void launch_banded_omega_check(const BandedOmegaArgs &a, hipStream_t st);
+void launch_banded_omega(const BandedOmegaArgs &a, hipStream_t st);
 
 // pair_blocks.hip
 // The same sums over v's list: pass 1 (every tile of the range and window)
